@@ -2,19 +2,26 @@
 gradient all-reduce + Adam) at the paper-default configuration (BASELINE.json configs[1]):
 patch 24, res x2, per-GPU batch 8, 8 low-res + 4 hi-res ResBlocks, fp32, synthetic inputs resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `metric`, `value` (patches/s of the whole job), `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (milliseconds of one timed step) and the run's configuration.  --dump-outputs DIR writes
+what the last timed step computed (the per-sample loss it returned, the weights after its Adam update, its gradient) as
+DIR/<name>.npy; the inputs and the initial weights are seeded, so two builds can be compared output for output.  Everything else
+the benchmark measures runs only with --full: the per-kernel pass and the roofline objects, the rocprofv3 traffic passes, the
+secondary legs and the CPU baseline.
 
 N > 1: one rank per GPU, RCCL sum-all-reduce of the flat gradient.  Either launched by torch.distributed.run (RANK /
 WORLD_SIZE in the environment) or -- when those are absent -- bench.py re-executes itself under torch.distributed.run
 with N ranks.  Asking for more ranks than GPUs is a hard error (unless --oversubscribe, a launcher self-test that puts
 several ranks on one device over gloo and marks the line as such).
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (the 64->64 3x3x3 MFMA conv, shared by forward and
+Prints ONE JSON line on rank 0.  With --full: `roofline` is for the dominant kernel (the 64->64 3x3x3 MFMA conv, shared by forward and
 dgrad), `roofline_wgrad` for the second one (the 64->64 weight-gradient kernel); both from launch durations measured
 live by HIP events on the launch stream inside the timed region.  `achieved`/`frac` count the FLOPs the kernel EXECUTES on the
 matrix pipe (frac <= 1 = pipe utilisation); the fp32 kernels are Winograd kernels that execute half of the direct algorithm's
 multiplies, so the ALGORITHMIC rate (221 184 FLOP per voxel) is reported beside it as `algorithmic_achieved` /
-`algorithmic_frac` (> 1) / `algorithmic_speedup`.  At N=1, after the timed region: `cpu_baseline` (the same
+`algorithmic_frac` (> 1) / `algorithmic_speedup`.  At N=1 with --full, after the timed region: `cpu_baseline` (the same
 train step on the host cores: torch-CPU/oneDNN, plus the numpy oracle as a second figure) and `secondary` (a sustained run of
 >= 300 steps with per-step min/median/max, a loader-fed cfg2 run with the on-device input pipeline inside the timed loop, and a
 short cfg4 bf16 run).  At N>1 the line carries `per_rank_ms_per_step` and `allreduce_exposed_ms` (HIP events around the point
@@ -399,6 +406,35 @@ def timed_steps(step_fn, steps, warmup, parallel):
     return time.perf_counter() - t0
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def step_outputs(tc, loss):
+    """What the timed train step hands its caller, as host float32 arrays: the (B,) loss vector it returned, the flat weights after
+    its Adam update and the flat gradient it computed (on N > 1 the all-reduced sum).  Copied before anything runs another step."""
+    return {"loss": loss.detach().float().cpu().numpy(),
+            "weights": tc.model.flat_w.detach().float().cpu().numpy(),
+            "gradient": tc.model.flat_g.detach().float().cpu().numpy()}
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Writes every array as out_dir/<name>.npy (float32, float64 kept as is).  When the arrays together exceed `budget`, each one
+    larger than an equal share of it is replaced by a fixed sample of its flattened elements (indices drawn without replacement
+    by default_rng(crc32(name)), kept in ascending order): the same shape gives the same indices in every run."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        share = budget // len(arrays)
+        for k, a in arrays.items():
+            if a.nbytes > share:
+                n = share // a.itemsize
+                idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(a.size, n, replace=False))
+                arrays[k] = a.reshape(-1)[idx]
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def secondary_runs(trainer, parallel, device, P, R, B, LB, HB, sustained_steps=300):
     """Short extra measurements at N=1 (VERDICT r1 #5/#6), outside the headline timed region."""
     sec = {}
@@ -714,6 +750,13 @@ def main():
                     help="storage type of activations / activation gradients (bf16 = BASELINE.json configs[3] arithmetic)")
     ap.add_argument("--config", choices=["cfg2", "cfg4"], default="cfg2",
                     help="cfg2 = the headline workload (defaults above); cfg4 = patch 32, res x4, batch 4, bf16 (secondary metric)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, weights after Adam, gradient) as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the per-kernel pass and the roofline objects, the rocprofv3 traffic "
+                         "passes, the secondary legs and the CPU baseline (--no-cpu-baseline, --no-secondary, --event-steps, "
+                         "--sustained-steps and --pmc shape these)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--event-steps", type=int, default=5,
@@ -723,11 +766,15 @@ def main():
                     help="N>1: ONE all-reduce of the whole gradient buffer after backward instead of the three buckets started inside it")
     ap.add_argument("--pmc", dest="pmc", action="store_true", default=None,
                     help="N=1: measure roofline.traffic in this run (two extra rocprofv3 --pmc passes of 2 steps) instead of quoting profiles/ "
-                         "(default: on for the full default run when rocprofv3 is on the box, off with --no-secondary)")
+                         "(needs --full; default: on with --full when rocprofv3 is on the box, off with --no-secondary)")
     ap.add_argument("--no-pmc", dest="pmc", action="store_false")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="launcher self-test: allow more ranks than GPUs (ranks share devices, gloo with host staging); not a scaling number")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.pmc and not args.full:
+        ap.error("--pmc measures the roofline objects' traffic: it needs --full")
     if args.config == "cfg4":
         args.patch, args.res, args.batch, args.dtype = 32, 4, 4, "bf16"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -765,8 +812,10 @@ def main():
                                    bucketed_allreduce=not args.single_allreduce)
     tc.profile_allreduce = world > 1
     batch = synthetic_batch(B, P, R, 1234 + rank, device)
-    timer = LaunchTimer(tc.model.ops)
-    timer.install()
+    timer = None
+    if args.full:
+        timer = LaunchTimer(tc.model.ops)
+        timer.install()
 
     for _ in range(args.warmup):
         tc.train_step(batch)
@@ -775,17 +824,21 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        tc.train_step(batch)
+        loss = tc.train_step(batch)
     torch.cuda.synchronize()
     dt_local = time.perf_counter() - t0               # this rank's own work is done (before the closing barrier)
     parallel.barrier()
     dt = time.perf_counter() - t0
-    # The per-kernel pass, in steps of its own BEHIND the timed region: the product step runs the weight gradients on a second
-    # stream beside the dgrad chain (network.overlap_wgrad), and an event pair around a launch that shares the chip with another
-    # stream's kernel times neither.  Here everything is issued on one stream and every 64->64 launch is bracketed by HIP events
-    # on it; same kernels, same operands, same order within each stream as the timed steps.
-    per_kernel_ms = event_pass(tc, batch, timer, args.event_steps)
-    timer.uninstall()
+    if args.dump_outputs and rank == 0:               # before any further step changes the weights
+        dump_outputs(args.dump_outputs, step_outputs(tc, loss))
+    per_kernel_ms = None
+    if args.full:
+        # The per-kernel pass, in steps of its own BEHIND the timed region: the product step runs the weight gradients on a second
+        # stream beside the dgrad chain (network.overlap_wgrad), and an event pair around a launch that shares the chip with another
+        # stream's kernel times neither.  Here everything is issued on one stream and every 64->64 launch is bracketed by HIP events
+        # on it; same kernels, same operands, same order within each stream as the timed steps.
+        per_kernel_ms = event_pass(tc, batch, timer, args.event_steps)
+        timer.uninstall()
 
     dt = parallel.allreduce_sum_host([dt], op="max")[0]
     # N>1 diagnostics: every rank's own time to finish its K steps, and the EXPOSED gradient all-reduce time per step (HIP events
@@ -799,8 +852,8 @@ def main():
     # rank 0 assembles the headline object BEFORE the N > 1 secondary legs run: those legs use point-to-point RCCL traffic that no
     # multi-GPU box has exercised yet, and a watchdog prints the headline (with the failure noted) rather than lose it to a hang
     line = None
-    if args.pmc is None:                               # the driver-facing default run measures its own traffic figure where the line is made
-        args.pmc = not args.no_secondary and world == 1
+    if args.pmc is None:                               # a --full run measures its own traffic figure where the line is made
+        args.pmc = args.full and not args.no_secondary and world == 1
     if rank == 0:
         fwd_flop = fwd_flop_per_patch(tc.model.specs, P, R, LB)
         tr = CFG4_TRAFFIC if args.config == "cfg4" else ([] if bf16 else CFG2_TRAFFIC)
@@ -817,7 +870,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3,
-            "ms_per_step_one_stream": per_kernel_ms,          # the per-kernel pass (event records included): what the overlap buys is the difference
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -832,15 +884,17 @@ def main():
                                       if oversub else "RCCL sum all-reduce of the flat fp32 gradient (%d B) per step, %s"
                                       % (4 * (tc.model.n_params + 1), "3 buckets started inside backward" if tc.bucketed_allreduce
                                          else "one call after backward"))},
-            "roofline": roofline_obj(timer, "conv", bf16, "%s (3x3x3 64->64 forward + fused-dgrad%s launches%s)"
-                                     % (("conv64_bf16_kernel", "", "") if bf16 else
-                                        ("conv64_wino2d", "", ": conv64_wino2d_kernel forward, conv64_wino2d_shell_kernel fused dgrad = inner box + shell faces in one "
-                                         "launch; 2-D Winograd F(4,3) along H x F(4,3) along W, the faces F(4,3) along W")), tr),
-            "roofline_wgrad": roofline_obj(timer, "wgrad", bf16, "%s (3x3x3 64->64 weight gradient + partial reduction%s)"
-                                           % (("wgrad64_bf16_dma_kernel", "") if bf16 else ("wgrad64_wino_kernel", "; Winograd F(3,2) along D x F(3,4) along W")), tr),
             "train_step_tflops": args.steps * B * world / dt * 3.0 * fwd_flop / 1e12,
             "lib_source_stamp": build.source_stamp()[:16],          # sha256 prefix of csrc/ + include/fdn.h + flags the binary was built from
         }
+        if args.full:
+            line["ms_per_step_one_stream"] = per_kernel_ms          # the per-kernel pass (event records included): what the overlap buys is the difference
+            line["roofline"] = roofline_obj(timer, "conv", bf16, "%s (3x3x3 64->64 forward + fused-dgrad%s launches%s)"
+                                            % (("conv64_bf16_kernel", "", "") if bf16 else
+                                               ("conv64_wino2d", "", ": conv64_wino2d_kernel forward, conv64_wino2d_shell_kernel fused dgrad = inner box + shell faces in one "
+                                                "launch; 2-D Winograd F(4,3) along H x F(4,3) along W, the faces F(4,3) along W")), tr)
+            line["roofline_wgrad"] = roofline_obj(timer, "wgrad", bf16, "%s (3x3x3 64->64 weight gradient + partial reduction%s)"
+                                                  % (("wgrad64_bf16_dma_kernel", "") if bf16 else ("wgrad64_wino_kernel", "; Winograd F(3,2) along D x F(3,4) along W")), tr)
         if world > 1:
             line["per_rank_ms_per_step"] = per_rank_ms
             line["allreduce_exposed_ms"] = {"per_rank_mean": per_rank_wait, "max": max(per_rank_wait),
@@ -848,7 +902,7 @@ def main():
         if oversub:
             line["oversubscribed"] = True
     sec_dp = None
-    if world > 1 and not bf16 and args.config == "cfg2" and not args.no_secondary:
+    if args.full and world > 1 and not bf16 and args.config == "cfg2" and not args.no_secondary:
         del tc, batch
         torch.cuda.empty_cache()
         sec_dp = guarded(lambda: secondary_runs_dp(trainer, parallel, device, P, R, B, LB, HB, rank, world), line, rank,
@@ -862,7 +916,7 @@ def main():
         line["secondary"] = sec_dp
     del tc, batch
     torch.cuda.empty_cache()
-    if world == 1 and not bf16 and args.config == "cfg2":
+    if args.full and world == 1 and not bf16 and args.config == "cfg2":
         if not args.no_secondary:
             try:                                    # secondary legs run after the headline was measured: a failing leg is recorded, not fatal
                 line["secondary"] = secondary_runs(trainer, parallel, device, P, R, B, LB, HB, args.sustained_steps)

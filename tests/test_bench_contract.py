@@ -119,6 +119,41 @@ def test_executed_flop_pricing_follows_the_kernel_the_planner_picks():
     assert 0.11 < b.executed_shell_flop(8, 48, 48, 48) / b.executed_conv64_flop(8, 48, 48, 48) < 0.13
 
 
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """bench.py --dump-outputs: every array lands as DIR/<name>.npy in float32 (float64 kept); over the budget, each array larger than
+    its share becomes a fixed seeded sample of its elements -- the same one in every run, so two builds compare element for element."""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(0)
+    arrays = {"loss": rng.normal(size=8).astype(np.float32), "weights": rng.normal(size=5000), "gradient": rng.normal(size=5000).astype(np.float16)}
+    b.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in arrays}
+    assert got["loss"].dtype == np.float32 and got["weights"].dtype == np.float64 and got["gradient"].dtype == np.float32
+    for k in arrays:
+        assert np.array_equal(got[k], arrays[k].astype(got[k].dtype))
+    budget = 3 * 1024
+    for run in ("a", "b"):
+        b.dump_outputs(str(tmp_path / run), arrays, budget=budget)
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in arrays}
+    assert sum(v.nbytes for v in a.values()) <= budget
+    assert np.array_equal(a["loss"], arrays["loss"])                           # small enough to stay whole
+    assert a["weights"].size == 1024 // 8 and np.isin(a["weights"], arrays["weights"]).all()
+    assert a["gradient"].size == 1024 // 4
+    for k in arrays:
+        assert np.array_equal(a[k], np.load(str(tmp_path / "b" / (k + ".npy"))))
+
+
+def test_measurements_beyond_the_headline_need_full():
+    """A plain run times the steps and prints the line; the PMC traffic passes belong to --full and are refused without it, before
+    any device work.  --steps sets the number of timed steps: fewer than one is refused."""
+    import subprocess
+    for extra in (["--pmc"], ["--steps", "0"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and "error" in r.stderr, (extra, r.stderr[-500:])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
 def test_secondary_watchdog_prints_the_headline_and_leaves():
     """bench.guarded(): the N > 1 secondary legs run after the headline has been measured; if they hang (point-to-point RCCL traffic
     no multi-GPU box has exercised), rank 0 still prints the ONE JSON line -- with the failure recorded -- and exits 0."""

@@ -13,7 +13,7 @@ b = importlib.import_module("4dflownet_amd.build")
 b.build_library()
 print(b.source_stamp())
 PY
-B="python $R/bench.py --no-cpu-baseline --no-secondary"
+B="python $R/bench.py --full --no-cpu-baseline --no-secondary"
 # the traced / counted passes run every launch on ONE stream (FDN_OVERLAP_WGRAD=0: the product step overlaps the weight gradients with
 # the dgrad chain on a second stream, and a kernel that shares the chip has no duration of its own); the bench lines at the end do not
 export FDN_OVERLAP_WGRAD=0
@@ -36,7 +36,7 @@ for set in "GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_C
   rm -rf /tmp/pq_$i
 done
 if [ "$2" != "nocfg4" ]; then
-  B4="python $R/bench.py --config cfg4 --no-cpu-baseline --no-secondary"
+  B4="python $R/bench.py --full --config cfg4 --no-cpu-baseline --no-secondary"
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt4 -- $B4 --steps 3 --warmup 1 > /dev/null 2>&1
   cp $(find /tmp/kt4 -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_cfg4_kernel_stats.csv
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/pf4 -- $B4 --steps 1 --warmup 1 > /dev/null 2>&1
@@ -51,5 +51,5 @@ if [ "$2" != "nocfg4" ]; then
 fi
 unset FDN_OVERLAP_WGRAD
 $B --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/${TAG}_bench_line_nosecondary.json
-python $R/bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench_line.json
+python $R/bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench_line.json
 echo done
