@@ -4,6 +4,8 @@
 #include <stdio.h>
 #include <mutex>
 #include <set>
+#include <string>
+#include <string.h>
 #include <utility>
 #include "fdn_common.h"
 
@@ -32,6 +34,49 @@ int fdn_func_max_lds(const void* fn, int bytes, const char* who) {
 FDN_HOOK_VAR(int, fdn_wgrad64_force_direct, 0);
 #ifdef FDN_TEST_HOOKS
 extern "C" int fdn_debug_set_wgrad64_direct(int on) { fdn_wgrad64_force_direct = on; return FDN_OK; }
+
+// the launch-plan recorder (fdn_common.h: FDN_PLAN)
+static std::mutex g_plan_mu;
+static std::string g_plan_log;
+static bool g_plan_on = false;
+
+void fdn_plan_note(const char* fmt, ...) {
+    std::lock_guard<std::mutex> lock(g_plan_mu);
+    if (!g_plan_on) return;
+    char line[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(line, sizeof(line), fmt, ap);
+    va_end(ap);
+    g_plan_log += line;
+    g_plan_log += '\n';
+}
+
+int fdn_plan_cus() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    return cus;
+}
+
+// on != 0: start recording (and drop what was recorded); 0: stop
+extern "C" int fdn_debug_plan_log(int on) {
+    std::lock_guard<std::mutex> lock(g_plan_mu);
+    g_plan_on = on != 0;
+    if (g_plan_on) g_plan_log.clear();
+    return FDN_OK;
+}
+
+// copies the recorded lines (NUL-terminated) into buf and clears the record when n > their length; returns that length either way
+extern "C" size_t fdn_debug_plan_read(char* buf, size_t n) {
+    std::lock_guard<std::mutex> lock(g_plan_mu);
+    const size_t len = g_plan_log.size();
+    if (buf && n > len) {
+        memcpy(buf, g_plan_log.data(), len);
+        buf[len] = 0;
+        g_plan_log.clear();
+    }
+    return len;
+}
 #endif
 
 extern "C" int fdn_version(void) { return FDN_VERSION; }   // 161: fdn_conv64_dgrad_fused_multi; 160: FDN_CONV64_PACK_FLOATS = 423 * 4096 (+ the bf16 x 3 stream), FDN_ALGO_WINO_BF16X3

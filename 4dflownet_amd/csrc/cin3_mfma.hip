@@ -170,6 +170,8 @@ int fdn_conv_cin3_fwd_mfma_launch(const T* x, const float* w, const float* bias,
     const int64_t nblk = ((int64_t)N * D * H * W + 31) / 32;
     int64_t grid = (nblk + 3) / 4;
     if (grid > 512) grid = 512;                     // 2 workgroups per CU, each wave walks several blocks with its weights resident
+    FDN_PLAN("fam=cin3_fwd op=fwd dt=%s N=%d D=%d H=%d W=%d grid=%lld tiles=%lld cus=%d", sizeof(T) == 2 ? "bf16" : "f32", N, D, H, W, (long long)grid,
+             (long long)nblk, fdn_plan_cus());
     hipLaunchKernelGGL(conv_cin3_fwd_mfma_kernel<T>, dim3((unsigned)grid), dim3(256), 0, s, x, w, bias, y, N, D, H, W, act, alpha);
     FDN_CHECK_LAUNCH("conv_cin3_fwd_mfma_kernel");
     return FDN_OK;

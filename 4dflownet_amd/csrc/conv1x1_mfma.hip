@@ -214,6 +214,8 @@ int fdn_conv1x1_fwd_mfma_launch(const T* xa, const T* xb, const float* w, const 
                                 hipStream_t s) {
     const int64_t nblk = (nvox + 31) / 32;
     const int nb = (int)((nblk + 3) / 4 < 512 ? (nblk + 3) / 4 : 512);
+    FDN_PLAN("fam=conv1x1_fwd op=fwd dt=%s nvox=%lld grid=%d tiles=%lld cus=%d", sizeof(T) == 2 ? "bf16" : "f32", (long long)nvox, nb, (long long)nblk,
+             fdn_plan_cus());
     hipLaunchKernelGGL(conv1x1_fwd_mfma_kernel<T>, dim3(nb), dim3(256), 0, s, xa, xb, w, bias, y, nvox, act, alpha);
     FDN_CHECK_LAUNCH("conv1x1_fwd_mfma_kernel");
     return FDN_OK;
@@ -223,6 +225,8 @@ template <typename T>
 int fdn_conv1x1_dgrad_mfma_launch(const T* dz, const float* w, const T* ya, const T* yb, T* dxa, T* dxb, int64_t nvox, hipStream_t s) {
     const int64_t nblk = (nvox + 31) / 32;
     const int nb = (int)((nblk + 3) / 4 < 512 ? (nblk + 3) / 4 : 512);
+    FDN_PLAN("fam=conv1x1_dgrad op=dgrad dt=%s nvox=%lld grid=%d tiles=%lld cus=%d", sizeof(T) == 2 ? "bf16" : "f32", (long long)nvox, nb, (long long)nblk,
+             fdn_plan_cus());
     hipLaunchKernelGGL(conv1x1_dgrad_mfma_kernel<T>, dim3(nb), dim3(256), 0, s, dz, w, ya, yb, dxa, dxb, nvox);
     FDN_CHECK_LAUNCH("conv1x1_dgrad_mfma_kernel");
     return FDN_OK;

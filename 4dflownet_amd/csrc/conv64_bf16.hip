@@ -729,12 +729,10 @@ int launch_bf16(Conv64BfArgs& a, const Box* boxes, int nbox, hipStream_t s) {
         r.swz_hs = t.tw <= 2 ? 2 : 0;
         r.swz_wm = t.tw >= 16 ? 1 : 0;
         r.swap_dh = bx.swap;
-#ifdef FDN_TEST_HOOKS                                    // the planner's choices, test build only (the product library reads no environment)
-        if (getenv("FDN_DEBUG_PLAN"))
-            fprintf(stderr, "conv64_bf16<MT=%d> box %d: out (%d,%d,%d)+(%d,%d,%d) taps a[%d,%d] b[%d,%d] c[%d,%d] tile %dx%dx%d x(%d,%d,%d) rows %d lrows %d hs %d %s\n",
-                    MT, i, bx.od, bx.oh, bx.ow, bx.ed, bx.eh, bx.ew, bx.ta0, bx.ta1, bx.tb0, bx.tb1, bx.tc0, bx.tc1, t.td, t.th,
-                    t.tw, t.ntd, t.nth, t.ntw, r.rows, r.lrows, r.hs, is_fast ? "FAST" : "general");
-#endif
+        FDN_PLAN("fam=bf16_%s op=%s dt=bf16 N=%d D=%d H=%d W=%d mt=%d box=%d taps=%d%d%d%d%d%d tile=%dx%dx%d tiles=%lld secondary=%d ymask=%d fmask=%d nsrc=%d cus=%d",
+                 is_fast2 ? "mode2" : (is_fast ? "fast" : "general"), a.fout ? "dgrad" : "fwd", a.N, a.ID, a.IH, a.IW, MT, i, bx.ta0, bx.ta1,
+                 bx.tb0, bx.tb1, bx.tc0, bx.tc1, t.td, t.th, t.tw, (long long)a.N * t.ntd * t.nth * t.ntw,
+                 i > 0 && (long long)a.N * t.ntd * t.nth * t.ntw < 1024, a.ymask != nullptr, a.fmask != nullptr, a.nsrc, fdn_plan_cus());
     }
     if (fast2.nreg > 0 && slow.nreg > 0 && fast.nreg == 0 && a.fout && !(fdn_conv64bf_dbg & 32)) {
         // the fused dgrad of a grid with 8 x 8 plane blocks: inner box + shell slabs in ONE launch (test build, bit 32: two launches)
@@ -750,6 +748,8 @@ int launch_bf16(Conv64BfArgs& a, const Box* boxes, int nbox, hipStream_t s) {
             if (r.lrows_p > max0) max0 = r.lrows_p;
         }
         const size_t lds = (size_t)(max2 > max0 ? max2 : max0) * 64 + C::MCAP * 4;
+        FDN_PLAN("fam=bf16_fused_launch op=dgrad dt=bf16 N=%d D=%d H=%d W=%d mt=%d nreg=%d+%d nsrc=%d grid=%d tiles=%d cus=%d", a.N, a.ID, a.IH, a.IW,
+                 MT, fast2.nreg, slow.nreg, a.nsrc, n2 + n0, n2 + n0, fdn_plan_cus());
         if (a.nsrc > 1) {
             if (int rc = fdn_func_max_lds((const void*)conv64_bf16_fused_kernel<MT, true>, C::LDS_BUDGET, "conv64_bf16_fused")) return rc;
             hipLaunchKernelGGL((conv64_bf16_fused_kernel<MT, true>), dim3((unsigned)(n2 + n0)), dim3(256), lds, s, fast2, slow, n2);

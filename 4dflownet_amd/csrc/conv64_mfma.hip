@@ -648,6 +648,15 @@ int launch_conv64(Conv64Args& a, const Box* boxes, int nbox, hipStream_t s) {
     const size_t lds = (size_t)max_rows * C::LROW + C::MCAP * 4;
     const Conv64Region& r0 = a.reg[0];
     const bool simple = a.nreg == 1 && r0.ta0 == 0 && r0.ta1 == 2 && r0.tb0 == 0 && r0.tb1 == 2 && r0.tc0 == 0 && r0.tc1 == 2;
+#ifdef FDN_TEST_HOOKS
+    {
+        char regs[256] = "";
+        for (int i = 0, o = 0; i < a.nreg && o < 200; ++i)
+            o += snprintf(regs + o, sizeof(regs) - o, " r%d=%dx%dx%d", i, a.reg[i].td, a.reg[i].th, a.reg[i].tw);
+        FDN_PLAN("fam=direct op=%s dt=f32 N=%d D=%d H=%d W=%d layout=%dx%dx%d nreg=%d%s grid=%d tiles=%d cus=%d", a.fout ? "dgrad" : "fwd",
+                 a.N, a.ID, a.IH, a.IW, MT, NW, CS, a.nreg, regs, first, first, fdn_plan_cus());
+    }
+#endif
     if (simple) hipLaunchKernelGGL((conv64_mfma_kernel<MT, NW, CS, false>), dim3((unsigned)first), dim3(256), lds, s, a);
     else hipLaunchKernelGGL((conv64_mfma_kernel<MT, NW, CS, true>), dim3((unsigned)first), dim3(256), lds, s, a);
     FDN_CHECK_LAUNCH("conv64_mfma_kernel");

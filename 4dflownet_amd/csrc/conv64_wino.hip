@@ -153,6 +153,16 @@ int fdn_conv64_wino_launch_boxes(const float* x, const float* upack, const float
     size_t lds = (size_t)6 * (kWinoMaxLtg * LROW + 64) + 192 * 4;      // fixed plane stride (see the kernel); max_ltg <= kWinoMaxLtg by the planner
     (void)max_ltg;
     if (fdn_conv64_wino_dbg & 64) lds = 82 * 1024;             // ablation: only ONE workgroup fits a CU
+#ifdef FDN_TEST_HOOKS
+    {
+        char regs[256] = "";
+        for (int i = 0, o = 0; i < a.nreg && o < 200; ++i)
+            o += snprintf(regs + o, sizeof(regs) - o, " r%d=%dx%dx%d%s", i, a.reg[i].td, a.reg[i].th, a.reg[i].tg, a.reg[i].wface ? "w" : "");
+        FDN_PLAN("fam=%s op=%s dt=f32 N=%d D=%d H=%d W=%d nreg=%d%s nsrc=%d grid=%lld tiles=%lld cus=%d",
+                 inner ? "wino2d_shell" : (shell_only ? "wino1d_shell" : "wino1d"), fout ? "dgrad" : "fwd", N, ID, IH, IW, a.nreg, regs,
+                 a.nsrc, blocks + (inner ? inner->blocks : 0), blocks + (inner ? inner->blocks : 0), fdn_plan_cus());
+    }
+#endif
     const int lds_max = 84 * 1024;
     if (int rc = fdn_func_max_lds((const void*)conv64_wino_kernel<CS, true>, lds_max, "conv64_wino")) return rc;
     if (int rc = fdn_func_max_lds((const void*)conv64_wino_kernel<CS, false>, lds_max, "conv64_wino")) return rc;

@@ -179,6 +179,10 @@ int fdn_conv64_wino2d_prepare(const float* x, const float* upack2, const float* 
     fdn_magic40(a.ntw, &a.mg_ntw_hi, &a.mg_ntw_lo);
     const long long blocks = (long long)N * a.ntd * a.nth * a.ntw;
     FDN_REQUIRE(blocks < (1ll << 31), "conv64 (2-D winograd): too many tiles");
+    FDN_PLAN("fam=%s op=%s dt=f32 N=%d D=%d H=%d W=%d hm=%d split=%d mb=%d tile=%dx%dx%d ymask=%d fmask=%d nsrc=%d grid=%lld tiles=%lld cus=%d",
+             (ebh < (fout ? IH : OH) || ebw < (fout ? IW : OW)) ? "wino2d_aligned" : "wino2d", fout ? "dgrad" : "fwd", N, ID, IH, IW, hm,
+             a.split, mb, pl.td, pl.ch, pl.cw, ymask != nullptr, fmask != nullptr, a.nsrc, split ? (blocks < device_cus() ? blocks : (long long)device_cus()) : blocks,
+             blocks, fdn_plan_cus());
     memcpy(out->args, &a, sizeof(a));
     out->blocks = (int)blocks;
     out->lds = split ? W2Geo<2, true>::lds : (mb == 2 ? kW2Lds : W2Geo<1>::lds);

@@ -510,6 +510,8 @@ static int upsample_fwd_t(const T* x, T* y, int N, int D, int H, int W, int C, i
     const int64_t rows = (int64_t)N * D * R * H * R;
     FDN_REQUIRE(rows < (1ll << 31), "fdn_upsample_trilinear_fwd: too many rows");
     const size_t lds = (size_t)4 * W * C * sizeof(T);
+    FDN_PLAN("fam=upsample_fwd op=fwd dt=%s N=%d D=%d H=%d W=%d R=%d staged=%d grid=%lld tiles=%lld cus=%d", sizeof(T) == 2 ? "bf16" : "f32", N, D, H, W, R,
+             lds <= 64 * 1024, (long long)(rows < 262144 ? rows : 262144), (long long)rows, fdn_plan_cus());
     if (lds <= 64 * 1024) {
         if (lds > 48 * 1024)
             if (int rc = fdn_func_max_lds((const void*)upsample_fwd_kernel<T, true>, 64 * 1024, "upsample_fwd")) return rc;
@@ -553,6 +555,8 @@ static int upsample_bwd_t(const T* dy, const T* y_prev, int act, float alpha, T*
     const int64_t blocks = (int64_t)N * D * ((H + hb - 1) / hb);
     const unsigned grid = (unsigned)(blocks < 65536 ? blocks : 65536);
     const float sd = axis_scale(D, R), sh = axis_scale(H, R), sw = axis_scale(W, R);
+    FDN_PLAN("fam=upsample_bwd op=bwd dt=%s N=%d D=%d H=%d W=%d R=%d hb=%d grid=%u tiles=%lld cus=%d", sizeof(T) == 2 ? "bf16" : "f32", N, D, H, W, R, hb,
+             grid, (long long)blocks, fdn_plan_cus());
     auto launch = [&](auto tag) -> int {
         constexpr int HB = decltype(tag)::value;
         if (lds > 48 * 1024) {

@@ -142,6 +142,17 @@ int fdn_func_max_lds(const void* fn, int bytes, const char* who);
 #define FDN_DBG_BITS(args) 0                     // ... and compiled out of the product library
 #endif
 
+// Launch-plan recorder (test build only; tests/test_gpu_plan_coverage.py): while fdn_debug_plan_log(1) is on, every launcher appends
+// one line of space-separated key=value fields per launch -- fam (kernel family), dt, N D H W, the tile / variant the planner chose,
+// grid (workgroups) against tiles (work items) and cus -- read back (and cleared) by fdn_debug_plan_read.  Compiled out of the product library.
+#ifdef FDN_TEST_HOOKS
+void fdn_plan_note(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+int fdn_plan_cus();
+#define FDN_PLAN(...) fdn_plan_note(__VA_ARGS__)
+#else
+#define FDN_PLAN(...) ((void)0)
+#endif
+
 #define FDN_CHECK_LAUNCH(name)                                                         \
     do {                                                                               \
         hipError_t e_ = hipGetLastError();                                             \

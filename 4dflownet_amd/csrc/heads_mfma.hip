@@ -206,6 +206,8 @@ int fdn_head_fwd_launch(const T* x, const float* w, const float* bias, float* y,
     const int ntiles = N * ntd * nth * ntw;
     const int iters = 3 * ((ntiles + 3 * 512 - 1) / (3 * 512));
     const int grid = (ntiles + iters - 1) / iters;
+    FDN_PLAN("fam=head_fwd op=fwd dt=%s N=%d D=%d H=%d W=%d iters=%d last=%d grid=%d tiles=%d cus=%d", sizeof(T) == 2 ? "bf16" : "f32", N, D, H, W,
+             iters, ntiles - (grid - 1) * iters, grid, ntiles, fdn_plan_cus());
     hipLaunchKernelGGL(head_fwd_kernel<T>, dim3((unsigned)grid), dim3(256), lds, s, x, w, bias, y, N, D, H, W, ntd, nth, ntw, iters,
                        ldy, y_coff, act, alpha, xcd_walk);
     FDN_CHECK_LAUNCH("head_fwd_kernel");

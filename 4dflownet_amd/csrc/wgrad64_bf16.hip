@@ -556,6 +556,8 @@ int fdn_wgrad64_bf16_launch(const uint16_t* x, const uint16_t* dz, float* dw, vo
         a.nseg = (D + want - 1) / want;
         a.seg_len = (D + a.nseg - 1) / a.nseg;
         a.nseg = (D + a.seg_len - 1) / a.seg_len;
+        FDN_PLAN("fam=wgrad_bf16_dma op=wgrad dt=bf16 N=%d D=%d H=%d W=%d splits=%d nseg=%d grid=%d tiles=%d cus=%d", N, D, H, W, a.S, a.nseg, 3 * a.S,
+                 a.ntiles, fdn_plan_cus());
         if (int rc = fdn_func_max_lds((const void*)wgrad64_bf16_dma_kernel, DLDS_BYTES, "wgrad64_bf16")) return rc;
         hipLaunchKernelGGL(wgrad64_bf16_dma_kernel, dim3(3 * a.S), dim3(256), DLDS_BYTES, s, a);
         FDN_CHECK_LAUNCH("wgrad64_bf16_dma_kernel");
@@ -563,6 +565,7 @@ int fdn_wgrad64_bf16_launch(const uint16_t* x, const uint16_t* dz, float* dw, vo
         a.bytes = 0;
         a.ntd = (D + TD - 1) / TD;
         a.ntiles = N * a.ntd * a.nth * a.ntw;
+        FDN_PLAN("fam=wgrad_bf16_reg op=wgrad dt=bf16 N=%d D=%d H=%d W=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, a.S, 3 * a.S, a.ntiles, fdn_plan_cus());
         hipLaunchKernelGGL(wgrad64_bf16_kernel, dim3(3 * a.S), dim3(256), LDS_BYTES, s, a);
         FDN_CHECK_LAUNCH("wgrad64_bf16_kernel");
     }
@@ -620,6 +623,8 @@ int fdn_wgrad64_bf16_batch_launch(const uint16_t* const* x, const uint16_t* cons
         a.nseg = (D + want - 1) / want;
         a.seg_len = (D + a.nseg - 1) / a.nseg;
         a.nseg = (D + a.seg_len - 1) / a.seg_len;
+        FDN_PLAN("fam=wgrad_bf16_batch op=wgrad dt=bf16 N=%d D=%d H=%d W=%d layers=%d splits=%d nseg=%d grid=%d tiles=%d cus=%d", N, D, H, W, chunk,
+                 a.S, a.nseg, 3 * a.S * chunk, a.ntiles, fdn_plan_cus());
         hipLaunchKernelGGL(wgrad64_bf16_dma_batch_kernel, dim3(3 * a.S * chunk), dim3(256), DLDS_BYTES, s, b);
         FDN_CHECK_LAUNCH("wgrad64_bf16_dma_batch_kernel");
         hipLaunchKernelGGL(wgrad64_reduce_batch_kernel, dim3(27 * 1024 / 64, chunk), dim3(256), 0, s, (const float*)ws, t, a.S);

@@ -266,6 +266,7 @@ int fdn_wgrad64_launch(const float* x, const float* dz, float* dw, void* ws, siz
     a.S = wgrad64_splits(N, D, H, W);
     FDN_REQUIRE((long long)N * D * H * W * 256 < (1ll << 32), "wgrad64: x of %dx%dx%dx%dx64 floats exceeds the 32-bit buffer addressing", N, D, H, W);
     a.bytes = (unsigned)((long long)N * D * H * W * 256);
+    FDN_PLAN("fam=wgrad_direct op=wgrad dt=f32 N=%d D=%d H=%d W=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, a.S, 3 * a.S, a.ntiles, fdn_plan_cus());
     const size_t lds = (size_t)3 * ((kTH + 2) * (kTW + 2) + kTH * kTW) * 256;
     if (int rc = fdn_func_max_lds((const void*)wgrad64_pipe_kernel<kTH, kTW>, (int)lds, "wgrad64")) return rc;
     hipLaunchKernelGGL((wgrad64_pipe_kernel<kTH, kTW>), dim3(a.S, 3), dim3(256), lds, s, a);

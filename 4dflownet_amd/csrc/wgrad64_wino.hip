@@ -523,6 +523,8 @@ int fdn_wgrad64_wino_launch(const float* x, const float* dz, float* dw, void* ws
     FDN_REQUIRE(ws_bytes >= (size_t)a.S * (dep ? 36 : 27) * 4096 * sizeof(float), "wgrad64 (winograd): workspace too small");
     a.bytes = (unsigned)((long long)N * D * H * W * 256);
     a.dbg = fdn_wgrad64_wino_dbg;
+    FDN_PLAN("fam=wgrad_wino op=wgrad dt=f32 N=%d D=%d H=%d W=%d dep=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, dep, a.S, (dep ? 4 : 3) * a.S,
+             a.ntiles, fdn_plan_cus());
     if (dep) {
         const size_t lds = (size_t)3 * WBUFB + XSCRATCH + ZSCRATCH;
         if (int rc = fdn_func_max_lds((const void*)wgrad64_wino_kernel<true>, (int)lds, "wgrad64_wino")) return rc;
@@ -578,6 +580,8 @@ int fdn_wgrad64_wino_batch_launch(const float* const* x, const float* const* dz,
     FDN_REQUIRE(ws_bytes >= fdn_wgrad64_wino_batch_workspace_bytes(n_layers, N, D, H, W), "wgrad64 (batched): workspace too small");
     a.bytes = (unsigned)((long long)N * D * H * W * 256);
     a.dbg = fdn_wgrad64_wino_dbg;
+    FDN_PLAN("fam=wgrad_wino_batch op=wgrad dt=f32 N=%d D=%d H=%d W=%d layers=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, n_layers, a.S,
+             4 * a.S * n_layers, a.ntiles, fdn_plan_cus());
     const size_t lds = (size_t)3 * WBUFB + XSCRATCH + ZSCRATCH;
     if (int rc = fdn_func_max_lds((const void*)wgrad64_wino_batch_kernel<true>, (int)lds, "wgrad64_wino_batch")) return rc;
     hipLaunchKernelGGL(wgrad64_wino_batch_kernel<true>, dim3(4 * a.S * n_layers), dim3(512), lds, s, b);

@@ -137,6 +137,14 @@ def test_predictor_end_to_end_on_example_volume(tmp_path):
     ref, _ = O.network_forward(params, tuple(np.asarray(a, np.float64) for a in ins), 2, 2, 1, f32_coeffs=True)
     got = net.predict(ins)
     assert np.abs(got - ref).max() / np.abs(ref).max() < 1e-4
+    # every patch of the chunked run (batch_size 8 over 12 patches: a chunk of N = 8, then the tail chunk of N = 4) against the oracle
+    assert len(vel[0]) == 12
+    rows = predictor.predict_patches(net2, vel, mag, 8)
+    ref_all, _ = O.network_forward(params, tuple(np.asarray(a, np.float64) for a in list(vel) + list(mag)), 2, 2, 1, f32_coeffs=True)
+    assert rows.shape == ref_all.shape
+    for i in range(len(rows)):
+        e = np.abs(rows[i] - ref_all[i]).max() / np.abs(ref_all[i]).max()
+        assert e < 1e-4, "patch %d (chunk of N = %d): rel err %.3e" % (i, 8 if i < 8 else 4, e)
     # small velocities are zeroed: nothing in (0, venc/2048)
     nz = np.abs(back["u"][back["u"] != 0])
     assert nz.size == 0 or nz.min() >= float(ds.velocity_per_px)
