@@ -322,14 +322,90 @@ __global__ __launch_bounds__(256) void mask_sums_kernel(const float* __restrict_
     if (threadIdx.x == 0) { atomicAdd(&scratch[n * 8 + 0], a); atomicAdd(&scratch[n * 8 + 1], b); }
 }
 
+// divergence loss (loss_utils.py:4-62, TrainerController.py:84-127 with lines 111-120 live): along the axis a paired with channel c
+// (u: D, v: H, w: W) (Da e)[k] = e[clamp(k-1)] - e[clamp(k+1)], e = pred - truth (the SYMMETRIC pad-1 cross-correlation; the
+// difference of the two gradients is the gradient of the difference).  One voxel k at position p of an axis of extent n and
+// voxel stride s: returns (Da e)[k] and adds Da^T r to *g, r[j] = two_w * c[j] * (Da e)[j], c[j] = m[j] inv_f + nf[j] inv_nf.
+// Da^T r at k: r[k+1] - r[k-1] inside, r[0] + r[1] at k = 0, -(r[n-2] + r[n-1]) at k = n-1, 0 when n = 1.  Every neighbour index
+// is clamped into the axis, so every load stays inside the sample.
+__device__ __forceinline__ float div_axis(const float* __restrict__ pred, const float* __restrict__ t, const float* __restrict__ mask,
+                                          int64_t g, int c, int p, int n, int64_t s, float e0, float c0, float inv_f, float inv_nf,
+                                          float two_w, float* gout) {
+    const int km2 = max(p - 2, 0), km1 = max(p - 1, 0), kp1 = min(p + 1, n - 1), kp2 = min(p + 2, n - 1);
+    auto e = [&](int k) { const int64_t q = g + (int64_t)(k - p) * s; return pred[q * 3 + c] - t[q]; };
+    auto cw = [&](int k) { const float m = mask[g + (int64_t)(k - p) * s]; return m * inv_f + (m < 0.5f ? inv_nf : 0.f); };
+    const float em2 = e(km2), em1 = e(km1), ep1 = e(kp1), ep2 = e(kp2);
+    const float cm1 = cw(km1), cp1 = cw(kp1);
+    const float d0 = em1 - ep1;                                     // (Da e)[p]
+    const float rm1 = p > 0 ? two_w * cm1 * (em2 - e0) : 0.f;       // r[p-1]: (Da e)[p-1] = e[clamp(p-2)] - e[p]
+    const float rp1 = p < n - 1 ? two_w * cp1 * (e0 - ep2) : 0.f;   // r[p+1]: (Da e)[p+1] = e[p] - e[clamp(p+2)]
+    const float r0 = two_w * c0 * d0;
+    float acc = rp1 - rm1;
+    if (p == 0) acc += r0;
+    if (p == n - 1) acc -= r0;
+    *gout += acc;
+    return d0;
+}
+
+// div_w == 0: the masked MSE alone, exactly the arithmetic and block -> voxel mapping of the plain loss.  div_w > 0 (fdn_loss_metrics_div):
+// the same pass also gathers each channel's stencil neighbours (e at +-1, +-2 and m at +-1 along its axis; L1 / L2 hits), adds the
+// divergence part of dpred and writes two more per-block partials (sum m d, sum nf d; the weight is applied in loss_finalize_kernel).
+// nparts: partials per block, 3 (plain) or 5.  (The branch's gathers in flight take the kernel from 26 to 68 VGPRs: seven waves per
+// SIMD instead of eight; capping it at 64 spills.)
 __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict__ pred, const float* __restrict__ uh,
                                                          const float* __restrict__ vh, const float* __restrict__ wh,
                                                          const float* __restrict__ mask, float* __restrict__ scratch,
-                                                         float* __restrict__ dpred, int64_t V) {
+                                                         float* __restrict__ dpred, int64_t V, int D, int H, int W, float div_w,
+                                                         int nparts) {
     __shared__ float red[4];
     const int n = blockIdx.y;
     const float inv_f = 1.f / (scratch[n * 8 + 0] + 1.f);
     const float inv_nf = 1.f / (scratch[n * 8 + 1] + 1.f);
+    if (div_w != 0.f) {
+        const float two_w = 2.f * div_w;
+        const int64_t HW = (int64_t)H * W;
+        float sf = 0.f, snf = 0.f, srel = 0.f, sdf = 0.f, sdn = 0.f;
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t g = (int64_t)n * V + i;
+            const float tu = uh[g], tv = vh[g], tw = wh[g];
+            const float du = pred[g * 3] - tu, dv = pred[g * 3 + 1] - tv, dw = pred[g * 3 + 2] - tw;
+            const float m = mask[g];
+            const float nf = m < 0.5f ? 1.f : 0.f;
+            const float mse = du * du + dv * dv + dw * dw;
+            sf += mse * m;
+            snf += mse * nf;
+            const float diff = sqrtf(mse);
+            const float actual = sqrtf(tu * tu + tv * tv + tw * tw);
+            float rel = diff / (actual + 1e-5f);
+            rel = fminf(fmaxf(rel, 0.f), 1.f);
+            float corr = actual != 0.f ? rel : diff;
+            corr = rintf(corr * 1e4f) / 1e4f;
+            if (m == 1.0f) srel += corr;
+            const unsigned iv = (unsigned)i;                       // V < 2^31 (fdn_loss_metrics_div)
+            const unsigned q = iv / (unsigned)W;
+            const int pw = (int)(iv - q * (unsigned)W), ph = (int)(q % (unsigned)H), pd = (int)(q / (unsigned)H);
+            const float c0 = m * inv_f + nf * inv_nf;
+            const float wgt = 2.f * c0;
+            float gu = du * wgt, gv = dv * wgt, gw = dw * wgt;
+            const float au = div_axis(pred, uh, mask, g, 0, pd, D, HW, du, c0, inv_f, inv_nf, two_w, &gu);
+            const float av = div_axis(pred, vh, mask, g, 1, ph, H, W, dv, c0, inv_f, inv_nf, two_w, &gv);
+            const float aw = div_axis(pred, wh, mask, g, 2, pw, W, 1, dw, c0, inv_f, inv_nf, two_w, &gw);
+            const float dd = au * au + av * av + aw * aw;
+            sdf += dd * m;
+            sdn += dd * nf;
+            if (dpred) { dpred[g * 3] = gu; dpred[g * 3 + 1] = gv; dpred[g * 3 + 2] = gw; }
+        }
+        const float a = block_sum(sf, red);
+        const float b = block_sum(snf, red);
+        const float c = block_sum(srel, red);
+        const float d = block_sum(sdf, red);
+        const float e = block_sum(sdn, red);
+        if (threadIdx.x == 0) {
+            float* part = scratch + (size_t)gridDim.y * 8 + ((size_t)n * gridDim.x + blockIdx.x) * 5;
+            part[0] = a; part[1] = b; part[2] = c; part[3] = d; part[4] = e;
+        }
+        return;
+    }
     float sf = 0.f, snf = 0.f, srel = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t g = (int64_t)n * V + i;
@@ -359,25 +435,37 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
     // per-block partials, summed by loss_finalize_kernel in block order: the reported loss / metric is run-to-run identical
     // (the mask counts above are integers < 2^24, so their atomic sums are exact in any order)
     if (threadIdx.x == 0) {
-        float* part = scratch + (size_t)gridDim.y * 8 + ((size_t)n * gridDim.x + blockIdx.x) * 3;
+        float* part = scratch + (size_t)gridDim.y * 8 + ((size_t)n * gridDim.x + blockIdx.x) * nparts;
         part[0] = a; part[1] = b; part[2] = c;
+        if (nparts == 5) { part[3] = 0.f; part[4] = 0.f; }
     }
 }
 
 // one wave per sample: lane t sums the partials of blocks t, t + 64, ..., then a shuffle tree -- a fixed order, so the reported loss /
-// metric stays run-to-run identical (one THREAD per sample walked the 256 partials as a chain of dependent loads: 24 us)
-__global__ __launch_bounds__(64) void loss_finalize_kernel(const float* __restrict__ scratch, float* __restrict__ out, int N, int nblk) {
+// metric stays run-to-run identical (one THREAD per sample walked the 256 partials as a chain of dependent loads: 24 us).
+// nparts 3: out (N,4); nparts 5: out (N,5), column 4 = div_w * (sum m d / (sum m + 1) + sum nf d / (sum nf + 1)).
+__global__ __launch_bounds__(64) void loss_finalize_kernel(const float* __restrict__ scratch, float* __restrict__ out, int N, int nblk,
+                                                           int nparts, float div_w) {
     const int n = blockIdx.x;
-    const float* part = scratch + (size_t)N * 8 + (size_t)n * nblk * 3;
-    float sf = 0.f, sn = 0.f, sr = 0.f;
-    for (int b = threadIdx.x; b < nblk; b += 64) { sf += part[b * 3]; sn += part[b * 3 + 1]; sr += part[b * 3 + 2]; }
+    const float* part = scratch + (size_t)N * 8 + (size_t)n * nblk * nparts;
+    float sf = 0.f, sn = 0.f, sr = 0.f, sdf = 0.f, sdn = 0.f;
+    if (nparts == 5) {
+        for (int b = threadIdx.x; b < nblk; b += 64) {
+            sf += part[b * 5]; sn += part[b * 5 + 1]; sr += part[b * 5 + 2]; sdf += part[b * 5 + 3]; sdn += part[b * 5 + 4];
+        }
+        for (int o = 32; o > 0; o >>= 1) { sdf += __shfl_down(sdf, o, 64); sdn += __shfl_down(sdn, o, 64); }
+    } else {
+        for (int b = threadIdx.x; b < nblk; b += 64) { sf += part[b * 3]; sn += part[b * 3 + 1]; sr += part[b * 3 + 2]; }
+    }
     for (int o = 32; o > 0; o >>= 1) { sf += __shfl_down(sf, o, 64); sn += __shfl_down(sn, o, 64); sr += __shfl_down(sr, o, 64); }
     if (threadIdx.x) return;
     const float sm = scratch[n * 8 + 0], snf = scratch[n * 8 + 1];
-    out[n * 4 + 0] = sf / (sm + 1.f) + sn / (snf + 1.f);
-    out[n * 4 + 1] = sr / (sm + 1.f) * 100.f;
-    out[n * 4 + 2] = sm;
-    out[n * 4 + 3] = snf;
+    const int nc = nparts == 5 ? 5 : 4;
+    out[n * nc + 0] = sf / (sm + 1.f) + sn / (snf + 1.f);
+    out[n * nc + 1] = sr / (sm + 1.f) * 100.f;
+    out[n * nc + 2] = sm;
+    out[n * nc + 3] = snf;
+    if (nparts == 5) out[n * 5 + 4] = div_w * (sdf / (sm + 1.f) + sdn / (snf + 1.f));
 }
 
 // ONE block (fixed summation order, no atomics): this pass only runs when the parameters changed outside the optimizer
@@ -587,21 +675,40 @@ extern "C" int fdn_upsample_trilinear_bwd_bf16(const uint16_t* dy, const uint16_
     return upsample_bwd_t<uint16_t>(dy, y_prev, act, alpha, dx, N, D, H, W, C, R, stream);
 }
 
-extern "C" int fdn_loss_metrics(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask,
-                                float* out, float* dpred, float* scratch, int N, int64_t V, void* stream) {
-    FDN_REQUIRE(pred && uh && vh && wh && mask && out && scratch && N > 0 && V > 0, "fdn_loss_metrics: bad argument");
+// the three launches of both loss entry points; nparts 3: out (N,4) (fdn_loss_metrics), 5: out (N,5) (fdn_loss_metrics_div)
+static int loss_launch(const char* who, const float* pred, const float* uh, const float* vh, const float* wh, const float* mask, float* out,
+                       float* dpred, float* scratch, int N, int64_t V, int D, int H, int W, float div_w, int nparts, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(scratch, 0, (size_t)N * 8 * sizeof(float), s);
-    if (e != hipSuccess) { fdn_set_error("fdn_loss_metrics: memset: %s", hipGetErrorString(e)); return FDN_ERR_HIP; }
+    if (e != hipSuccess) { fdn_set_error("%s: memset: %s", who, hipGetErrorString(e)); return FDN_ERR_HIP; }
     const int gx = grid_for(V, FDN_LOSS_BLOCKS);
     // (16 blocks per sample: with 256 the 2 x 256 x N atomics on 2 N words took longer than reading the mask -- 29 us at cfg2)
     hipLaunchKernelGGL(mask_sums_kernel, dim3(gx < 16 ? gx : 16, N), dim3(256), 0, s, mask, scratch, V);
     FDN_CHECK_LAUNCH("mask_sums_kernel");
-    hipLaunchKernelGGL(loss_main_kernel, dim3(gx, N), dim3(256), 0, s, pred, uh, vh, wh, mask, scratch, dpred, V);
+    hipLaunchKernelGGL(loss_main_kernel, dim3(gx, N), dim3(256), 0, s, pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts);
     FDN_CHECK_LAUNCH("loss_main_kernel");
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(N), dim3(64), 0, s, (const float*)scratch, out, N, gx);
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(N), dim3(64), 0, s, (const float*)scratch, out, N, gx, nparts, div_w);
     FDN_CHECK_LAUNCH("loss_finalize_kernel");
     return FDN_OK;
+}
+
+extern "C" int fdn_loss_metrics(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask,
+                                float* out, float* dpred, float* scratch, int N, int64_t V, void* stream) {
+    FDN_REQUIRE(pred && uh && vh && wh && mask && out && scratch && N > 0 && V > 0, "fdn_loss_metrics: bad argument");
+    // (the extents only matter to the divergence pass, which div_w = 0 switches off)
+    return loss_launch("fdn_loss_metrics", pred, uh, vh, wh, mask, out, dpred, scratch, N, V, 1, 1, 1, 0.f, 3, stream);
+}
+
+extern "C" int fdn_loss_metrics_div(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask,
+                                    float div_weight, float* out, float* dpred, float* scratch, int N, int D, int H, int W,
+                                    void* stream) {
+    FDN_REQUIRE(pred && uh && vh && wh && mask && out && scratch, "fdn_loss_metrics_div: NULL operand");
+    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_loss_metrics_div: extents N=%d D=%d H=%d W=%d must be positive", N, D, H, W);
+    FDN_REQUIRE((int64_t)D * H * W <= (int64_t)INT32_MAX, "fdn_loss_metrics_div: %d x %d x %d voxels per sample exceed 2^31 - 1", D, H, W);
+    FDN_REQUIRE(__builtin_isfinite(div_weight) && div_weight >= 0.f, "fdn_loss_metrics_div: div_weight %g must be finite and >= 0",
+                (double)div_weight);
+    return loss_launch("fdn_loss_metrics_div", pred, uh, vh, wh, mask, out, dpred, scratch, N, (int64_t)D * H * W, D, H, W, div_weight, 5,
+                       stream);
 }
 
 extern "C" int fdn_l2_sumsq(const float* w, const uint8_t* is_kernel, int64_t n, float* out, void* stream) {

@@ -296,9 +296,13 @@ def upsample_trilinear_bwd(dy, R, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA, 
     return out
 
 
-def loss_metrics(pred, uh, vh, wh, mask, want_grad=True, out=None, dpred=None, scratch=None):
-    """Returns out (N,4) = [mse-loss, rel-err %, sum mask, sum nonfluid] and dpred (N,...,3) or None."""
+def loss_metrics(pred, uh, vh, wh, mask, want_grad=True, out=None, dpred=None, scratch=None, div_weight=0.0):
+    """Returns out (N,4) = [mse-loss, rel-err %, sum mask, sum nonfluid] and dpred (N,...,3) or None.
+    div_weight != 0 (pred (N,D,H,W,3)): fdn_loss_metrics_div, out (N,5) with the weighted divergence loss div_b in column 4 and its
+    gradient in dpred (the sample's loss is out[:, 0] + out[:, 4]).  div_weight == 0 is exactly the plain call."""
     N = pred.shape[0]
+    if div_weight != 0:
+        return _loss_metrics_div(pred, uh, vh, wh, mask, float(div_weight), want_grad, out, dpred, scratch)
     V = pred.numel() // (3 * N)
     if out is None:
         out = torch.empty((N, 4), device=pred.device, dtype=torch.float32)
@@ -309,6 +313,28 @@ def loss_metrics(pred, uh, vh, wh, mask, want_grad=True, out=None, dpred=None, s
     check(_lib.load().fdn_loss_metrics(_p(pred), _p(uh), _p(vh), _p(wh), _p(mask), _p(out),
                                        _p(dpred, allow_none=True) if want_grad else None, _p(scratch), N, V, _stream()),
           "fdn_loss_metrics")
+    return out, (dpred if want_grad else None)
+
+
+def _loss_metrics_div(pred, uh, vh, wh, mask, div_weight, want_grad, out, dpred, scratch):
+    if pred.dim() != 5 or pred.shape[-1] != 3:
+        raise FdnError("loss_metrics: the divergence term needs pred of shape (N,D,H,W,3), got %s" % (tuple(pred.shape),))
+    N, D, H, W = pred.shape[:4]
+    V = D * H * W
+    for name, t in (("uh", uh), ("vh", vh), ("wh", wh), ("mask", mask)):
+        if t.numel() != N * V:
+            raise FdnError("loss_metrics: %s holds %d values, pred's grid %d" % (name, t.numel(), N * V))
+    if out is None:
+        out = torch.empty((N, 5), device=pred.device, dtype=torch.float32)
+    if scratch is None:
+        scratch = torch.empty((N * (8 + 5 * 256),), device=pred.device, dtype=torch.float32)     # FDN_LOSS_DIV_SCRATCH_FLOATS(N)
+    if want_grad and dpred is None:
+        dpred = torch.empty_like(pred)
+    if out.numel() < N * 5 or scratch.numel() < N * (8 + 5 * 256) or (want_grad and dpred.numel() != pred.numel()):
+        raise FdnError("loss_metrics: out needs (N,5), scratch N*(8 + 5*256) floats and dpred pred's shape")
+    check(_lib.load().fdn_loss_metrics_div(_p(pred), _p(uh), _p(vh), _p(wh), _p(mask), div_weight, _p(out),
+                                           _p(dpred, allow_none=True) if want_grad else None, _p(scratch), N, D, H, W, _stream()),
+          "fdn_loss_metrics_div")
     return out, (dpred if want_grad else None)
 
 

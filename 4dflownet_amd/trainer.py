@@ -70,13 +70,16 @@ class _Optimizer:
 class TrainerController:
     def __init__(self, patch_size, res_increase, initial_learning_rate=1e-4, quicksave_enable=True,
                  network_name='4DFlowNet', low_resblock=8, hi_resblock=4, device=None, seed=0, dtype='float32',
-                 bucketed_allreduce=None, conv_algo=None):
+                 bucketed_allreduce=None, conv_algo=None, div_weight=0):
         """Reference arguments: TrainerController.py:18.  Extra (keyword-only in spirit): device, seed (Glorot draw), dtype
         (activation storage, 'float32' | 'bfloat16'), bucketed_allreduce (data parallel only: True = one asynchronous SUM
         all-reduce per gradient bucket started inside backward -- the default --, False = ONE all-reduce of the whole buffer
         after backward; env FDN_DP_BUCKETED=0 selects the latter when the argument is None), conv_algo ('auto' | 'direct' |
-        {layer name: ...}: algorithm of the 64->64 layers, see FlowNetModel)."""
-        self.div_weight = 0            # divergence loss is dead code in the reference (TrainerController.py:23,121)
+        {layer name: ...}: algorithm of the 64->64 layers, see FlowNetModel), div_weight (weight of the divergence loss,
+        TrainerController.py:23,84-127 with :111-120 live; 0 = the reference's shipped loss.  The attribute of the same name is
+        read on every step, so setting it later works too)."""
+        self.div_weight = div_weight   # TrainerController.py:23
+        self._checked_div_weight()
         self.non_fluid_weight = 1
         self.res_increase = res_increase
         self.patch_size = patch_size
@@ -124,17 +127,30 @@ class TrainerController:
         ops.sum_partials(self._l2_partials, self._l2_buf)          # (else the Adam kernel left the per-block sums behind)
         return self._l2_buf[0] * L2_LAMBDA
 
+    def _checked_div_weight(self):
+        w = self.div_weight
+        try:
+            wf = float(w)
+        except (TypeError, ValueError):
+            raise ValueError("div_weight must be a finite number >= 0, got %r" % (w,)) from None
+        if not np.isfinite(wf) or wf < 0:
+            raise ValueError("div_weight must be a finite number >= 0, got %r" % (w,))
+        return wf
+
     def calculate_and_update_metrics(self, hires, predictions, mask, metric_set, want_grad):
-        out, dpred = ops.loss_metrics(predictions, hires[0], hires[1], hires[2], mask, want_grad=want_grad)
+        """TrainerController.py:84-127 (loss_function, the divergence term live when div_weight != 0), :243-256 (metrics)."""
+        div_weight = self._checked_div_weight()
+        out, dpred = ops.loss_metrics(predictions, hires[0], hires[1], hires[2], mask, want_grad=want_grad, div_weight=div_weight)
         mse, rel_error = out[:, 0], out[:, 1]
-        loss = mse
+        div = out[:, 4] if div_weight != 0 else None
+        loss = mse if div is None else mse + div
         if metric_set == 'train':
             l2 = self.calculate_regularizer_loss()
             self.loss_metrics['l2_reg_loss'].update_state(l2.reshape(1))
-            loss = mse + l2
+            loss = loss + l2
         self.loss_metrics['%s_loss' % metric_set].update_state(loss)
         self.loss_metrics['%s_mse' % metric_set].update_state(mse)
-        self.loss_metrics['%s_div' % metric_set].update_state(0.0)
+        self.loss_metrics['%s_div' % metric_set].update_state(0.0 if div is None else div)
         self.loss_metrics['%s_accuracy' % metric_set].update_state(rel_error)
         return loss, dpred
 
@@ -434,10 +450,11 @@ class TrainerController:
     def quicksave(self, testset, epoch_nr):
         """TrainerController.py:415-454: predict the first benchmark batch, append to quicksave_<name>.h5."""
         from . import h5io
+        div_weight = self._checked_div_weight()
         for data_pairs in testset:
             inputs, hires, venc, mask = self._unpack(data_pairs)
             preds_t = self.model.forward(inputs)
-            out, _ = ops.loss_metrics(preds_t, hires[0], hires[1], hires[2], mask, want_grad=False)
+            out, _ = ops.loss_metrics(preds_t, hires[0], hires[1], hires[2], mask, want_grad=False, div_weight=div_weight)
             break
         out = out.cpu().numpy()
         preds = preds_t.cpu().numpy()
@@ -454,4 +471,6 @@ class TrainerController:
             sv("hr_w", np.squeeze(cpu(hires[2]), -1))
             sv("venc", cpu(venc)); sv("mask", cpu(mask))
         h5io.append_datasets(path, cols, compression='gzip')      # one pass over the file for all columns
+        if div_weight != 0:                                       # (loss, rel-error, mse, divergence loss) per sample
+            return out[:, 0] + out[:, 4], out[:, 1], out[:, 0], out[:, 4]
         return out[:, 0], out[:, 1], out[:, 0], np.zeros_like(out[:, 0])

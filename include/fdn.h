@@ -237,6 +237,20 @@ int fdn_upsample_trilinear_bwd(const float* dy, const float* y_prev, int act, fl
 int fdn_loss_metrics(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask,
                      float* out, float* dpred, float* scratch, int N, int64_t V, void* stream);
 
+/* fdn_loss_metrics + the divergence loss the reference defines (src/Network/loss_utils.py:4-62) and weights into the loss
+ * (src/Network/TrainerController.py:84-127, the lines 111-120 it ships commented out).  pred (N,D,H,W,3); uh,vh,wh,mask (N,D,H,W).
+ * Along the axis paired with each channel (u: D, v: H, w: W) (Da x)[k] = x[clamp(k-1)] - x[clamp(k+1)] (SYMMETRIC pad 1 + the
+ * conv3d cross-correlation); per voxel d = sum_c (Da pred_c - Da truth_c)^2; per sample
+ * div_b = div_weight * (sum(mask d) / (sum(mask) + 1) + sum(nf d) / (sum(nf) + 1)), nf = mask < 0.5.
+ * out (N,5) = {mse loss, rel-error %, sum(mask), sum(nonfluid), div_b}; the sample's loss is out[0] + out[4].
+ * dpred (N,D,H,W,3) = d(sum_b (mse_b + div_b))/dpred, or NULL.  scratch: FDN_LOSS_DIV_SCRATCH_FLOATS(N) floats.  div_weight == 0:
+ * columns 0-3 and dpred equal fdn_loss_metrics' bit for bit, column 4 is 0.  D*H*W < 2^31.  Run-to-run identical like
+ * fdn_loss_metrics (no atomics beyond the mask counts).  Refuses NULL operands, non-positive extents and a non-finite or negative
+ * weight before it touches the device. */
+#define FDN_LOSS_DIV_SCRATCH_FLOATS(N) ((N) * (8 + 5 * FDN_LOSS_BLOCKS))
+int fdn_loss_metrics_div(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask,
+                         float div_weight, float* out, float* dpred, float* scratch, int N, int D, int H, int W, void* stream);
+
 /* On-device input pipeline: the per-sample slicing / np.rot90 / sign / normalisation / mask threshold of
  * PatchHandler3D.load_patches_from_index_file (src/Network/PatchHandler3D.py:49-160) as one gather per output
  * tensor.  desc: B device-resident descriptors of 56 bytes each
