@@ -107,6 +107,26 @@ template <typename T> int fdn_bias_grad_launch(const T* dz, float* db, void* ws,
                                                int lddz, int dz_coff, hipStream_t s);
 size_t fdn_small_wgrad_workspace_bytes(int Cin, int Cout, int K);
 
+// The fp32 64->64 entry points: the checks they share, and their call descriptor -- a forward over the (N, D, H, W) grid, or a dgrad
+// (op FDN_CONV64_DGRAD[_FUSED]) onto its padded (D+2, H+2, W+2) grid.  mask_act: act must be one a sign mask belongs to.
+static int conv64_check(const char* who, int algo, int N, int D, int H, int W, int act, bool mask_act = false) {
+    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "%s: bad algo %d", who, algo);
+    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= 1020 && H <= 1020 && W <= 1020, "%s: bad dims", who);
+    if (mask_act) FDN_REQUIRE(act == FDN_ACT_RELU || act == FDN_ACT_LEAKY, "%s: a mask belongs to an activation (act %d)", who, act);
+    else FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "%s: bad act %d", who, act);
+    return FDN_OK;
+}
+
+static FdnConv64Call conv64_call(FdnConv64Op op, const float* x, const float* wpack, float* y, int N, int D, int H, int W, int act,
+                                 float alpha, void* stream) {
+    const int pad = op == FDN_CONV64_FWD ? 0 : 2;
+    FdnConv64Call c;
+    c.op = op; c.x = x; c.wpack = wpack; c.y = y;
+    c.N = N; c.ID = D; c.IH = H; c.IW = W; c.OD = D + pad; c.OH = H + pad; c.OW = W + pad;
+    c.act = act; c.alpha = alpha; c.s = (hipStream_t)stream;
+    return c;
+}
+
 extern "C" int fdn_conv3d_fwd(const float* x, const float* x2, const float* w, const float* wpack, const float* bias,
                               const float* residual, float* y, int N, int D, int H, int W, int Cin, int Cout, int K,
                               int ldy, int y_coff, int act, float alpha, int algo, void* stream) {
@@ -119,7 +139,9 @@ extern "C" int fdn_conv3d_fwd(const float* x, const float* x2, const float* w, c
         FDN_REQUIRE(wpack, "fdn_conv3d_fwd: the 64->64 MFMA path needs wpack (fdn_pack_conv64_weights)");
         FDN_REQUIRE(ldy == 64 && y_coff == 0, "fdn_conv3d_fwd: 64->64 path writes dense rows (ldy=64,y_coff=0)");
         FDN_REQUIRE(D <= 1022 && H <= 1022 && W <= 1022, "fdn_conv3d_fwd: dims too large");
-        return fdn_conv64_launch(x, wpack, bias, residual, y, N, D, H, W, D, H, W, 0, 0, act, alpha, s, algo);
+        FdnConv64Call c = conv64_call(FDN_CONV64_FWD, x, wpack, y, N, D, H, W, act, alpha, stream);
+        c.bias = bias; c.residual = residual;
+        return fdn_conv64_launch_ex(c, 3, algo);
     }
     FDN_REQUIRE(residual == nullptr, "fdn_conv3d_fwd: residual only on the 64->64 path");
     if (Cin == 3 && Cout == 64 && K == 3) {
@@ -148,8 +170,7 @@ extern "C" int fdn_conv3d_dgrad(const float* dz, const float* w, const float* wp
         FDN_REQUIRE(wpack, "fdn_conv3d_dgrad: the 64->64 MFMA path needs wpack = wp_dgrad");
         FDN_REQUIRE(lddz == 64 && dz_coff == 0, "fdn_conv3d_dgrad: 64->64 path reads dense rows");
         FDN_REQUIRE(D <= 1020 && H <= 1020 && W <= 1020, "fdn_conv3d_dgrad: dims too large");
-        return fdn_conv64_launch(dz, wpack, nullptr, nullptr, dxpad, N, D, H, W, D + 2, H + 2, W + 2, -1, 1,
-                                 FDN_ACT_NONE, 0.f, s, algo);
+        return fdn_conv64_launch_ex(conv64_call(FDN_CONV64_DGRAD, dz, wpack, dxpad, N, D, H, W, FDN_ACT_NONE, 0.f, stream), 3, algo);
     }
     if (Cin == 64 && Cout == 1 && K == 3) {
         FDN_REQUIRE(w, "fdn_conv3d_dgrad(64->1): needs w");
@@ -163,41 +184,36 @@ extern "C" int fdn_conv3d_dgrad_fused(const float* dz, const float* wpack, float
                                       const float* y_prev, int act, float alpha, float* dz_prev, int N, int D, int H,
                                       int W, int algo, void* stream) {
     FDN_REQUIRE(dz && wpack && dxpad && dz_prev, "fdn_conv3d_dgrad_fused: NULL argument");
-    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "fdn_conv3d_dgrad_fused: bad algo %d", algo);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= 1020 && H <= 1020 && W <= 1020, "fdn_conv3d_dgrad_fused: bad dims");
-    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "fdn_conv3d_dgrad_fused: bad act %d", act);
-    return fdn_conv64_launch_ex(dz, wpack, nullptr, nullptr, dxpad, skip, y_prev, dz_prev, N, D, H, W, D + 2, H + 2, W + 2,
-                                -1, 1, act, alpha, (hipStream_t)stream, 3, algo);
+    if (int rc = conv64_check("fdn_conv3d_dgrad_fused", algo, N, D, H, W, act)) return rc;
+    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz, wpack, dxpad, N, D, H, W, act, alpha, stream);
+    c.fskip = skip; c.fy = y_prev; c.fout = dz_prev;
+    return fdn_conv64_launch_ex(c, 3, algo);
 }
 
 // 64->64 forward that also writes the sign mask of its output, and the fused dgrad that reads the mask instead of y_prev (conv64_wino2d_kernel.h)
 extern "C" int fdn_conv64_fwd_mask(const float* x, const float* wpack, const float* bias, const float* residual, float* y, uint16_t* y_mask,
                                    int N, int D, int H, int W, int act, float alpha, int algo, void* stream) {
     FDN_REQUIRE(x && wpack && y && y_mask, "fdn_conv64_fwd_mask: NULL argument");
-    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "fdn_conv64_fwd_mask: bad algo %d", algo);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= 1020 && H <= 1020 && W <= 1020, "fdn_conv64_fwd_mask: bad dims");
-    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "fdn_conv64_fwd_mask: bad act %d", act);
-    return fdn_conv64_launch_ex(x, wpack, bias, residual, y, nullptr, nullptr, nullptr, N, D, H, W, D, H, W, 0, 0, act, alpha,
-                                (hipStream_t)stream, 3, algo, nullptr, y_mask, nullptr);
+    if (int rc = conv64_check("fdn_conv64_fwd_mask", algo, N, D, H, W, act)) return rc;
+    FdnConv64Call c = conv64_call(FDN_CONV64_FWD, x, wpack, y, N, D, H, W, act, alpha, stream);
+    c.bias = bias; c.residual = residual; c.ymask = y_mask;
+    return fdn_conv64_launch_ex(c, 3, algo);
 }
 
 extern "C" int fdn_conv64_dgrad_fused_mask(const float* dz, const float* wpack, float* dxpad, const float* skip, const uint16_t* y_mask,
                                            int act, float alpha, float* dz_prev, int N, int D, int H, int W, int algo, void* stream) {
     FDN_REQUIRE(dz && wpack && dxpad && dz_prev && y_mask, "fdn_conv64_dgrad_fused_mask: NULL argument");
-    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "fdn_conv64_dgrad_fused_mask: bad algo %d", algo);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= 1020 && H <= 1020 && W <= 1020, "fdn_conv64_dgrad_fused_mask: bad dims");
-    FDN_REQUIRE(act == FDN_ACT_RELU || act == FDN_ACT_LEAKY, "fdn_conv64_dgrad_fused_mask: a mask belongs to an activation (act %d)", act);
-    return fdn_conv64_launch_ex(dz, wpack, nullptr, nullptr, dxpad, skip, nullptr, dz_prev, N, D, H, W, D + 2, H + 2, W + 2,
-                                -1, 1, act, alpha, (hipStream_t)stream, 3, algo, nullptr, nullptr, y_mask);
+    if (int rc = conv64_check("fdn_conv64_dgrad_fused_mask", algo, N, D, H, W, act, true)) return rc;
+    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz, wpack, dxpad, N, D, H, W, act, alpha, stream);
+    c.fskip = skip; c.fmask = y_mask; c.fout = dz_prev;
+    return fdn_conv64_launch_ex(c, 3, algo);
 }
 
 extern "C" int fdn_conv64_dgrad_fused_multi(const float* const* dz, const float* const* wpack, int nsrc, float* dxpad, const float* skip,
                                             const float* y_prev, const uint16_t* y_mask, int act, float alpha, float* dz_prev, int N, int D,
                                             int H, int W, int algo, void* stream) {
     FDN_REQUIRE(dz && wpack && dxpad && dz_prev && nsrc >= 1 && nsrc <= 3, "fdn_conv64_dgrad_fused_multi: NULL argument or nsrc outside 1..3");
-    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "fdn_conv64_dgrad_fused_multi: bad algo %d", algo);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= 1020 && H <= 1020 && W <= 1020, "fdn_conv64_dgrad_fused_multi: bad dims");
-    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "fdn_conv64_dgrad_fused_multi: bad act %d", act);
+    if (int rc = conv64_check("fdn_conv64_dgrad_fused_multi", algo, N, D, H, W, act)) return rc;
     FDN_REQUIRE(!(y_mask && y_prev), "fdn_conv64_dgrad_fused_multi: y_prev OR its sign mask");
     FDN_REQUIRE(!y_mask || act == FDN_ACT_RELU || act == FDN_ACT_LEAKY, "fdn_conv64_dgrad_fused_multi: a mask belongs to an activation (act %d)", act);
     // the kernels address the further sources' weight streams as non-negative byte distances from source 0's: order by pack address
@@ -206,26 +222,25 @@ extern "C" int fdn_conv64_dgrad_fused_multi(const float* const* dz, const float*
     for (int i = 0; i < nsrc; ++i) FDN_REQUIRE(dz[i] && wpack[i], "fdn_conv64_dgrad_fused_multi: NULL pointer for source %d", i);
     for (int i = 1; i < nsrc; ++i)
         for (int j = i; j > 0 && wpack[ord[j]] < wpack[ord[j - 1]]; --j) { const int t = ord[j]; ord[j] = ord[j - 1]; ord[j - 1] = t; }
-    FdnExtraSrc ex{nsrc, nullptr, nullptr, 0, 0};
+    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz[ord[0]], wpack[ord[0]], dxpad, N, D, H, W, act, alpha, stream);
+    c.fskip = skip; c.fy = y_prev; c.fmask = y_mask; c.fout = dz_prev; c.nsrc = nsrc;
     for (int i = 1; i < nsrc; ++i) {
         const long long d = (long long)(wpack[ord[i]] - wpack[ord[0]]) * (long long)sizeof(float);
         FDN_REQUIRE(d >= 0 && d < (1ll << 30), "fdn_conv64_dgrad_fused_multi: the packs of the sources must lie within 1 GiB of each other (one fdn_pack_conv64_weights_batch buffer)");
-        if (i == 1) { ex.x1 = dz[ord[1]]; ex.wd1 = (int)d; } else { ex.x2 = dz[ord[2]]; ex.wd2 = (int)d; }
+        if (i == 1) { c.x1 = dz[ord[1]]; c.wd1 = (int)d; } else { c.x2 = dz[ord[2]]; c.wd2 = (int)d; }
     }
-    return fdn_conv64_launch_ex(dz[ord[0]], wpack[ord[0]], nullptr, nullptr, dxpad, skip, y_prev, dz_prev, N, D, H, W, D + 2, H + 2, W + 2,
-                                -1, 1, act, alpha, (hipStream_t)stream, 3, algo, nullptr, nullptr, y_mask, nsrc > 1 ? &ex : nullptr);
+    return fdn_conv64_launch_ex(c, 3, algo);
 }
 
 extern "C" int fdn_conv3d_dgrad_fused_part(const float* dz, const float* wpack, float* dxpad, const float* skip,
                                            const float* y_prev, int act, float alpha, float* dz_prev, int N, int D, int H,
                                            int W, int parts, int algo, void* stream) {
     FDN_REQUIRE(dz && wpack && dxpad && dz_prev, "fdn_conv3d_dgrad_fused_part: NULL argument");
-    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "fdn_conv3d_dgrad_fused_part: bad algo %d", algo);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= 1020 && H <= 1020 && W <= 1020, "fdn_conv3d_dgrad_fused_part: bad dims");
-    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "fdn_conv3d_dgrad_fused_part: bad act %d", act);
+    if (int rc = conv64_check("fdn_conv3d_dgrad_fused_part", algo, N, D, H, W, act)) return rc;
     FDN_REQUIRE(parts >= 1 && parts <= 3, "fdn_conv3d_dgrad_fused_part: parts must be FDN_DGRAD_INNER | FDN_DGRAD_SHELL");
-    return fdn_conv64_launch_ex(dz, wpack, nullptr, nullptr, dxpad, skip, y_prev, dz_prev, N, D, H, W, D + 2, H + 2, W + 2,
-                                -1, 1, act, alpha, (hipStream_t)stream, parts, algo);
+    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz, wpack, dxpad, N, D, H, W, act, alpha, stream);
+    c.fskip = skip; c.fy = y_prev; c.fout = dz_prev;
+    return fdn_conv64_launch_ex(c, parts, algo);
 }
 
 extern "C" int fdn_fold_halo_border(const float* dxpad0, const float* dxpad1, const float* dxpad2, int nsrc,

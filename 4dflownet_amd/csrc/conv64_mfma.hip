@@ -544,35 +544,121 @@ extern "C" int fdn_pack_conv64_weights_batch(const float* w_base, const int64_t*
     return fdn_pack_conv64_weights_batch_streams(w_base, w_offsets, n_layers, packs, FDN_PACK_STREAM_ALL, FDN_PACK_STREAM_ALL, stream);
 }
 
-extern "C" int fdn_conv64_pack_streams(int N, int D, int H, int W, int algo, int role) {
+// --------------------------------------------------------------------------------------------
+// host side: route selection, tile planning, launch
+// --------------------------------------------------------------------------------------------
+namespace {
+
+// How fdn_conv64_launch_ex computes one call.  Forward and plain dgrad (the whole output grid):
+//   WINO2D: the 2-D Winograd kernel;  ALIGNED: the largest (h, w)-aligned box on F(4,3) x F(4,3), the direct kernel the strips beside it;
+//   WINO1D: the 1-D Winograd kernel;  DIRECT: the direct kernel.
+// Fused dgrad -- the inner box [1, ID] x [1, IH] x [1, IW] of the padded grid (all 27 taps, fused-fold epilogue) and its one-voxel shell:
+//   FUSED_ONE: 2-D inner box + 1-D shell faces as ONE launch;  FUSED_PARTS: the same as separate launches;  FUSED_WINO1D: 1-D inner box +
+//   shell (wface_direct: the w faces on the direct kernel);  ALIGNED: the aligned split of the inner box + the shell slabs on the direct
+//   kernel;  FUSED_DIRECT: inner box + six shell slabs as one direct launch.  With shell_slabs = 0 (test build) a fused dgrad takes
+//   WINO1D or DIRECT over the whole padded grid.
+enum Conv64Kind { WINO2D, ALIGNED, WINO1D, DIRECT, FUSED_ONE, FUSED_PARTS, FUSED_WINO1D, FUSED_DIRECT };
+struct Conv64Route {
+    Conv64Kind kind;
+    int hm;              // output rows per cell of the 2-D kernel: 2 or 4 (0: no 2-D launch)
+    bool bf16x3;         // the 2-D kernel's products as three bf16 pieces (FDN_ALGO_WINO_BF16X3)
+    unsigned streams;    // FDN_PACK_STREAM_* bits of the pack streams the route reads
+    bool masks;          // the route writes / reads sign masks (ymask / fmask)
+    bool sources;        // the route takes further sources (nsrc > 1)
+    const char* name;
+};
+
+// The selection rule of fdn_conv64_launch_ex, fdn_conv64_pack_streams and fdn_conv64_mask_ok: pure host code.
+// Staged rows are addressed with 32-bit byte offsets from the sample's first voxel (256 B per voxel).
+int conv64_route(int N, int ID, int IH, int IW, FdnConv64Op op, int parts, int algo, Conv64Route& r) {
+    FDN_REQUIRE((long long)ID * IH * IW < (1ll << 24), "conv64: a sample of %dx%dx%d voxels exceeds the 32-bit row addressing", ID, IH, IW);
+    const int pad = op == FDN_CONV64_FWD ? 0 : 2, OD = ID + pad, OH = IH + pad, OW = IW + pad;
+    // Winograd F(4,3) along W (conv64_wino.hip) whenever the W extent is a multiple of 4: half the MFMA work.  FDN_ALGO_DIRECT
+    // (per call) or a forced direct layout (test build) selects the direct kernel.
+    const bool wino = algo != FDN_ALGO_DIRECT && (fdn_conv64_force_layout == 0 || fdn_conv64_force_layout == 7);
+    // 2-D Winograd (conv64_wino2d.hip): F(4,3) along H on top of F(4,3) along W (6.75 of the 27 tap-equivalents) when H is a multiple
+    // of 4, F(2,3) along H (9 tap-equivalents; FDN_ALGO_WINO_H2 forces it) when H is even
+    const bool wino2 = wino && algo != FDN_ALGO_WINO_W && fdn_conv64_force_layout == 0;
+    auto hm_for = [&](int eh, int ew) {                           // output rows per cell of the 2-D kernel for an (eh, ew) box, 0 = not applicable
+        if (!wino2) return 0;
+        if (algo != FDN_ALGO_WINO_H2 && fdn_conv64_wino2d_ok(1, eh, ew, ID, IH, IW, 4)) return 4;
+        return fdn_conv64_wino2d_ok(1, eh, ew, ID, IH, IW, 2) ? 2 : 0;
+    };
+    // FDN_ALGO_WINO_BF16X3: F(4,3) x F(4,3) boxes read the bf16 x 3 stream and run the SPLIT kernel
+    auto bf16x3 = [&](int hm) { return algo == FDN_ALGO_WINO_BF16X3 && hm == 4; };
+    auto stream_2d = [&](int hm) { return hm == 4 ? (bf16x3(hm) ? 16u : 8u) : 4u; };
+    // Grids off the multiple-of-4 raster (patch sizes 10, 18, 22 are legal: README.md:83 of the reference): the F(4,3) x F(4,3) kernel takes
+    // the largest (h, w)-aligned box -- eh4 x ew4 of eh x ew, when that is most of the grid -- and the direct kernel the one or two
+    // remainder strips beside it (w in [ew4, ew) over all h; h in [eh4, eh) over the aligned w range) as regions of ONE more launch.
+    // Round 6 (tools/bench_small_grids.py, profiles/r6_small_grids.txt): at 8 x 22^3 the all-direct forward costs 0.186 ms, 2.4x the 24^3 grid's.
+    // (W % 4 == 0 grids have Winograd paths of their own; below ~24 K voxels the second launch costs more than the strips' multiplies:
+    // 8 x 10^3: forward 0.037 ms all direct, 0.071 split)
+    auto aligned = [&](int eh, int ew) {
+        const int eh4 = eh & ~3, ew4 = ew & ~3;
+        return wino2 && algo != FDN_ALGO_WINO_H2 && ew4 != ew && eh4 >= 4 && ew4 >= 4 && 2 * eh4 * ew4 >= eh * ew && (long long)N * ID * IH * IW >= 24576 &&
+               fdn_conv64_wino2d_ok(1, eh4, ew4, ID, IH, IW, 4);
+    };
+    if (op != FDN_CONV64_DGRAD_FUSED || !fdn_conv64_shell_slabs) {
+        const bool fused = op == FDN_CONV64_DGRAD_FUSED;           // (a fused fold outside the slab path is the 1-D / direct kernels' business)
+        if (const int hm = fused ? 0 : hm_for(OH, OW))
+            r = {WINO2D, hm, bf16x3(hm), stream_2d(hm), hm == 4 && !bf16x3(hm), false, "2-D Winograd"};
+        else if (!fused && aligned(OH, OW))
+            r = {ALIGNED, 4, bf16x3(4), stream_2d(4) | 1u, false, false, "aligned box + strips"};
+        else if (wino && fdn_conv64_wino_ok(OD, OH, OW))
+            r = {WINO1D, 0, false, 2u, false, false, "1-D Winograd"};
+        else
+            r = {DIRECT, 0, false, 1u, false, false, "direct"};
+        return FDN_OK;
+    }
+    // parts: bit 0 = the inner box (finishes the interior of dz_prev), bit 1 = the six shell slabs (padded scratch only).  The two
+    // write disjoint positions, so a caller may issue them on different streams and join before the border fold.
+    const bool wface_direct = (parts & 2) && fdn_conv64_wface_direct != 0;   // test build: the round-2 path (direct-kernel w faces)
+    if (wino && fdn_conv64_wino_ok(ID, IH, IW)) {
+        const unsigned shell = (parts & 2) ? 2u | (wface_direct ? 1u : 0u) : 0u;
+        if (const int hm = (parts & 1) ? hm_for(IH, IW) : 0) {
+            // round 4: the inner box (95 % / 91 % of the positions at 48^3 / 24^3) on the 2-D Winograd body, the shell faces on the 1-D body
+            // (their single depth / height / width tap has nothing to transform along that axis); bf16 x 3: the inner box is a
+            // persistent launch of its own
+            if ((parts & 2) && !wface_direct && !fdn_conv64_split_dgrad && !bf16x3(hm))
+                r = {FUSED_ONE, hm, false, stream_2d(hm) | 2u, hm == 4, hm == 4, "2-D inner box + 1-D shell"};
+            else
+                r = {FUSED_PARTS, hm, bf16x3(hm), stream_2d(hm) | shell, false, false, "fused dgrad issued in parts"};
+        } else {
+            r = {FUSED_WINO1D, 0, false, 2u | shell, false, false, "1-D Winograd fused dgrad"};
+        }
+    } else if (aligned(IH, IW)) {
+        r = {ALIGNED, 4, bf16x3(4), stream_2d(4) | 1u, false, false, "fused dgrad: aligned box + strips + slabs"};
+    } else {
+        r = {FUSED_DIRECT, 0, false, 1u, false, false, "fused dgrad off the Winograd kernels"};
+    }
+    return FDN_OK;
+}
+
+// fdn_conv64_pack_streams / fdn_conv64_mask_ok: the route of a (N, D, H, W) grid in role `op` (FDN_ROLE_*), after their argument checks
+int conv64_query(int N, int D, int H, int W, int algo, int op, Conv64Route& r) {
     FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "fdn_conv64_pack_streams: bad algo %d", algo);
     FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= 1020 && H <= 1020 && W <= 1020, "fdn_conv64_pack_streams: bad dims");
-    FDN_REQUIRE(role >= FDN_ROLE_FWD && role <= FDN_ROLE_DGRAD_FUSED, "fdn_conv64_pack_streams: bad role %d", role);
-    unsigned m = 0;
-    float* const some = reinterpret_cast<float*>(sizeof(float));      // a fused fold is requested by a non-NULL dz_prev; nothing is dereferenced
-    int rc;
-    if (role == FDN_ROLE_FWD)
-        rc = fdn_conv64_launch_ex(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, D, H, W, D, H, W, 0, 0, FDN_ACT_NONE, 0.f,
-                                  nullptr, 3, algo, &m);
-    else
-        rc = fdn_conv64_launch_ex(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, role == FDN_ROLE_DGRAD_FUSED ? some : nullptr, N, D, H, W,
-                                  D + 2, H + 2, W + 2, -1, 1, FDN_ACT_NONE, 0.f, nullptr, 3, algo, &m);
-    return rc ? rc : (int)m;
+    FDN_REQUIRE(op >= FDN_ROLE_FWD && op <= FDN_ROLE_DGRAD_FUSED, "fdn_conv64_pack_streams: bad role %d", op);
+    return conv64_route(N, D, H, W, (FdnConv64Op)op, 3, algo, r);
+}
+
+}  // namespace
+
+extern "C" int fdn_conv64_pack_streams(int N, int D, int H, int W, int algo, int role) {
+    Conv64Route r;
+    const int rc = conv64_query(N, D, H, W, algo, role, r);
+    return rc ? rc : (int)r.streams;
 }
 
 // 1: the forward and the fused dgrad of a 64->64 layer on this grid both run the plain F(4,3) x F(4,3) fp32-MFMA kernels, which write / read
 // sign masks (fdn_conv64_fwd_mask / fdn_conv64_dgrad_fused_mask); 0: they do not (the caller keeps y); < 0: error.  The launcher's own selection.
 extern "C" int fdn_conv64_mask_ok(int N, int D, int H, int W, int algo) {
-    const int f = fdn_conv64_pack_streams(N, D, H, W, algo, FDN_ROLE_FWD);
-    if (f < 0) return f;
-    const int d = fdn_conv64_pack_streams(N, D, H, W, algo, FDN_ROLE_DGRAD_FUSED);
-    if (d < 0) return d;
-    return f == FDN_PACK_STREAM_WINO_H4 && d == (FDN_PACK_STREAM_WINO_H4 | FDN_PACK_STREAM_WINO_W) ? 1 : 0;
+    Conv64Route f, d;
+    if (int rc = conv64_query(N, D, H, W, algo, FDN_ROLE_FWD, f)) return rc;
+    if (int rc = conv64_query(N, D, H, W, algo, FDN_ROLE_DGRAD_FUSED, d)) return rc;
+    return f.masks && d.masks ? 1 : 0;
 }
 
-// --------------------------------------------------------------------------------------------
-// host side: tile planning + launch
-// --------------------------------------------------------------------------------------------
 namespace {
 
 // an output box of the (OD,OH,OW) grid and the tap range that is non-zero for it
@@ -664,18 +750,24 @@ int launch_conv64(Conv64Args& a, const Box* boxes, int nbox, hipStream_t s) {
 }
 
 // pick the variant from the first (dominant) box, then launch all boxes as regions of ONE launch
-int launch_boxes(Conv64Args& a, const Box* boxes, int nbox, hipStream_t s) {
+int launch_boxes(const FdnConv64Call& c, const Box* boxes, int nbox) {
+    Conv64Args a;
+    a.x = c.x; a.wp = c.wpack; a.bias = c.bias; a.res = c.residual; a.y = c.y;
+    a.fskip = c.fskip; a.fy = c.fy; a.fout = c.fout;
+    a.N = c.N; a.ID = c.ID; a.IH = c.IH; a.IW = c.IW; a.OD = c.OD; a.OH = c.OH; a.OW = c.OW;
+    a.off = c.off(); a.zero_mode = c.zero_mode(); a.act = c.act; a.alpha = c.alpha; a.dbg = fdn_conv64_dbg;
+    const hipStream_t s = c.s;
     const Box& bx = boxes[0];
     // variant table: 1:<2,1,2> 2:<2,1,4> 3:<1,1,2> 4:<1,1,4> 5:<1,2,2> 6:<1,2,4>
-    const double c[7] = {1e30, plan_for<2, 1, 2>(a.N, bx).cost, plan_for<2, 1, 4>(a.N, bx).cost, plan_for<1, 1, 2>(a.N, bx).cost,
-                         1e30, plan_for<1, 2, 2>(a.N, bx).cost, 1e30};
+    const double cost[7] = {1e30, plan_for<2, 1, 2>(a.N, bx).cost, plan_for<2, 1, 4>(a.N, bx).cost, plan_for<1, 1, 2>(a.N, bx).cost,
+                            1e30, plan_for<1, 2, 2>(a.N, bx).cost, 1e30};
     int v = fdn_conv64_force_layout;
     if (v < 1 || v > 6) {
         // auto: cheapest of the cs2 variants (tools/bench_kernels.py: <1,1,cs2> wins at 48^3 N=8 -- 6912 tiles = 27 per CU
         // exactly -- <1,2,cs2> at 24^3; the cs4 variants are never ahead)
         v = 1;
-        if (c[3] < c[v]) v = 3;
-        if (c[5] < c[v]) v = 5;
+        if (cost[3] < cost[v]) v = 3;
+        if (cost[5] < cost[v]) v = 5;
     }
     switch (v) {
         case 1: return launch_conv64<2, 1, 2>(a, boxes, nbox, s);
@@ -691,92 +783,21 @@ int launch_boxes(Conv64Args& a, const Box* boxes, int nbox, hipStream_t s) {
 
 }  // namespace
 
-FdnTile fdn_plan_tile(int N, int OD, int OH, int OW, int max_vox, int max_halo_rows, int) {
-    return best_plan(N, Box{0, 0, 0, OD, OH, OW, 0, 2, 0, 2, 0, 2}, max_vox, max_halo_rows, 2, 1.0).t;
-}
-
-int fdn_conv64_launch_ex(const float* x, const float* wpack, const float* bias, const float* residual, float* y,
-                         const float* fskip, const float* fy, float* fout, int N, int ID, int IH, int IW, int OD, int OH,
-                         int OW, int off, int zero_mode, int act, float alpha, hipStream_t s, int parts, int algo, unsigned* probe,
-                         uint16_t* ymask, const uint16_t* fmask, const FdnExtraSrc* extra) {
-    // ymask / fmask (sign masks, conv64_wino2d_kernel.h): only the plain F(4,3) x F(4,3) fp32-MFMA paths write / read them -- the forward
-    // over the whole grid, the fused dgrad as ONE launch; every other path refuses (the caller asks fdn_conv64_mask_ok first)
-    // extra (further sources of a fused dgrad, fdn_conv64_dgrad_fused_multi): the same rule -- the one-launch F(4,3) x F(4,3) / F(2,3) x F(4,3) form only
-    auto no_mask = [&](const char* what) {
-        if (extra && extra->nsrc > 1) {
-            fdn_set_error("conv64: a multi-source fused dgrad is not supported on this path (%s): ask fdn_conv64_mask_ok", what);
-            return FDN_ERR_UNSUPPORTED;
-        }
-        if (!ymask && !fmask) return FDN_OK;
-        fdn_set_error("conv64: sign masks are not supported on this path (%s): ask fdn_conv64_mask_ok", what);
+// One fp32 64->64 convolution: the route (conv64_route), then its launches.  Sign masks (ymask / fmask, conv64_wino2d_kernel.h) and further
+// sources (fdn_conv64_dgrad_fused_multi) are taken only by the routes that say so: the plain F(4,3) x F(4,3) fp32-MFMA forward over the
+// whole grid and fused dgrad as ONE launch (the caller asks fdn_conv64_mask_ok first).
+int fdn_conv64_launch_ex(const FdnConv64Call& c, int parts, int algo) {
+    Conv64Route r;
+    if (int rc = conv64_route(c.N, c.ID, c.IH, c.IW, c.op, parts, algo, r)) return rc;
+    if (c.nsrc > 1 && !r.sources) {
+        fdn_set_error("conv64: a multi-source fused dgrad is not supported on this path (%s): ask fdn_conv64_mask_ok", r.name);
         return FDN_ERR_UNSUPPORTED;
-    };
-    // probe != nullptr: launch nothing, OR into *probe the streams of the pack this call would read (bit 0 direct, 1 1-D Winograd,
-    // 2 F(2,3)xF(4,3), 3 F(4,3)xF(4,3), 4 the same as bf16 x 3) -- fdn_conv64_pack_streams; the selection below is the only statement of the rule.
-    // staged rows are addressed with 32-bit byte offsets from the sample's first voxel (256 B per voxel)
-    FDN_REQUIRE((long long)ID * IH * IW < (1ll << 24), "conv64: a sample of %dx%dx%d voxels exceeds the 32-bit row addressing", ID, IH, IW);
-    Conv64Args a;
-    a.x = x; a.wp = wpack; a.bias = bias; a.res = residual; a.y = y;
-    a.fskip = fskip; a.fy = fy; a.fout = fout;
-    a.N = N; a.ID = ID; a.IH = IH; a.IW = IW; a.OD = OD; a.OH = OH; a.OW = OW;
-    a.off = off; a.zero_mode = zero_mode; a.act = act; a.alpha = alpha; a.dbg = fdn_conv64_dbg;
-    const Box full{0, 0, 0, OD, OH, OW, 0, 2, 0, 2, 0, 2};
-    // Winograd F(4,3) along W (conv64_wino.hip) whenever the W extent is a multiple of 4: half the MFMA work.  FDN_ALGO_DIRECT
-    // (per call) or a forced direct layout (test build) selects the direct kernel below.
-    const bool wino = algo != FDN_ALGO_DIRECT && (fdn_conv64_force_layout == 0 || fdn_conv64_force_layout == 7);
-    const float* upack = wpack + kDirectPackFloats;
-    const float* upack2 = upack + kWino1PackFloats;
-    // 2-D Winograd (conv64_wino2d.hip): F(4,3) along H on top of F(4,3) along W (6.75 of the 27 tap-equivalents) when H is a multiple
-    // of 4, F(2,3) along H (9 tap-equivalents; FDN_ALGO_WINO_H2 forces it) when H is even
-    const bool wino2 = wino && algo != FDN_ALGO_WINO_W && fdn_conv64_force_layout == 0;
-    auto hm_for = [&](int eh, int ew) {                           // output rows per cell of the 2-D kernel for an (eh, ew) box, 0 = not applicable
-        if (!wino2) return 0;
-        if (algo != FDN_ALGO_WINO_H2 && fdn_conv64_wino2d_ok(1, eh, ew, ID, IH, IW, 4)) return 4;
-        return fdn_conv64_wino2d_ok(1, eh, ew, ID, IH, IW, 2) ? 2 : 0;
-    };
-    // FDN_ALGO_WINO_BF16X3: F(4,3) x F(4,3) grids read the bf16 x 3 stream and run the SPLIT kernel (hm is passed on as 4 | 8)
-    const bool split = algo == FDN_ALGO_WINO_BF16X3;
-    auto upack_hm = [&](int hm) { return hm == 4 ? (split ? upack2 + kWino2PackFloats + kWino44PackFloats : upack2 + kWino2PackFloats) : upack2; };
-    auto stream_bit = [&](int hm) { return hm == 4 ? (split ? 16u : 8u) : 4u; };
-    auto hm_arg = [&](int hm) { return hm == 4 && split ? 12 : hm; };
-    // Grids off the multiple-of-4 raster (patch sizes 10, 18, 22 are legal: README.md:83 of the reference): the F(4,3) x F(4,3) kernel takes
-    // the largest (h, w)-aligned box -- eh4 x ew4 of eh x ew, when that is most of the grid -- and the direct kernel the one or two
-    // remainder strips beside it (w in [ew4, ew) over all h; h in [eh4, eh) over the aligned w range) as regions of ONE more launch.
-    // Round 6 (tools/bench_small_grids.py, profiles/r6_small_grids.txt): at 8 x 22^3 the all-direct forward costs 0.186 ms, 2.4x the 24^3 grid's.
-    auto split_box = [&](int eh, int ew, int& eh4, int& ew4) {
-        eh4 = eh & ~3; ew4 = ew & ~3;
-        // (W % 4 == 0 grids have Winograd paths of their own; below ~24 K voxels the second launch costs more than the strips' multiplies:
-        // 8 x 10^3: forward 0.037 ms all direct, 0.071 split)
-        return wino2 && algo != FDN_ALGO_WINO_H2 && ew4 != ew && eh4 >= 4 && ew4 >= 4 && 2 * eh4 * ew4 >= eh * ew && (long long)N * ID * IH * IW >= 24576 &&
-               fdn_conv64_wino2d_ok(1, eh4, ew4, ID, IH, IW, 4);
-    };
-    if (!(fout && zero_mode && off == -1 && fdn_conv64_shell_slabs)) {
-        if (const int hm = fout ? 0 : hm_for(OH, OW)) {           // (a fused fold outside the slab path is the 1-D / direct kernels' business)
-            if (probe) { *probe |= stream_bit(hm); return FDN_OK; }
-            if (hm != 4 || split) if (int rc = no_mask("not the fp32 F(4,3) x F(4,3) forward")) return rc;
-            return fdn_conv64_wino2d_launch(x, upack_hm(hm), bias, residual, y, nullptr, nullptr, nullptr, N, ID, IH, IW, OD, OH, OW, 0, 0, 0,
-                                            OD, OH, OW, off, zero_mode, act, alpha, hm_arg(hm), s, ymask, nullptr);
-        }
-        if (!probe) if (int rc = no_mask("forward off the F(4,3) x F(4,3) kernel")) return rc;
-        int oh4, ow4;
-        if (!fout && split_box(OH, OW, oh4, ow4)) {
-            if (probe) { *probe |= stream_bit(4) | 1u; return FDN_OK; }
-            if (int rc = no_mask("aligned box + strips")) return rc;
-            if (int rc = fdn_conv64_wino2d_launch(x, upack_hm(4), bias, residual, y, nullptr, nullptr, nullptr, N, ID, IH, IW, OD, OH, OW, 0, 0, 0,
-                                                  OD, oh4, ow4, off, zero_mode, act, alpha, hm_arg(4), s))
-                return rc;
-            const Box strips[2] = {{0, 0, ow4, OD, OH, OW - ow4, 0, 2, 0, 2, 0, 2}, {0, oh4, 0, OD, OH - oh4, ow4, 0, 2, 0, 2, 0, 2}};
-            const int first = OW > ow4 ? 0 : 1, count = (OW > ow4 ? 1 : 0) + (OH > oh4 ? 1 : 0);
-            return launch_boxes(a, strips + first, count, s);
-        }
-        if (wino && fdn_conv64_wino_ok(OD, OH, OW)) {
-            if (probe) { *probe |= 2u; return FDN_OK; }
-            return fdn_conv64_wino_launch(x, upack, bias, residual, y, fskip, fy, fout, N, ID, IH, IW, OD, OH, OW, 0, 0, 0, OD, OH,
-                                          OW, off, zero_mode, act, alpha, s);
-        }
-        if (probe) { *probe |= 1u; return FDN_OK; }
-        return launch_boxes(a, &full, 1, s);
     }
+    if ((c.ymask || c.fmask) && !r.masks) {
+        fdn_set_error("conv64: sign masks are not supported on this path (%s): ask fdn_conv64_mask_ok", r.name);
+        return FDN_ERR_UNSUPPORTED;
+    }
+    const int ID = c.ID, IH = c.IH, IW = c.IW, OD = c.OD, OH = c.OH, OW = c.OW;
     // Fused dgrad on the padded grid (OD = ID+2): padded index p <-> position P = p-1 reads dz[p - 2 + tap], zero outside.
     // The inner box p in [1,ID]^3 needs all 27 taps.  Every shell position has at least one coordinate at 0 or ID+1, where
     // only tap 2 (resp. tap 0) of that dimension can reach a real voxel: six disjoint 1-voxel slabs with 9 taps each
@@ -787,77 +808,56 @@ int fdn_conv64_launch_ex(const float* x, const float* wpack, const float* bias, 
         {0, 0, 0, 1, OH, OW, 2, 2, 0, 2, 0, 2},       {ID + 1, 0, 0, 1, OH, OW, 0, 0, 0, 2, 0, 2},     // d faces, full (h,w)
         {1, 0, 0, ID, 1, OW, 0, 2, 2, 2, 0, 2},       {1, IH + 1, 0, ID, 1, OW, 0, 2, 0, 0, 0, 2},     // h faces, d inner
         {1, 1, 0, ID, IH, 1, 0, 2, 0, 2, 2, 2},       {1, 1, IW + 1, ID, IH, 1, 0, 2, 0, 2, 0, 0}};    // w faces, d,h inner
-    // parts: bit 0 = the inner box (finishes the interior of dz_prev), bit 1 = the six shell slabs (padded scratch only).  The two
-    // write disjoint positions, so a caller may issue them on different streams and join before the border fold.
-    if (wino && fdn_conv64_wino_ok(ID, IH, IW)) {
-        // ONE Winograd launch: the inner box (fused-fold epilogue) + the d and h faces of the shell restricted to the inner W
-        // range (one depth resp. height tap each: a third of the work per tile, dispatched last, they fill the tail) + the pair of
-        // w faces over the full (d,h) range as a region of its own (a single W tap = one Winograd coordinate per face: K loop over
-        // xi in {0, 5}, no output transform; conv64_wino.hip).  Until round 3 the w faces were a separate launch of the direct kernel.
-        const FdnWinoBox wb[6] = {
-            {1, 1, 1, ID, IH, IW, 0, 2, 0, 2, 0},
-            {0, 0, 1, 1, OH, IW, 2, 2, 0, 2, 0}, {ID + 1, 0, 1, 1, OH, IW, 0, 0, 0, 2, 0},        // d faces, full h
-            {1, 0, 1, ID, 1, IW, 0, 2, 2, 2, 0}, {1, IH + 1, 1, ID, 1, IW, 0, 2, 0, 0, 0},       // h faces, d inner
-            {0, 0, 0, OD, OH, 4, 0, 2, 0, 2, 1}};                                                // w faces, full (d,h)
-        const Box wfaces[2] = {{0, 0, 0, OD, OH, 1, 0, 2, 0, 2, 2, 2}, {0, 0, IW + 1, OD, OH, 1, 0, 2, 0, 2, 0, 0}};
-        const bool wface_direct = fdn_conv64_wface_direct != 0;       // test build: the round-2 path (direct-kernel slab launch)
-        int first = (parts & 1) ? 0 : 1;
-        int count = ((parts & 1) ? 1 : 0) + ((parts & 2) ? (wface_direct ? 4 : 5) : 0);
-        if (const int hm = (parts & 1) ? hm_for(IH, IW) : 0) {
-            // round 4: the inner box (all 27 taps, fused-fold epilogue; 95 % / 91 % of the positions at 48^3 / 24^3) on the 2-D Winograd
-            // body, the shell faces on the 1-D body (their single depth / height / width tap has nothing to transform along that axis)
-            if ((parts & 2) && !wface_direct && !fdn_conv64_split_dgrad && !(split && hm == 4)) {      // (bf16 x 3: the inner box is a persistent launch of its own)
-                // both parts: ONE launch, the shell faces behind the inner box's workgroups (conv64_wino2d_shell_kernel, conv64_wino.hip)
-                if (probe) { *probe |= stream_bit(hm) | 2u; return FDN_OK; }
-                if (hm != 4) if (int rc = no_mask("not the fp32 F(4,3) x F(4,3) fused dgrad")) return rc;
-                FdnWino2dPrepared inner;
-                if (int rc = fdn_conv64_wino2d_prepare(x, upack_hm(hm), bias, residual, y, fskip, fy, fout, N, ID, IH, IW, OD, OH, OW, 1, 1, 1, ID,
-                                                       IH, IW, off, zero_mode, act, alpha, hm_arg(hm), &inner, nullptr, fmask, extra))
-                    return rc;
-                return fdn_conv64_wino_launch_boxes(x, upack, bias, residual, y, fskip, fy, fout, N, ID, IH, IW, OD, OH, OW, wb + 1, count - 1,
-                                                    off, zero_mode, act, alpha, s, &inner, extra);
+    // The 1-D Winograd form: the inner box (fused-fold epilogue) + the d and h faces of the shell restricted to the inner W range (one
+    // depth resp. height tap each: a third of the work per tile, dispatched last, they fill the tail) + the pair of w faces over the
+    // full (d,h) range as a region of its own (a single W tap = one Winograd coordinate per face: K loop over xi in {0, 5}, no output
+    // transform; conv64_wino.hip).  Until round 3 the w faces were a separate launch of the direct kernel (wface_direct).
+    const FdnWinoBox wb[6] = {
+        {1, 1, 1, ID, IH, IW, 0, 2, 0, 2, 0},
+        {0, 0, 1, 1, OH, IW, 2, 2, 0, 2, 0}, {ID + 1, 0, 1, 1, OH, IW, 0, 0, 0, 2, 0},        // d faces, full h
+        {1, 0, 1, ID, 1, IW, 0, 2, 2, 2, 0}, {1, IH + 1, 1, ID, 1, IW, 0, 2, 0, 0, 0},       // h faces, d inner
+        {0, 0, 0, OD, OH, 4, 0, 2, 0, 2, 1}};                                                // w faces, full (d,h)
+    const Box wfaces[2] = {{0, 0, 0, OD, OH, 1, 0, 2, 0, 2, 2, 2}, {0, 0, IW + 1, OD, OH, 1, 0, 2, 0, 2, 0, 0}};
+    const Box full{0, 0, 0, OD, OH, OW, 0, 2, 0, 2, 0, 2};                                   // the whole output grid
+    const FdnWinoBox wfull{0, 0, 0, OD, OH, OW, 0, 2, 0, 2, 0};
+    switch (r.kind) {
+        case WINO2D:
+            return fdn_conv64_wino2d_launch(c, r.hm, r.bf16x3, 0, 0, 0, OD, OH, OW);
+        case ALIGNED: {
+            // the aligned box and the strips beside it (ew4 < ew: the route's condition) of the output grid, or of a fused dgrad's inner
+            // box (fused-fold epilogue in both kernels) with the six shell slabs behind it
+            const bool fused = c.op == FDN_CONV64_DGRAD_FUSED;
+            const int o = fused ? 1 : 0, ed = fused ? ID : OD, eh = fused ? IH : OH, ew = fused ? IW : OW, eh4 = eh & ~3, ew4 = ew & ~3;
+            if (!fused || (parts & 1)) {
+                if (int rc = fdn_conv64_wino2d_launch(c, 4, r.bf16x3, o, o, o, ed, eh4, ew4)) return rc;
+                const Box strips[2] = {{o, o, o + ew4, ed, eh, ew - ew4, 0, 2, 0, 2, 0, 2}, {o, o + eh4, o, ed, eh - eh4, ew4, 0, 2, 0, 2, 0, 2}};
+                if (int rc = launch_boxes(c, strips, eh > eh4 ? 2 : 1)) return rc;
             }
-            if (!probe) if (int rc = no_mask("fused dgrad issued in parts")) return rc;
-            if (probe) *probe |= stream_bit(hm);
-            else if (int rc = fdn_conv64_wino2d_launch(x, upack_hm(hm), bias, residual, y, fskip, fy, fout, N, ID, IH, IW, OD, OH, OW, 1, 1, 1, ID, IH,
-                                                       IW, off, zero_mode, act, alpha, hm_arg(hm), s))
-                return rc;
-            first = 1; count -= 1;
-            if (count == 0) return FDN_OK;
+            return fused && (parts & 2) ? launch_boxes(c, boxes + 1, 6) : FDN_OK;
         }
-        if (!probe) if (int rc = no_mask("1-D Winograd fused dgrad")) return rc;
-        if (probe) { *probe |= 2u | (((parts & 2) && wface_direct) ? 1u : 0u); return FDN_OK; }
-        if (int rc = fdn_conv64_wino_launch_boxes(x, upack, bias, residual, y, fskip, fy, fout, N, ID, IH, IW, OD, OH, OW, wb + first,
-                                                  count, off, zero_mode, act, alpha, s))
-            return rc;
-        return ((parts & 2) && wface_direct) ? launch_boxes(a, wfaces, 2, s) : FDN_OK;
-    }
-    if (!probe) if (int rc = no_mask("fused dgrad off the Winograd kernels")) return rc;
-    int ih4, iw4;
-    if (split_box(IH, IW, ih4, iw4)) {
-        // the same split of the inner box [1, ID] x [1, IH] x [1, IW] (fused-fold epilogue in both kernels), the six shell slabs behind it
-        if (probe) { *probe |= stream_bit(4) | 1u; return FDN_OK; }
-        if (parts & 1) {
-            if (int rc = fdn_conv64_wino2d_launch(x, upack_hm(4), bias, residual, y, fskip, fy, fout, N, ID, IH, IW, OD, OH, OW, 1, 1, 1, ID, ih4,
-                                                  iw4, off, zero_mode, act, alpha, hm_arg(4), s))
-                return rc;
-            const Box strips[2] = {{1, 1, 1 + iw4, ID, IH, IW - iw4, 0, 2, 0, 2, 0, 2}, {1, 1 + ih4, 1, ID, IH - ih4, iw4, 0, 2, 0, 2, 0, 2}};
-            const int first = IW > iw4 ? 0 : 1, count = (IW > iw4 ? 1 : 0) + (IH > ih4 ? 1 : 0);
-            if (int rc = launch_boxes(a, strips + first, count, s)) return rc;
+        case WINO1D: return fdn_conv64_wino_launch_boxes(c, &wfull, 1);
+        case DIRECT: return launch_boxes(c, &full, 1);
+        case FUSED_ONE: {
+            // the shell faces behind the inner box's workgroups (conv64_wino2d_shell_kernel, conv64_wino.hip)
+            FdnWino2dPrepared inner;
+            if (int rc = fdn_conv64_wino2d_prepare(c, r.hm, false, 1, 1, 1, ID, IH, IW, &inner)) return rc;
+            return fdn_conv64_wino_launch_boxes(c, wb + 1, 5, &inner);
         }
-        return (parts & 2) ? launch_boxes(a, boxes + 1, 6, s) : FDN_OK;
+        case FUSED_PARTS:
+            if (int rc = fdn_conv64_wino2d_launch(c, r.hm, r.bf16x3, 1, 1, 1, ID, IH, IW)) return rc;
+            [[fallthrough]];
+        case FUSED_WINO1D: {
+            // one 1-D launch of wb[first, last): the inner box unless the 2-D kernel took it or parts leaves it out, the shell faces of parts
+            const bool wface_direct = (parts & 2) && fdn_conv64_wface_direct != 0;
+            const int first = r.kind == FUSED_PARTS || !(parts & 1) ? 1 : 0, last = (parts & 2) ? (wface_direct ? 5 : 6) : 1;
+            if (last > first)
+                if (int rc = fdn_conv64_wino_launch_boxes(c, wb + first, last - first)) return rc;
+            return wface_direct ? launch_boxes(c, wfaces, 2) : FDN_OK;
+        }
+        case FUSED_DIRECT:                                         // (parts: 1..3)
+            return launch_boxes(c, boxes + ((parts & 1) ? 0 : 1), ((parts & 1) ? 1 : 0) + ((parts & 2) ? 6 : 0));
     }
-    if (probe) { *probe |= 1u; return FDN_OK; }
-    if (parts == 3) return launch_boxes(a, boxes, 7, s);
-    if (parts & 1) return launch_boxes(a, boxes, 1, s);
-    return (parts & 2) ? launch_boxes(a, boxes + 1, 6, s) : FDN_OK;
-}
-
-int fdn_conv64_launch(const float* x, const float* wpack, const float* bias, const float* residual, float* y, int N,
-                      int ID, int IH, int IW, int OD, int OH, int OW, int off, int zero_mode, int act, float alpha,
-                      hipStream_t s, int algo) {
-    return fdn_conv64_launch_ex(x, wpack, bias, residual, y, nullptr, nullptr, nullptr, N, ID, IH, IW, OD, OH, OW, off,
-                                zero_mode, act, alpha, s, 3, algo, nullptr);
+    return FDN_OK;
 }
 
 int fdn_fold_halo_border_launch(const float* s0, const float* s1, const float* s2, int nsrc, const float* skip,

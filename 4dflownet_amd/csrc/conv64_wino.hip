@@ -94,23 +94,17 @@ WinoPlan wino_plan(int N, const FdnWinoBox& bx, bool tail) {
 // Is the Winograd kernel applicable to this output box?  (W extent a multiple of 4; everything else falls to the direct kernel.)
 bool fdn_conv64_wino_ok(int ebd, int ebh, int ebw) { return ebd > 0 && ebh > 0 && ebw >= 4 && (ebw & 3) == 0; }
 
-int fdn_conv64_wino_launch_boxes(const float* x, const float* upack, const float* bias, const float* residual, float* y,
-                                 const float* fskip, const float* fy, float* fout, int N, int ID, int IH, int IW, int OD, int OH,
-                                 int OW, const FdnWinoBox* boxes, int nbox, int off, int zero_mode, int act, float alpha,
-                                 hipStream_t s, const FdnWino2dPrepared* inner, const FdnExtraSrc* extra) {
+int fdn_conv64_wino_launch_boxes(const FdnConv64Call& c, const FdnWinoBox* boxes, int nbox, const FdnWino2dPrepared* inner) {
+    const int N = c.N, ID = c.ID, IH = c.IH, IW = c.IW;
     FDN_REQUIRE((long long)ID * IH * IW < (1ll << 24), "conv64 (winograd): a sample of %dx%dx%d voxels exceeds the 32-bit row addressing", ID, IH, IW);
     FDN_REQUIRE(nbox >= 1 && nbox <= 6, "conv64 (winograd): %d regions", nbox);
     constexpr int CS = kWinoCS, LROW = 256 / CS + 16, CH = 256 / CS / 16;
     WinoArgs a;
-    a.x = x; a.up = upack; a.bias = bias; a.res = residual; a.y = y; a.fskip = fskip; a.fy = fy; a.fout = fout;
-    a.x1 = a.x2 = nullptr; a.wd1 = a.wd2 = 0; a.nsrc = 1; a.wspan = 0;
-    if (extra) {
-        FDN_REQUIRE(inner && fout && extra->nsrc >= 1 && extra->nsrc <= 3, "conv64 (winograd): further sources belong to the one-launch fused dgrad, 1..3 in all");
-        a.x1 = extra->x1; a.x2 = extra->x2; a.wd1 = extra->wd1; a.wd2 = extra->wd2; a.nsrc = extra->nsrc;
-        a.wspan = extra->nsrc > 2 ? extra->wd2 : (extra->nsrc > 1 ? extra->wd1 : 0);
-    }
-    a.N = N; a.ID = ID; a.IH = IH; a.IW = IW; a.OD = OD; a.OH = OH; a.OW = OW;
-    a.off = off; a.zero_mode = zero_mode; a.act = act; a.alpha = alpha; a.dbg = fdn_conv64_wino_dbg;
+    a.x = c.x; a.up = c.wpack + 27 * 64 * 64; a.bias = c.bias; a.res = c.residual; a.y = c.y;      // (the 1-D stream: pack + 27*4096)
+    a.fskip = c.fskip; a.fy = c.fy; a.fout = c.fout;
+    fdn_conv64_set_sources(a, c);
+    a.N = N; a.ID = ID; a.IH = IH; a.IW = IW; a.OD = c.OD; a.OH = c.OH; a.OW = c.OW;
+    a.off = c.off(); a.zero_mode = c.zero_mode(); a.act = c.act; a.alpha = c.alpha; a.dbg = fdn_conv64_wino_dbg;
     a.nreg = 0;
     long long blocks = 0;
     int max_ltg = 0;
@@ -121,7 +115,7 @@ int fdn_conv64_wino_launch_boxes(const float* x, const float* upack, const float
         const FdnWinoBox& bx = boxes[i];
         if (bx.ed <= 0 || bx.eh <= 0 || bx.ew <= 0) continue;
         FDN_REQUIRE(fdn_conv64_wino_ok(bx.ed, bx.eh, bx.ew), "conv64 (winograd): W extent %d is not a multiple of 4", bx.ew);
-        FDN_REQUIRE(!bx.wface || (zero_mode && fout && bx.ew == 4 && bx.ow == 0 && bx.ta0 == 0 && bx.ta1 == 2 && bx.tb0 == 0 && bx.tb1 == 2),
+        FDN_REQUIRE(!bx.wface || (c.zero_mode() && c.fout && bx.ew == 4 && bx.ow == 0 && bx.ta0 == 0 && bx.ta1 == 2 && bx.tb0 == 0 && bx.tb1 == 2),
                     "conv64 (winograd): a w-face region belongs to a fused dgrad launch");
         WinoPlan pl = wino_plan(N, bx, bx.wface != 0);
         if (fdn_conv64_wino_tile && a.nreg == 0) {
@@ -159,7 +153,7 @@ int fdn_conv64_wino_launch_boxes(const float* x, const float* upack, const float
         for (int i = 0, o = 0; i < a.nreg && o < 200; ++i)
             o += snprintf(regs + o, sizeof(regs) - o, " r%d=%dx%dx%d%s", i, a.reg[i].td, a.reg[i].th, a.reg[i].tg, a.reg[i].wface ? "w" : "");
         FDN_PLAN("fam=%s op=%s dt=f32 N=%d D=%d H=%d W=%d nreg=%d%s nsrc=%d grid=%lld tiles=%lld cus=%d",
-                 inner ? "wino2d_shell" : (shell_only ? "wino1d_shell" : "wino1d"), fout ? "dgrad" : "fwd", N, ID, IH, IW, a.nreg, regs,
+                 inner ? "wino2d_shell" : (shell_only ? "wino1d_shell" : "wino1d"), c.fout ? "dgrad" : "fwd", N, ID, IH, IW, a.nreg, regs,
                  a.nsrc, blocks + (inner ? inner->blocks : 0), blocks + (inner ? inner->blocks : 0), fdn_plan_cus());
     }
 #endif
@@ -180,7 +174,7 @@ int fdn_conv64_wino_launch_boxes(const float* x, const float* upack, const float
         if (int rc = fdn_func_max_lds(fn, lds_max, "conv64_wino2d_shell")) return rc;
         int n2d = inner->blocks;
         void* kargs[] = {(void*)&a2, (void*)&a, (void*)&n2d};
-        const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(blocks + inner->blocks)), dim3(256), kargs, lds, s);
+        const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(blocks + inner->blocks)), dim3(256), kargs, lds, c.s);
         if (e != hipSuccess) {
             fdn_set_error("conv64_wino2d_shell_kernel: launch failed: %s", hipGetErrorString(e));
             return FDN_ERR_HIP;
@@ -189,19 +183,10 @@ int fdn_conv64_wino_launch_boxes(const float* x, const float* upack, const float
     }
     const WinoRegion& r0 = a.reg[0];
     const bool simple = a.nreg == 1 && r0.ta0 == 0 && r0.ta1 == 2 && r0.tb0 == 0 && r0.tb1 == 2;
-    if (simple) hipLaunchKernelGGL((conv64_wino_kernel<CS, false>), dim3((unsigned)blocks), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((conv64_wino_kernel<CS, true>), dim3((unsigned)blocks), dim3(256), lds, s, a);
+    if (simple) hipLaunchKernelGGL((conv64_wino_kernel<CS, false>), dim3((unsigned)blocks), dim3(256), lds, c.s, a);
+    else hipLaunchKernelGGL((conv64_wino_kernel<CS, true>), dim3((unsigned)blocks), dim3(256), lds, c.s, a);
     FDN_CHECK_LAUNCH("conv64_wino_kernel");
     return FDN_OK;
-}
-
-int fdn_conv64_wino_launch(const float* x, const float* upack, const float* bias, const float* residual, float* y,
-                           const float* fskip, const float* fy, float* fout, int N, int ID, int IH, int IW, int OD, int OH,
-                           int OW, int obd, int obh, int obw, int ebd, int ebh, int ebw, int off, int zero_mode, int act,
-                           float alpha, hipStream_t s) {
-    const FdnWinoBox bx{obd, obh, obw, ebd, ebh, ebw, 0, 2, 0, 2};
-    return fdn_conv64_wino_launch_boxes(x, upack, bias, residual, y, fskip, fy, fout, N, ID, IH, IW, OD, OH, OW, &bx, 1, off,
-                                        zero_mode, act, alpha, s);
 }
 
 #ifdef FDN_TEST_HOOKS

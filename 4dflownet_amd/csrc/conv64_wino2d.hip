@@ -121,42 +121,34 @@ Wino2Plan wino2d_plan(int N, int ed, int ech, int ecw, int mb) {
 // addressable with 30-bit byte offsets -- the staging plan adds a row offset and a column offset, each of which may be the
 // "reads zero" marker 2^30.)
 bool fdn_conv64_wino2d_ok(int ebd, int ebh, int ebw, int ID, int IH, int IW, int hm) {
-    hm &= 7;                                            // (bit 3 of a launcher's hm argument: the bf16 x 3 products, FDN_ALGO_WINO_BF16X3)
     return (hm == 2 || hm == 4) && ebd > 0 && ebh >= hm && ebh % hm == 0 && ebw >= 4 && (ebw & 3) == 0 && (long long)ID * IH * IW <= (1ll << 22);
 }
 
 static_assert(sizeof(Wino2Args) <= sizeof(FdnWino2dPrepared::args), "FdnWino2dPrepared::args too small");
 
-int fdn_conv64_wino2d_prepare(const float* x, const float* upack2, const float* bias, const float* residual, float* y,
-                              const float* fskip, const float* fy, float* fout, int N, int ID, int IH, int IW, int OD, int OH,
-                              int OW, int obd, int obh, int obw, int ebd, int ebh, int ebw, int off, int zero_mode, int act,
-                              float alpha, int hm_arg, FdnWino2dPrepared* out, uint16_t* ymask, const uint16_t* fmask, const FdnExtraSrc* extra) {
-    const int hm = hm_arg & 7;
-    const bool split = (hm_arg & 8) != 0;               // F(4,3) x F(4,3) products as bf16 x 3 (upack2 = that stream)
-    FDN_REQUIRE(!split || hm == 4, "conv64 (2-D winograd): the bf16 x 3 products exist for F(4,3) along H only");
+// bf16x3 (F(4,3) along H only): the products as three bf16 pieces, FDN_ALGO_WINO_BF16X3
+int fdn_conv64_wino2d_prepare(const FdnConv64Call& c, int hm, bool bf16x3, int obd, int obh, int obw, int ebd, int ebh, int ebw,
+                              FdnWino2dPrepared* out) {
+    const int N = c.N, ID = c.ID, IH = c.IH, IW = c.IW;
+    FDN_REQUIRE(!bf16x3 || hm == 4, "conv64 (2-D winograd): the bf16 x 3 products exist for F(4,3) along H only");
     FDN_REQUIRE(fdn_conv64_wino2d_ok(ebd, ebh, ebw, ID, IH, IW, hm), "conv64 (2-D winograd, F(%d,3) along H): box %dx%dx%d of a %dx%dx%d grid is not supported",
                 hm, ebd, ebh, ebw, ID, IH, IW);
-    FDN_REQUIRE(!fout || (zero_mode && off == -1 && obd == 1 && obh == 1 && obw == 1), "conv64 (2-D winograd): the fused fold belongs to the inner box of a padded dgrad");
-    FDN_REQUIRE(!(ymask || fmask) || (hm == 4 && !split && (fmask ? fout != nullptr : fout == nullptr)),
-                "conv64 (2-D winograd): sign masks belong to the F(4,3) x F(4,3) fp32-MFMA kernels (forward writes, fused dgrad reads)");
+    FDN_REQUIRE(!c.fout || (obd == 1 && obh == 1 && obw == 1), "conv64 (2-D winograd): the fused fold belongs to the inner box of a padded dgrad");
     Wino2Args a;
-    a.x = x; a.up = upack2; a.bias = bias; a.res = residual; a.y = y; a.fskip = fskip; a.fy = fy; a.fout = fout;
-    a.ymask = ymask; a.fmask = fmask;
-    a.x1 = a.x2 = nullptr; a.wd1 = a.wd2 = 0; a.nsrc = 1; a.wspan = 0;
-    if (extra) {
-        FDN_REQUIRE(fout && !split && extra->nsrc >= 1 && extra->nsrc <= 3, "conv64 (2-D winograd): further sources belong to a fused dgrad (fp32-MFMA), 1..3 in all");
-        a.x1 = extra->x1; a.x2 = extra->x2; a.wd1 = extra->wd1; a.wd2 = extra->wd2; a.nsrc = extra->nsrc;
-        a.wspan = extra->nsrc > 2 ? extra->wd2 : (extra->nsrc > 1 ? extra->wd1 : 0);
-    }
-    a.N = N; a.ID = ID; a.IH = IH; a.IW = IW; a.OD = OD; a.OH = OH; a.OW = OW;
-    a.off = off; a.zero_mode = zero_mode; a.act = act; a.alpha = alpha; a.dbg = fdn_conv64_wino2d_dbg;
-    a.hm = hm; a.split = split ? 1 : 0;
+    // the stream (FDN_CONV64_PACK_FLOATS): F(2,3) x F(4,3) at pack + 81*4096, F(4,3) x F(4,3) at + 153*4096, its bf16 x 3 form at + 261*4096
+    a.x = c.x; a.up = c.wpack + (hm == 2 ? 81 : bf16x3 ? 261 : 153) * 64 * 64; a.bias = c.bias; a.res = c.residual; a.y = c.y;
+    a.fskip = c.fskip; a.fy = c.fy; a.fout = c.fout;
+    a.ymask = c.ymask; a.fmask = c.fmask;
+    fdn_conv64_set_sources(a, c);
+    a.N = N; a.ID = ID; a.IH = IH; a.IW = IW; a.OD = c.OD; a.OH = c.OH; a.OW = c.OW;
+    a.off = c.off(); a.zero_mode = c.zero_mode(); a.act = c.act; a.alpha = c.alpha; a.dbg = fdn_conv64_wino2d_dbg;
+    a.hm = hm; a.split = bf16x3 ? 1 : 0;
     a.obd = obd; a.obh = obh; a.obw = obw; a.ebd = ebd; a.ebh = ebh; a.ebw = ebw;
     const int ech = ebh / hm, ecw = ebw / 4;
     Wino2Plan pl = wino2d_plan(N, ebd, ech, ecw, 2);
     // half-size tiles (F(4,3) along H only) where the full-size ones leave CUs with one workgroup or none: kW2HalfBelow full tiles
     int mb = 2;
-    if (hm == 4 && !split) {
+    if (hm == 4 && !bf16x3) {
         const long long full = (long long)N * ((ebd + pl.td - 1) / pl.td) * ((ech + pl.ch - 1) / pl.ch) * ((ecw + pl.cw - 1) / pl.cw);
         if (full < kW2HalfBelow) mb = 1;
         if (fdn_conv64_wino2d_mb) mb = fdn_conv64_wino2d_mb;
@@ -180,55 +172,47 @@ int fdn_conv64_wino2d_prepare(const float* x, const float* upack2, const float* 
     const long long blocks = (long long)N * a.ntd * a.nth * a.ntw;
     FDN_REQUIRE(blocks < (1ll << 31), "conv64 (2-D winograd): too many tiles");
     FDN_PLAN("fam=%s op=%s dt=f32 N=%d D=%d H=%d W=%d hm=%d split=%d mb=%d tile=%dx%dx%d ymask=%d fmask=%d nsrc=%d grid=%lld tiles=%lld cus=%d",
-             (ebh < (fout ? IH : OH) || ebw < (fout ? IW : OW)) ? "wino2d_aligned" : "wino2d", fout ? "dgrad" : "fwd", N, ID, IH, IW, hm,
-             a.split, mb, pl.td, pl.ch, pl.cw, ymask != nullptr, fmask != nullptr, a.nsrc, split ? (blocks < device_cus() ? blocks : (long long)device_cus()) : blocks,
+             (ebh < (c.fout ? IH : c.OH) || ebw < (c.fout ? IW : c.OW)) ? "wino2d_aligned" : "wino2d", c.fout ? "dgrad" : "fwd", N, ID, IH, IW, hm,
+             a.split, mb, pl.td, pl.ch, pl.cw, c.ymask != nullptr, c.fmask != nullptr, a.nsrc, bf16x3 ? (blocks < device_cus() ? blocks : (long long)device_cus()) : blocks,
              blocks, fdn_plan_cus());
     memcpy(out->args, &a, sizeof(a));
     out->blocks = (int)blocks;
-    out->lds = split ? W2Geo<2, true>::lds : (mb == 2 ? kW2Lds : W2Geo<1>::lds);
+    out->lds = bf16x3 ? W2Geo<2, true>::lds : (mb == 2 ? kW2Lds : W2Geo<1>::lds);
     return FDN_OK;
 }
 
-int fdn_conv64_wino2d_launch(const float* x, const float* upack2, const float* bias, const float* residual, float* y,
-                             const float* fskip, const float* fy, float* fout, int N, int ID, int IH, int IW, int OD, int OH,
-                             int OW, int obd, int obh, int obw, int ebd, int ebh, int ebw, int off, int zero_mode, int act,
-                             float alpha, int hm_arg, hipStream_t s, uint16_t* ymask, const uint16_t* fmask) {
-    const int hm = hm_arg & 7;
+int fdn_conv64_wino2d_launch(const FdnConv64Call& c, int hm, bool bf16x3, int obd, int obh, int obw, int ebd, int ebh, int ebw) {
     FdnWino2dPrepared pr;
-    if (int rc = fdn_conv64_wino2d_prepare(x, upack2, bias, residual, y, fskip, fy, fout, N, ID, IH, IW, OD, OH, OW, obd, obh, obw, ebd,
-                                           ebh, ebw, off, zero_mode, act, alpha, hm_arg, &pr, ymask, fmask))
-        return rc;
+    if (int rc = fdn_conv64_wino2d_prepare(c, hm, bf16x3, obd, obh, obw, ebd, ebh, ebw, &pr)) return rc;
     Wino2Args a;
     memcpy(&a, pr.args, sizeof(a));
     const long long blocks = pr.blocks;
     if (a.split) {
         // bf16 x 3 products: one persistent producer / consumer workgroup per CU walks the tiles
-        const void* fnp = fout ? (const void*)conv64_wino2d_pc_kernel<true> : (const void*)conv64_wino2d_pc_kernel<false>;
+        const void* fnp = c.fout ? (const void*)conv64_wino2d_pc_kernel<true> : (const void*)conv64_wino2d_pc_kernel<false>;
         bool sync_variant = false;
 #ifdef FDN_TEST_HOOKS
         sync_variant = fdn_conv64_wino2d_variant == 10;           // test build: the barrier-synchronous bf16 x 3 kernel (SPLIT body), for A/B
-        if (sync_variant) fnp = fout ? (const void*)conv64_wino2d_kernel<true, 4, 2, true> : (const void*)conv64_wino2d_kernel<false, 4, 2, true>;
+        if (sync_variant) fnp = c.fout ? (const void*)conv64_wino2d_kernel<true, 4, 2, true> : (const void*)conv64_wino2d_kernel<false, 4, 2, true>;
 #endif
         const int ldsp = sync_variant ? W2Geo<2, true>::lds : kPcLds;
         if (int rc = fdn_func_max_lds(fnp, ldsp, "conv64_wino2d_pc")) return rc;
         const int cus = device_cus();
         const unsigned grid = sync_variant ? (unsigned)blocks : (unsigned)(blocks < cus ? blocks : cus);
         void* kargs[] = {(void*)&a};
-        const hipError_t e = hipLaunchKernel(fnp, dim3(grid), dim3(sync_variant ? 256 : kPcThreads), kargs, ldsp, s);
+        const hipError_t e = hipLaunchKernel(fnp, dim3(grid), dim3(sync_variant ? 256 : kPcThreads), kargs, ldsp, c.s);
         if (e != hipSuccess) {
             fdn_set_error("conv64_wino2d_pc_kernel: launch failed: %s", hipGetErrorString(e));
             return FDN_ERR_HIP;
         }
         return FDN_OK;
     }
-    FDN_REQUIRE(!a.fmask, "conv64 (2-D winograd): the mask-reading fused dgrad is the one-launch form (inner box + shell)");
-    FDN_REQUIRE(a.nsrc == 1, "conv64 (2-D winograd): the multi-source fused dgrad is the one-launch form (inner box + shell)");
     const void* fn = a.ymask ? (a.mb == 1 ? (const void*)conv64_wino2d_kernel<false, 4, 1, false, true> : (const void*)conv64_wino2d_kernel<false, 4, 2, false, true>)
-                   : fout ? (hm == 4 ? (a.mb == 1 ? (const void*)conv64_wino2d_kernel<true, 4, 1> : (const void*)conv64_wino2d_kernel<true, 4>) : (const void*)conv64_wino2d_kernel<true, 2>)
+                   : c.fout ? (hm == 4 ? (a.mb == 1 ? (const void*)conv64_wino2d_kernel<true, 4, 1> : (const void*)conv64_wino2d_kernel<true, 4>) : (const void*)conv64_wino2d_kernel<true, 2>)
                           : (hm == 4 ? (a.mb == 1 ? (const void*)conv64_wino2d_kernel<false, 4, 1> : (const void*)conv64_wino2d_kernel<false, 4>) : (const void*)conv64_wino2d_kernel<false, 2>);
     int lds = pr.lds;
 #ifdef FDN_TEST_HOOKS
-    if (fdn_conv64_wino2d_variant && !fout && hm == 2) {
+    if (fdn_conv64_wino2d_variant && !c.fout && hm == 2) {
         switch (fdn_conv64_wino2d_variant) {
             case 1: fn = (const void*)conv64_wino2d_occ1_kernel<6, 3, 1>; break;
             case 2: fn = (const void*)conv64_wino2d_occ1_kernel<12, 6, 1>; break;
@@ -242,7 +226,7 @@ int fdn_conv64_wino2d_launch(const float* x, const float* upack2, const float* b
 #endif
     if (int rc = fdn_func_max_lds(fn, lds, "conv64_wino2d")) return rc;
     void* kargs[] = {(void*)&a};
-    const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), kargs, lds, s);
+    const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), kargs, lds, c.s);
     if (e != hipSuccess) {
         fdn_set_error("conv64_wino2d_kernel: launch failed: %s", hipGetErrorString(e));
         return FDN_ERR_HIP;

@@ -195,54 +195,63 @@ __device__ __forceinline__ float fdn_act_grad(float y, int act, float alpha) {
     return 1.f;
 }
 
-// Tile planner shared by host code of the MFMA kernels: choose (td,th,tw) with td*th*tw <= max_vox and
-// halo rows <= max_rows minimising the number of workgroup-rounds over `ncu` CUs.
+// Tile of an MFMA kernel's box: td x th x tw voxels, ntd x nth x ntw tiles
 struct FdnTile { int td, th, tw, ntd, nth, ntw; };
-FdnTile fdn_plan_tile(int N, int OD, int OH, int OW, int max_vox, int max_halo_rows, int halo_d);
+
+// One fp32 64->64 3x3x3 convolution, as fdn_conv64_launch_ex and the kernel families' launchers take it (host only).
+//   FDN_CONV64_FWD: y = act(conv(x) + bias + residual) over the (ID, IH, IW) grid (edge clamp == SYMMETRIC p=1);
+//   FDN_CONV64_DGRAD: y = conv_T(x) on the padded (ID+2, IH+2, IW+2) grid (zero outside);
+//   FDN_CONV64_DGRAD_FUSED: the same, with the mirror-pad fold of the interior finished into fout = (sum + fskip) * act'(fy or fmask).
+// The op values are the FDN_ROLE_* of fdn_conv64_pack_streams.
+enum FdnConv64Op { FDN_CONV64_FWD = FDN_ROLE_FWD, FDN_CONV64_DGRAD = FDN_ROLE_DGRAD, FDN_CONV64_DGRAD_FUSED = FDN_ROLE_DGRAD_FUSED };
+struct FdnConv64Call {
+    // x: input rows (dz of a dgrad); wpack: the pack (FDN_CONV64_PACK_FLOATS), each launcher reads its own stream of it; y: output rows
+    // (the padded scratch of a dgrad); fskip, fy, fout: skip, y_prev and dz_prev of the fused fold
+    const float *x = nullptr, *wpack = nullptr, *bias = nullptr, *residual = nullptr, *fskip = nullptr, *fy = nullptr;
+    float *y = nullptr, *fout = nullptr;
+    uint16_t* ymask = nullptr;                 // sign masks (conv64_wino2d_kernel.h): the forward writes ymask, the fused dgrad reads fmask
+    const uint16_t* fmask = nullptr;
+    // further sources of a multi-source fused dgrad (fdn_conv64_dgrad_fused_multi: dz_prev = fold(sum_s conv_T(dz_s, W_s))): rows and the
+    // byte distance of the source's PACK from source 0's (>= 0: the caller orders the sources by pack address; every stream of a pack lies
+    // at the same offset inside it, so one distance serves the 2-D and the 1-D kernel)
+    int nsrc = 1, wd1 = 0, wd2 = 0;
+    const float *x1 = nullptr, *x2 = nullptr;
+    int N = 0, ID = 0, IH = 0, IW = 0, OD = 0, OH = 0, OW = 0;
+    FdnConv64Op op = FDN_CONV64_FWD;
+    int act = FDN_ACT_NONE;
+    float alpha = 0.f;
+    hipStream_t s = nullptr;
+    // the kernels' boundary arguments: output p reads input p + tap - 1 + off; zero_mode: zero outside the input, else edge clamp
+    int off() const { return op == FDN_CONV64_FWD ? 0 : -1; }
+    int zero_mode() const { return op == FDN_CONV64_FWD ? 0 : 1; }
+};
+// the source fields of a kernel argument struct (WinoArgs, Wino2Args)
+template <typename Args> void fdn_conv64_set_sources(Args& a, const FdnConv64Call& c) {
+    a.x1 = c.x1; a.x2 = c.x2; a.wd1 = c.wd1; a.wd2 = c.wd2; a.nsrc = c.nsrc;
+    a.wspan = c.nsrc > 2 ? c.wd2 : (c.nsrc > 1 ? c.wd1 : 0);
+}
 
 // entry points implemented in the per-kernel translation units
-int fdn_conv64_launch(const float* x, const float* wpack, const float* bias, const float* residual, float* y,
-                      int N, int ID, int IH, int IW, int OD, int OH, int OW, int off, int zero_mode, int act,
-                      float alpha, hipStream_t s, int algo = FDN_ALGO_AUTO);
-// Further sources of a multi-source fused dgrad (fdn_conv64_dgrad_fused_multi: dz_prev = fold(sum_s conv_T(dz_s, W_s))): rows and the byte
-// distance of the source's PACK from source 0's (>= 0: the caller orders the sources by pack address; every stream of a pack lies at
-// the same offset inside it, so one distance serves the 2-D and the 1-D kernel)
-struct FdnExtraSrc { int nsrc; const float* x1; const float* x2; int wd1, wd2; };
-int fdn_conv64_launch_ex(const float* x, const float* wpack, const float* bias, const float* residual, float* y,
-                         const float* fskip, const float* fy, float* fout, int N, int ID, int IH, int IW, int OD, int OH,
-                         int OW, int off, int zero_mode, int act, float alpha, hipStream_t s, int parts = 3,
-                         int algo = FDN_ALGO_AUTO, unsigned* probe = nullptr, uint16_t* ymask = nullptr, const uint16_t* fmask = nullptr,
-                         const FdnExtraSrc* extra = nullptr);
-// Winograd F(4,3)-along-W variant of the 64->64 conv (conv64_wino.hip): one output box with all 27 taps
-// output box + its non-zero (kd, kh) tap ranges.  wface = 1: the pair of w faces of a fused dgrad's shell (box = the (d,h) range of the
-// padded grid, ow = 0, ew = 4: one "group" per (d,h) position; see conv64_wino.hip)
+// parts (fused dgrad): FDN_DGRAD_INNER | FDN_DGRAD_SHELL; algo: FDN_ALGO_*
+int fdn_conv64_launch_ex(const FdnConv64Call& c, int parts = 3, int algo = FDN_ALGO_AUTO);
+// Winograd F(4,3)-along-W variant of the 64->64 conv (conv64_wino.hip): output boxes + their non-zero (kd, kh) tap ranges.  wface = 1:
+// the pair of w faces of a fused dgrad's shell (box = the (d,h) range of the padded grid, ow = 0, ew = 4: one "group" per (d,h)
+// position; see conv64_wino.hip)
 struct FdnWino2dPrepared;
 struct FdnWinoBox { int od, oh, ow, ed, eh, ew, ta0, ta1, tb0, tb1, wface; };
 bool fdn_conv64_wino_ok(int ebd, int ebh, int ebw);
-int fdn_conv64_wino_launch_boxes(const float* x, const float* upack, const float* bias, const float* residual, float* y,
-                                 const float* fskip, const float* fy, float* fout, int N, int ID, int IH, int IW, int OD, int OH,
-                                 int OW, const FdnWinoBox* boxes, int nbox, int off, int zero_mode, int act, float alpha,
-                                 hipStream_t s, const struct FdnWino2dPrepared* inner = nullptr, const FdnExtraSrc* extra = nullptr);
-int fdn_conv64_wino_launch(const float* x, const float* upack, const float* bias, const float* residual, float* y,
-                           const float* fskip, const float* fy, float* fout, int N, int ID, int IH, int IW, int OD, int OH,
-                           int OW, int obd, int obh, int obw, int ebd, int ebh, int ebw, int off, int zero_mode, int act,
-                           float alpha, hipStream_t s);
+int fdn_conv64_wino_launch_boxes(const FdnConv64Call& c, const FdnWinoBox* boxes, int nbox, const struct FdnWino2dPrepared* inner = nullptr);
 int fdn_pack_conv64_wino_launch(const float* w, float* uf, float* ud, hipStream_t s);
-// 2-D Winograd variant (conv64_wino2d.hip): F(2,3) along H x F(4,3) along W; one output box with all 27 taps
-// (hm = output rows per cell: 2 = F(2,3) along H, stream at pack + 81*4096; 4 = F(4,3) along H, stream at pack + 153*4096)
+// 2-D Winograd variant (conv64_wino2d.hip): F(hm,3) along H x F(4,3) along W; one output box with all 27 taps
+// (hm = output rows per cell: 2 = F(2,3) along H, stream at pack + 81*4096; 4 = F(4,3) along H, stream at pack + 153*4096, or with
+// bf16x3 -- the products as three bf16 pieces, FDN_ALGO_WINO_BF16X3 -- the stream at pack + 261*4096)
 bool fdn_conv64_wino2d_ok(int ebd, int ebh, int ebw, int ID, int IH, int IW, int hm);
 // A planned, not yet launched 2-D launch (the kernel's argument block, opaque outside conv64_wino2d_kernel.h): fdn_conv64_wino_launch_boxes
 // takes one as `inner` and issues it together with its own regions as ONE launch (conv64_wino2d_shell_kernel: the fused dgrad).
 struct FdnWino2dPrepared { alignas(8) unsigned char args[384]; int blocks; int lds; };
-int fdn_conv64_wino2d_prepare(const float* x, const float* upack2, const float* bias, const float* residual, float* y,
-                              const float* fskip, const float* fy, float* fout, int N, int ID, int IH, int IW, int OD, int OH,
-                              int OW, int obd, int obh, int obw, int ebd, int ebh, int ebw, int off, int zero_mode, int act,
-                              float alpha, int hm, FdnWino2dPrepared* out, uint16_t* ymask = nullptr, const uint16_t* fmask = nullptr,
-                              const FdnExtraSrc* extra = nullptr);
-int fdn_conv64_wino2d_launch(const float* x, const float* upack2, const float* bias, const float* residual, float* y,
-                             const float* fskip, const float* fy, float* fout, int N, int ID, int IH, int IW, int OD, int OH,
-                             int OW, int obd, int obh, int obw, int ebd, int ebh, int ebw, int off, int zero_mode, int act,
-                             float alpha, int hm, hipStream_t s, uint16_t* ymask = nullptr, const uint16_t* fmask = nullptr);
+int fdn_conv64_wino2d_prepare(const FdnConv64Call& c, int hm, bool bf16x3, int obd, int obh, int obw, int ebd, int ebh, int ebw,
+                              FdnWino2dPrepared* out);
+int fdn_conv64_wino2d_launch(const FdnConv64Call& c, int hm, bool bf16x3, int obd, int obh, int obw, int ebd, int ebh, int ebw);
 int fdn_pack_conv64_wino2d_launch(const float* w, float* uf, float* ud, hipStream_t s);
 int fdn_fold_halo_border_launch(const float* s0, const float* s1, const float* s2, int nsrc, const float* skip,
                                 const float* yprev, int act, float alpha, float* out, int N, int D, int H, int W,

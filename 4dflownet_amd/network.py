@@ -66,6 +66,19 @@ def keras_layer_order(low_resblock=8, hi_resblock=4):
     return [2, 0, 3, 1] + list(range(4, n_trunk)) + [h, h + 2, h + 4, h + 1, h + 3, h + 5]
 
 
+def slow_grid_warning(N, D, H, W):
+    """The warning for an fp32 (N, D, H, W) grid whose 64->64 layers FDN_ALGO_AUTO runs off the 2-D Winograd kernels -- all of them on the
+    direct kernels, or on the 1-D Winograd kernels -- or None.  The library's own selection decides (fdn_conv64_pack_streams)."""
+    how = {ops.PACK_STREAM_DIRECT: "the direct kernels (about 3x the time of the 2-D Winograd kernels)",
+           ops.PACK_STREAM_WINO_W: "the 1-D Winograd kernels (about 1.5x the time of the 2-D Winograd kernels)"}.get(
+        ops.conv64_pack_streams(N, D, H, W, ops.ALGO_AUTO, ops.ROLE_FWD))
+    if how is None:
+        return None
+    return ("4dflownet_amd: the 64->64 3x3x3 layers of the %dx%dx%d grid run on %s: FDN_ALGO_AUTO takes the 2-D Winograd kernels "
+            "only where W %% 4 == 0 and H is even (fastest: H %% 4 == 0 as well).  patch_size * res_increase (and patch_size "
+            "itself for the low-res stack) a multiple of 4 avoids this." % (D, H, W, how))
+
+
 class _Layer:
     __slots__ = ("name", "k", "cin", "cout", "w", "b", "gw", "gb", "wp_f", "wp_d", "w_off", "b_off")
 
@@ -302,19 +315,10 @@ class FlowNetModel:
         self._slow_warned.add((D, H, W))
         if not any(a == ops.ALGO_AUTO for a in self.conv_algo.values()):
             return
-        if W % 4:
-            h4, w4 = H & ~3, W & ~3
-            if h4 >= 4 and w4 >= 4 and 2 * h4 * w4 >= H * W and N * D * H * W >= 24576:   # (conv64_mfma.hip, split_box: the aligned box on F(4,3) x F(4,3), the strips direct)
-                return
-            how = "the direct kernels (about 3x the time of the 2-D Winograd kernels)"
-        elif H % 2:
-            how = "the 1-D Winograd kernels (about 1.5x the time of the 2-D Winograd kernels)"
-        else:
-            return
-        import warnings
-        warnings.warn("4dflownet_amd: the 64->64 3x3x3 layers of the %dx%dx%d grid run on %s: FDN_ALGO_AUTO takes the 2-D Winograd kernels "
-                      "only where W %% 4 == 0 and H is even (fastest: H %% 4 == 0 as well).  patch_size * res_increase (and patch_size "
-                      "itself for the low-res stack) a multiple of 4 avoids this." % (D, H, W, how), RuntimeWarning, stacklevel=3)
+        msg = slow_grid_warning(N, D, H, W)
+        if msg:
+            import warnings
+            warnings.warn(msg, RuntimeWarning, stacklevel=3)
 
     def _require_pack_streams(self, N, D, H, W, training):
         """Make sure the pack streams the 64->64 layers read on this grid are current (see __init__)."""

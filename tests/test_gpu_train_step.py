@@ -65,7 +65,7 @@ def test_auto_algo_warns_once_when_a_grid_falls_off_the_winograd_kernels(fdn):
         assert len(hits) == (1 if expect else 0), [str(i.message) for i in w]
         if expect:
             assert "direct kernels" in str(hits[0].message) and "14x6x6" in str(hits[0].message)
-        # the library agrees with the python rule: which pack streams does this grid read?
+        # the warning follows the library: which pack streams does this grid read?
         need = fdn.ops.conv64_pack_streams(*shp, fdn.ops.ALGO_AUTO, fdn.ops.ROLE_FWD)
         assert bool(need & fdn.ops.PACK_STREAM_WINO_H4) == (not expect), (shp, need)
 
