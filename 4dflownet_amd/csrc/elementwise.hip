@@ -489,10 +489,12 @@ __global__ __launch_bounds__(1024) void l2_sumsq_kernel(const float* __restrict_
 
 // sumsq != null: block b also writes sum(w_new^2) over its kernel (non-bias) elements to sumsq[b] (fixed order: the
 // regulariser value of the NEXT step's loss, so fdn_l2_sumsq does not have to stream the parameters again).
+// lr_t_dev != null: the step size is lr_t_dev[0], read on the device (fdn_adam_step_dev: a captured launch must not bake it in).
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, const uint8_t* __restrict__ isk, int64_t n, float lr_t,
-                                                   float b1, float b2, float eps, float l2s_host,
+                                                   float* __restrict__ v, const uint8_t* __restrict__ isk, int64_t n, float lr_t_host,
+                                                   const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float l2s_host,
                                                    const float* __restrict__ l2s_dev, float* __restrict__ sumsq) {
+    const float lr_t = lr_t_dev ? lr_t_dev[0] : lr_t_host;
     const float l2s = l2s_dev ? l2s_host * l2s_dev[0] : l2s_host;
     float ss = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -733,7 +735,20 @@ extern "C" int fdn_adam_step(float* w, const float* g, float* m, float* v, const
     // fixed grid of FDN_ADAM_PARTIALS blocks when partials are requested (blocks beyond the data write 0)
     const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);
     hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       lr_t, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials);
+                       lr_t, (const float*)nullptr, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials);
+    FDN_CHECK_LAUNCH("adam_kernel");
+    return FDN_OK;
+}
+
+extern "C" int fdn_adam_step_dev(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, int64_t n,
+                                 const float* lr_t_dev, float b1, float b2, float eps, float l2_grad_scale,
+                                 const float* l2_scale_dev, float* sumsq_partials, void* stream) {
+    FDN_REQUIRE(w && g && m && v && is_kernel, "fdn_adam_step_dev: NULL operand");
+    FDN_REQUIRE(lr_t_dev, "fdn_adam_step_dev: lr_t_dev is NULL (fdn_adam_step takes the step size by value)");
+    FDN_REQUIRE(n > 0, "fdn_adam_step_dev: n=%lld must be positive", (long long)n);
+    const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);
+    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
+                       0.f, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials);
     FDN_CHECK_LAUNCH("adam_kernel");
     return FDN_OK;
 }

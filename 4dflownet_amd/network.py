@@ -180,6 +180,7 @@ class FlowNetModel:
         self.overlap_wgrad = os.environ.get("FDN_OVERLAP_WGRAD", "1") not in ("", "0")
         self._ws_side = None           # the side stream's own workspace (allocated and re-allocated under that stream: see _workspace)
         self._side_keep = []           # operands of side-stream launches, kept alive until the streams are joined
+        self._side_busy = False        # the side stream has been given work since the last join
         self.set_conv_algo(conv_algo)
         self._cache = None
         # Gradient buckets in the order backward() completes them: slices [lo, hi) of flat_g_ext that are final when the hi-res part
@@ -466,6 +467,7 @@ class FlowNetModel:
             self._side = torch.cuda.Stream(device=self.device)
         main = torch.cuda.current_stream()
         self._side.wait_stream(main)                      # dz is ready
+        self._side_busy = True
         ws = self._workspace(nws, side=True)
         with torch.cuda.stream(self._side):
             self.ops.conv3d_wgrad(x, dz, L.k, L.cin, L.cout, x2=x2, dw=L.gw, dbias=L.gb if bias else None, workspace=ws, lddz=lddz,
@@ -485,6 +487,7 @@ class FlowNetModel:
                 if self._side is None:
                     self._side = torch.cuda.Stream(device=self.device)
                 self._side.wait_stream(torch.cuda.current_stream())
+                self._side_busy = True
             with torch.cuda.stream(self._side) if side else contextlib.nullcontext():
                 if len(items) == 1:
                     x, dz, L, bias = items[0]
@@ -503,8 +506,9 @@ class FlowNetModel:
         (Holding references until the join instead of Tensor.record_stream: with record_stream the caching allocator could not reuse a
         block until the side stream had passed its free point, took fresh device memory for the main stream meanwhile and never came
         back -- 0.8 GB per step, 96 GB reserved after 120 cfg2 steps, and one 2.9-s step when it finally had to give the cache back.)"""
-        if self._side is not None:
-            torch.cuda.current_stream().wait_stream(self._side)
+        if self._side is not None and self._side_busy:    # (an idle side stream is not waited for: under stream capture it has not
+            torch.cuda.current_stream().wait_stream(self._side)          # joined the capture, and a wait for it would end the capture)
+            self._side_busy = False
         self._side_keep.clear()
 
     def _pad_like(self, t):
@@ -537,6 +541,7 @@ class FlowNetModel:
                     # all-reduce in it) is issued from the side stream after that stream has been made to wait for the main one, so the
                     # collective is ordered behind both and the dgrad chain on the main stream does not stop for it
                     self._side.wait_stream(torch.cuda.current_stream())
+                    self._side_busy = True
                     with torch.cuda.stream(self._side):
                         grad_ready(*self.grad_buckets[k])
                 else:

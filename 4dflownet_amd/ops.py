@@ -348,10 +348,20 @@ def l2_sumsq(w_flat, is_kernel, out=None):
 ADAM_PARTIALS = 2048                  # FDN_ADAM_PARTIALS
 
 
-def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_dev=None, sumsq_partials=None):
-    """sumsq_partials (ADAM_PARTIALS floats): also receive per-block sums of the updated kernel parameters' squares."""
+def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_dev=None, sumsq_partials=None, lr_t_dev=None):
+    """sumsq_partials (ADAM_PARTIALS floats): also receive per-block sums of the updated kernel parameters' squares.
+    lr_t_dev (one fp32 device element): the step size is read from it on the device and `lr_t` is ignored (fdn_adam_step_dev) -- the
+    form a captured launch needs, since a by-value lr_t would be frozen into the graph."""
     if sumsq_partials is not None and sumsq_partials.numel() < ADAM_PARTIALS:
         raise FdnError("adam_step: sumsq_partials needs %d floats" % ADAM_PARTIALS)
+    if lr_t_dev is not None:
+        if not lr_t_dev.is_cuda or lr_t_dev.dtype != torch.float32 or lr_t_dev.numel() < 1:
+            raise FdnError("adam_step: lr_t_dev must hold one float32 on the GPU")
+        check(_lib.load().fdn_adam_step_dev(_p(w), _p(g), _p(m), _p(v), _p(is_kernel), w.numel(), _p(lr_t_dev), float(b1), float(b2),
+                                            float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
+                                            _p(sumsq_partials, allow_none=True), _stream()),
+              "fdn_adam_step_dev")
+        return
     check(_lib.load().fdn_adam_step(_p(w), _p(g), _p(m), _p(v), _p(is_kernel), w.numel(), float(lr_t), float(b1), float(b2),
                                     float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
                                     _p(sumsq_partials, allow_none=True), _stream()),

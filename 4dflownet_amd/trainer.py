@@ -33,7 +33,11 @@ class Mean:
         self.reset_states()
 
     def reset_states(self):
-        self._total = torch.zeros((), device=self.device, dtype=torch.float64)
+        # zeroed in place: the tensor result() reads stays the same object over epochs (a step recorded into a HIP graph accumulates into it)
+        if getattr(self, "_total", None) is None:
+            self._total = torch.zeros((), device=self.device, dtype=torch.float64)
+        else:
+            self._total.zero_()
         self._count = 0
 
     def update_state(self, values):

@@ -276,6 +276,12 @@ int fdn_adam_step(float* w, const float* g, float* m, float* v, const uint8_t* i
  * 5e-7 * that sum is the regulariser value of the next step's loss, so fdn_l2_sumsq need not stream the
  * parameters again.  src/Network/TrainerController.py:129-141. */
 #define FDN_ADAM_PARTIALS 2048
+/* fdn_adam_step with the step size read on the device: lr_t_dev[0] (one float, must not be NULL) instead of the by-value lr_t.
+ * For a launch that is captured into a HIP graph and replayed: the caller rewrites that float before every replay.  Same
+ * kernel, same arithmetic: with lr_t_dev[0] == (float)lr_t the update is bit-identical to fdn_adam_step. */
+int fdn_adam_step_dev(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, int64_t n,
+                      const float* lr_t_dev, float b1, float b2, float eps, float l2_grad_scale,
+                      const float* l2_scale_dev, float* sumsq_partials, void* stream);
 int fdn_sum_partials(const float* partials, int n, float* out, void* stream);
 /* The same FDN_ADAM_PARTIALS per-block sums for parameters no fdn_adam_step has touched yet (first step, after loading a
  * checkpoint): the multi-block form of fdn_l2_sumsq, which needs no scratch and runs as ONE block.  Follow with fdn_sum_partials. */
