@@ -8,16 +8,54 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // src/Network/SR4DFlowNet.py:10-15
 // ---------------------------------------------------------------------------------------------
+// sqrt(a*a + b*b + c*c) with its roundings spelled out -- one product rounded, the other two fused, the way this kernel has always been
+// compiled.  Left to the compiler the choice of which products are fused follows the surrounding code (it changed when the loads
+// moved into two branches), and results must not depend on that.
+__device__ __forceinline__ float norm3(float a, float b, float c) {
+    return sqrtf(__builtin_fmaf(c, c, __builtin_fmaf(a, a, b * b)));
+}
+
+// Sliding-window geometry of fdn_input_features_volume (src/Network/PatchGenerator.py:13-40,53-86): with P > 0 the six inputs of output
+// voxel i are gathered from resident frames (F,6,X,Y,Z) at u -- patch g0 + i / P^3 of the window at stride P - 4, shifted by the 2-voxel
+// side pad, zero outside the volume -- instead of being read at u[i] .. mw[i].  P == 0: no geometry (fdn_input_features).
+struct InputGeom {
+    int32_t P, X, Y, Z;
+    int32_t nx, ny, nz, pad_;
+    int64_t g0;
+};
+
 template <typename T>
 __global__ void input_features_kernel(const float* __restrict__ u, const float* __restrict__ v, const float* __restrict__ w,
                                       const float* __restrict__ mu, const float* __restrict__ mv,
                                       const float* __restrict__ mw, T* __restrict__ phase, T* __restrict__ pc,
-                                      int64_t nvox) {
+                                      int64_t nvox, InputGeom geo) {
+    const int P = geo.P, E = P - 4;
+    const int64_t per = (int64_t)P * P * P, plane = (int64_t)geo.X * geo.Y * geo.Z;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvox; i += (int64_t)gridDim.x * blockDim.x) {
-        const float a = u[i], b = v[i], c = w[i];
-        const float speed = sqrtf(a * a + b * b + c * c);
-        const float ma = mu[i], mb = mv[i], mc = mw[i];
-        const float mag = sqrtf(ma * ma + mb * mb + mc * mc);
+        float a, b, c, ma, mb, mc;
+        if (P == 0) {
+            a = u[i]; b = v[i]; c = w[i];
+            ma = mu[i]; mb = mv[i]; mc = mw[i];
+        } else {
+            const int64_t n = i / per;                       // patch of this launch
+            int r = (int)(i - n * per);                      // voxel of the patch, z fastest
+            const int pa = r / (P * P); r -= pa * P * P;
+            const int pb = r / P, pcz = r - pb * P;
+            int64_t g = geo.g0 + n;                          // global patch: frame, then (i, j, k) with k fastest
+            const int pk = (int)(g % geo.nz); g /= geo.nz;
+            const int pj = (int)(g % geo.ny); g /= geo.ny;
+            const int pi = (int)(g % geo.nx);
+            const int64_t f = g / geo.nx;
+            const int x = pi * E + pa - 2, y = pj * E + pb - 2, z = pk * E + pcz - 2;
+            a = b = c = ma = mb = mc = 0.f;
+            if (x >= 0 && x < geo.X && y >= 0 && y < geo.Y && z >= 0 && z < geo.Z) {
+                const float* s = u + f * 6 * plane + ((int64_t)x * geo.Y + y) * geo.Z + z;
+                a = s[0]; b = s[plane]; c = s[2 * plane];
+                ma = s[3 * plane]; mb = s[4 * plane]; mc = s[5 * plane];
+            }
+        }
+        const float speed = norm3(a, b, c);
+        const float mag = norm3(ma, mb, mc);
         fdn_st1(phase + i * 3 + 0, a); fdn_st1(phase + i * 3 + 1, b); fdn_st1(phase + i * 3 + 2, c);
         fdn_st1(pc + i * 3 + 0, mag * speed); fdn_st1(pc + i * 3 + 1, mag); fdn_st1(pc + i * 3 + 2, speed);
     }
@@ -567,7 +605,27 @@ static int input_features_t(const float* u, const float* v, const float* w, cons
                             T* phase, T* pc, int64_t nvox, void* stream) {
     FDN_REQUIRE(u && v && w && mu && mv && mw && phase && pc && nvox > 0, "fdn_input_features: NULL argument or nvox<=0");
     hipLaunchKernelGGL(input_features_kernel<T>, dim3(grid_for(nvox)), dim3(256), 0, (hipStream_t)stream, u, v, w, mu, mv, mw,
-                       phase, pc, nvox);
+                       phase, pc, nvox, InputGeom{});
+    FDN_CHECK_LAUNCH("input_features_kernel");
+    return FDN_OK;
+}
+template <typename T>
+static int input_features_volume_t(const char* who, const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz,
+                                   int64_t g0, int count, T* phase, T* pc, void* stream) {
+    FDN_REQUIRE(frames && phase && pc, "%s: NULL argument", who);
+    FDN_REQUIRE(F > 0 && X > 0 && Y > 0 && Z > 0, "%s: bad frames (F=%d, X=%d, Y=%d, Z=%d)", who, F, X, Y, Z);
+    FDN_REQUIRE(P > 4 && P <= 1024, "%s: patch size P=%d must be in 5..1024 (the window advances by P - 4)", who, P);
+    FDN_REQUIRE(nx > 0 && ny > 0 && nz > 0, "%s: bad patch counts (%d,%d,%d)", who, nx, ny, nz);
+    FDN_REQUIRE(count > 0, "%s: count=%d", who, count);
+    FDN_REQUIRE(g0 >= 0, "%s: g0=%lld", who, (long long)g0);
+    FDN_REQUIRE(g0 + count <= (int64_t)F * nx * ny * nz, "%s: patches [%lld, %lld) exceed F*nx*ny*nz = %lld", who, (long long)g0,
+                (long long)(g0 + count), (long long)((int64_t)F * nx * ny * nz));
+    const int64_t nvox = (int64_t)count * P * P * P;
+    InputGeom geo{};
+    geo.P = P; geo.X = X; geo.Y = Y; geo.Z = Z; geo.nx = nx; geo.ny = ny; geo.nz = nz; geo.g0 = g0;
+    hipLaunchKernelGGL(input_features_kernel<T>, dim3(grid_for(nvox)), dim3(256), 0, (hipStream_t)stream, frames,
+                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                       (const float*)nullptr, phase, pc, nvox, geo);      // the frames travel as `u`; v .. mw are not read
     FDN_CHECK_LAUNCH("input_features_kernel");
     return FDN_OK;
 }
@@ -578,6 +636,15 @@ extern "C" int fdn_input_features(const float* u, const float* v, const float* w
 extern "C" int fdn_input_features_bf16(const float* u, const float* v, const float* w, const float* mu, const float* mv,
                                        const float* mw, uint16_t* phase, uint16_t* pc, int64_t nvox, void* stream) {
     return input_features_t<uint16_t>(u, v, w, mu, mv, mw, phase, pc, nvox, stream);
+}
+extern "C" int fdn_input_features_volume(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
+                                         int count, float* phase, float* pc, void* stream) {
+    return input_features_volume_t<float>("fdn_input_features_volume", frames, F, X, Y, Z, P, nx, ny, nz, g0, count, phase, pc, stream);
+}
+extern "C" int fdn_input_features_volume_bf16(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz,
+                                              int64_t g0, int count, uint16_t* phase, uint16_t* pc, void* stream) {
+    return input_features_volume_t<uint16_t>("fdn_input_features_volume_bf16", frames, F, X, Y, Z, P, nx, ny, nz, g0, count, phase, pc,
+                                             stream);
 }
 
 extern "C" int fdn_fold_halo(const float* dxpad0, const float* dxpad1, const float* dxpad2, int nsrc, const float* skip,

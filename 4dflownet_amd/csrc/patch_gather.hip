@@ -16,8 +16,42 @@ struct PatchDesc {          // one per (sample, output tensor); mirrored by data
     float sign, div;        // div = venc or 4095; thr is passed in `div` for mode 1
 };
 
+// mode 1 of the kernel, fdn_stitch_patches (src/Network/PatchGenerator.py:116-154, src/predictor.py:67-115): the inverse direction for
+// inference.  B predicted patches (B,S,S,S,3) at `pred`, global patches g0 .. g0 + B of F frames of nx*ny*nz patches each (k fastest);
+// the core of every patch (S - 2*side per axis) goes to out = (F,3,Xo,Yo,Zo) at patch coordinate * core, voxels beyond the extents (the
+// cropped far pad) are dropped.  One element (voxel, component) per thread and step: reads are contiguous, writes of different patches
+// disjoint.
+struct StitchGeom {
+    const float* pred;
+    int64_t g0;
+    int32_t Xo, Yo, Zo, side;
+    int32_t nx, ny, nz, pad_;
+};
+
 __global__ __launch_bounds__(256) void gather_patches_kernel(const PatchDesc* __restrict__ desc, float* __restrict__ out, int B,
-                                                              int S) {
+                                                              int S, int mode, StitchGeom sg) {
+    if (mode == 1) {
+        const int cs = S - 2 * sg.side;                                  // core edge
+        const int64_t per = (int64_t)cs * cs * cs * 3;
+        const int64_t total = per * B;
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t n = i / per;
+            int r = (int)(i - n * per);
+            const int a = r / (cs * cs * 3); r -= a * cs * cs * 3;
+            const int b = r / (cs * 3); r -= b * cs * 3;
+            const int c = r / 3, comp = r - c * 3;
+            int64_t g = sg.g0 + n;
+            const int pk = (int)(g % sg.nz); g /= sg.nz;
+            const int pj = (int)(g % sg.ny); g /= sg.ny;
+            const int pi = (int)(g % sg.nx);
+            const int64_t f = g / sg.nx;
+            const int64_t x = (int64_t)pi * cs + a, y = (int64_t)pj * cs + b, z = (int64_t)pk * cs + c;
+            if (x >= sg.Xo || y >= sg.Yo || z >= sg.Zo) continue;
+            const float v = sg.pred[(((n * S + sg.side + a) * S + sg.side + b) * S + sg.side + c) * 3 + comp];
+            out[(((f * 3 + comp) * sg.Xo + x) * sg.Yo + y) * sg.Zo + z] = v;
+        }
+        return;
+    }
     const int64_t per = (int64_t)S * S * S;
     const int64_t total = per * B;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -47,7 +81,31 @@ extern "C" int fdn_gather_patches(const void* desc, float* out, int B, int S, vo
     int64_t nb = (total + 255) / 256;
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(gather_patches_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const PatchDesc*)desc,
-                       out, B, S);
+                       out, B, S, 0, StitchGeom{});
+    FDN_CHECK_LAUNCH("gather_patches_kernel");
+    return FDN_OK;
+}
+
+extern "C" int fdn_stitch_patches(const float* pred, float* vol, int F, int Xo, int Yo, int Zo, int S, int side, int nx, int ny, int nz,
+                                  int64_t g0, int count, void* stream) {
+    FDN_REQUIRE(pred && vol, "fdn_stitch_patches: NULL argument");
+    FDN_REQUIRE(side >= 0 && S > 2 * side && S <= 512, "fdn_stitch_patches: S=%d must exceed 2*side (side=%d) and not 512", S, side);
+    FDN_REQUIRE(F > 0 && nx > 0 && ny > 0 && nz > 0, "fdn_stitch_patches: bad frame / patch counts (F=%d, %d,%d,%d)", F, nx, ny, nz);
+    FDN_REQUIRE(count > 0, "fdn_stitch_patches: count=%d", count);
+    FDN_REQUIRE(g0 >= 0, "fdn_stitch_patches: g0=%lld", (long long)g0);
+    FDN_REQUIRE(g0 + count <= (int64_t)F * nx * ny * nz, "fdn_stitch_patches: patches [%lld, %lld) exceed F*nx*ny*nz = %lld",
+                (long long)g0, (long long)(g0 + count), (long long)((int64_t)F * nx * ny * nz));
+    const int64_t cs = S - 2 * side;
+    FDN_REQUIRE(Xo > 0 && Yo > 0 && Zo > 0 && Xo <= nx * cs && Yo <= ny * cs && Zo <= nz * cs,
+                "fdn_stitch_patches: output extents (%d,%d,%d) must be in 1..n*(S-2*side) = (%lld,%lld,%lld)", Xo, Yo, Zo,
+                (long long)(nx * cs), (long long)(ny * cs), (long long)(nz * cs));
+    const int64_t total = (int64_t)count * cs * cs * cs * 3;
+    int64_t nb = (total + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    StitchGeom sg{};
+    sg.pred = pred; sg.g0 = g0; sg.Xo = Xo; sg.Yo = Yo; sg.Zo = Zo; sg.side = side; sg.nx = nx; sg.ny = ny; sg.nz = nz;
+    hipLaunchKernelGGL(gather_patches_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const PatchDesc*)nullptr, vol,
+                       count, S, 1, sg);
     FDN_CHECK_LAUNCH("gather_patches_kernel");
     return FDN_OK;
 }

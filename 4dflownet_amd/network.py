@@ -319,7 +319,7 @@ class FlowNetModel:
         msg = slow_grid_warning(N, D, H, W)
         if msg:
             import warnings
-            warnings.warn(msg, RuntimeWarning, stacklevel=3)
+            warnings.warn(msg, RuntimeWarning, stacklevel=4)
 
     def _require_pack_streams(self, N, D, H, W, training):
         """Make sure the pack streams the 64->64 layers read on this grid are current (see __init__)."""
@@ -373,17 +373,38 @@ class FlowNetModel:
             B, D, H, W = u.shape[:4]
         else:
             B, D, H, W = u.shape
+        self._prepare_grid(B, D, H, W, training)
+        phase = torch.empty((B, D, H, W, 3), device=self.device, dtype=self.act_dtype)
+        pc = torch.empty((B, D, H, W, 3), device=self.device, dtype=self.act_dtype)
+        self.ops.input_features(u, v, w, mu, mv, mw, phase, pc)
+        return self._forward_body(phase, pc, training)
+
+    def _prepare_grid(self, B, D, H, W, training):
+        """Slow-grid warnings and pack streams of the LR grid and of the upsampled one."""
         R = self.res_increase
-        Ls = self.layers
         self._warn_slow_grid(B, D, H, W)
         self._require_pack_streams(B, D, H, W, training)
         if R > 1:                                          # (the three head convs run on the upsampled grid whatever hi_resblock is)
             if self.hi_resblock > 0:
                 self._warn_slow_grid(B, D * R, H * R, W * R)
             self._require_pack_streams(B, D * R, H * R, W * R, training)
-        phase = torch.empty((B, D, H, W, 3), device=self.device, dtype=self.act_dtype)
-        pc = torch.empty((B, D, H, W, 3), device=self.device, dtype=self.act_dtype)
-        self.ops.input_features(u, v, w, mu, mv, mw, phase, pc)
+
+    def forward_features(self, phase, pc, training=False):
+        """forward() entered behind input_features: phase, pc (B,P,P,P,3) device tensors of the activation dtype, e.g. from
+        ops.input_features_volume (the sliding window of predictor.predict_volume).  Same result as forward() on the inputs they
+        were computed from."""
+        want = (self.device, self.act_dtype)
+        for n, t in (("phase", phase), ("pc", pc)):
+            if t.dim() != 5 or t.shape[4] != 3 or (t.device, t.dtype) != want or not t.is_contiguous():
+                raise FdnError("forward_features: %s must be a contiguous (B,D,H,W,3) %s tensor on %s" % (n, want[1], want[0]))
+        if phase.shape != pc.shape:
+            raise FdnError("forward_features: phase %s and pc %s differ" % (tuple(phase.shape), tuple(pc.shape)))
+        self._prepare_grid(*phase.shape[:4], training)
+        return self._forward_body(phase, pc, training)
+
+    def _forward_body(self, phase, pc, training):
+        R = self.res_increase
+        Ls = self.layers
         a0 = self._conv(pc, Ls[0], ACT_RELU)
         a1 = self._conv(a0, Ls[1], ACT_RELU)
         p0 = self._conv(phase, Ls[2], ACT_RELU)

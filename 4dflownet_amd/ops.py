@@ -49,6 +49,47 @@ def input_features(u, v, w, mu, mv, mw, phase=None, pc=None):
     return phase, pc
 
 
+def _volume_geometry(frames, patch_size, counts, g0, count, who):
+    if frames.dim() != 5 or frames.shape[1] != 6:
+        raise FdnError("%s: frames must be (F,6,X,Y,Z), got %s" % (who, tuple(frames.shape)))
+    F, _, X, Y, Z = frames.shape
+    nx, ny, nz = (int(n) for n in counts)
+    count = F * nx * ny * nz - int(g0) if count is None else int(count)
+    return (F, X, Y, Z, int(patch_size), nx, ny, nz, int(g0), count)
+
+
+def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None):
+    """input_features of patches [g0, g0 + count) of the sliding window over resident frames (F,6,X,Y,Z) (u,v,w,mag_u,mag_v,mag_w,
+    normalised): the patches are never materialised.  counts = (nx,ny,nz) of tiler.PatchGenerator.plan; patch g = frame g // (nx*ny*nz),
+    then (i,j,k) with k fastest.  Returns (phase, pc), each (count,P,P,P,3)."""
+    geo = _volume_geometry(frames, patch_size, counts, g0, count, "input_features_volume")
+    P, count = geo[4], geo[9]
+    if phase is None:
+        phase = torch.empty((max(count, 0), P, P, P, 3), device=frames.device, dtype=torch.float32)
+    if pc is None:
+        pc = torch.empty((max(count, 0), P, P, P, 3), device=frames.device, dtype=torch.float32)
+    if min(phase.numel(), pc.numel()) < max(count, 0) * P ** 3 * 3:
+        raise FdnError("input_features_volume: phase / pc hold fewer than (%d,%d,%d,%d,3) elements" % (count, P, P, P))
+    check(_lib.load().fdn_input_features_volume(_p(frames, "frames"), *geo, _p(phase, "phase"), _p(pc, "pc"), _stream()),
+          "fdn_input_features_volume")
+    return phase, pc
+
+
+def stitch_patches(pred, vol, side, counts, g0=0):
+    """Cores of the predicted patches [g0, g0 + len(pred)) into the stitched volumes: pred (count,S,S,S,3), vol (F,3,Xo,Yo,Zo), side =
+    2 * res_increase HR voxels stripped per patch side; core voxels that fall into the cropped far pad are dropped (tiler.PatchGenerator.
+    _patchup_with_overlap per frame and component).  Writes of different patches are disjoint: any batching gives the same volume."""
+    if pred.dim() != 5 or pred.shape[4] != 3 or not (pred.shape[1] == pred.shape[2] == pred.shape[3]):
+        raise FdnError("stitch_patches: pred must be (count,S,S,S,3), got %s" % (tuple(pred.shape),))
+    if vol.dim() != 5 or vol.shape[1] != 3:
+        raise FdnError("stitch_patches: vol must be (F,3,Xo,Yo,Zo), got %s" % (tuple(vol.shape),))
+    F, _, Xo, Yo, Zo = vol.shape
+    nx, ny, nz = (int(n) for n in counts)
+    check(_lib.load().fdn_stitch_patches(_p(pred, "pred"), _p(vol, "vol"), F, Xo, Yo, Zo, pred.shape[1], int(side), nx, ny, nz,
+                                         int(g0), pred.shape[0], _stream()), "fdn_stitch_patches")
+    return vol
+
+
 def pack_conv64_weights(w, wp_fwd=None, wp_dgrad=None, want_dgrad=True):
     if tuple(w.shape) != (3, 3, 3, 64, 64):
         raise FdnError("pack_conv64_weights: expected (3,3,3,64,64), got %s" % (tuple(w.shape),))

@@ -7,7 +7,8 @@ import torch
 
 from . import _lib
 from ._lib import FdnError, check
-from .ops import (ACT_NONE, ACT_RELU, ACT_LEAKY, LEAKY_ALPHA, _stream, loss_metrics, l2_sumsq, adam_step)  # noqa: F401
+from .ops import (ACT_NONE, ACT_RELU, ACT_LEAKY, LEAKY_ALPHA, _stream, _volume_geometry, loss_metrics, l2_sumsq, adam_step,  # noqa: F401
+                  stitch_patches)
 
 BF16 = torch.bfloat16
 ACT_DTYPE = BF16
@@ -43,6 +44,21 @@ def input_features(u, v, w, mu, mv, mw, phase=None, pc=None):
         pc = torch.empty(tuple(shp) + (3,), device=u.device, dtype=BF16)
     check(_lib.load().fdn_input_features_bf16(_pf(u), _pf(v), _pf(w), _pf(mu), _pf(mv), _pf(mw), _pb(phase), _pb(pc),
                                               u.numel(), _stream()), "fdn_input_features_bf16")
+    return phase, pc
+
+
+def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None):
+    """ops.input_features_volume with bf16 phase / pc (the frames stay fp32)."""
+    geo = _volume_geometry(frames, patch_size, counts, g0, count, "input_features_volume")
+    P, count = geo[4], geo[9]
+    if phase is None:
+        phase = torch.empty((max(count, 0), P, P, P, 3), device=frames.device, dtype=BF16)
+    if pc is None:
+        pc = torch.empty((max(count, 0), P, P, P, 3), device=frames.device, dtype=BF16)
+    if min(phase.numel(), pc.numel()) < max(count, 0) * P ** 3 * 3:
+        raise FdnError("input_features_volume: phase / pc hold fewer than (%d,%d,%d,%d,3) elements" % (count, P, P, P))
+    check(_lib.load().fdn_input_features_volume_bf16(_pf(frames, "frames"), *geo, _pb(phase, "phase"), _pb(pc, "pc"), _stream()),
+          "fdn_input_features_volume_bf16")
     return phase, pc
 
 

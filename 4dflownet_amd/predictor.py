@@ -153,10 +153,132 @@ def predict_patches(network, velocities, magnitudes, batch_size):
     return None
 
 
+def predict_volume(network, frames, patch_size, batch_size, out=None):
+    """Sliding-window inference with the tiler on the device (predictor.py:67-115 without its host work).  frames: (F,6,X,Y,Z)
+    normalised fp32 (u,v,w,mag_u,mag_v,mag_w as ImageDataset.load_vectorfield leaves them), numpy or a device tensor; they are
+    uploaded once.  Runs batches of `batch_size` consecutive global patches -- a batch may span two frames, so only the last one is
+    ragged --: features straight from the frames (ops.input_features_volume), network.forward_features, the cores into the output
+    (ops.stitch_patches).  Returns the stitched NORMALISED predictions, a (F,3,X*R,Y*R,Z*R) fp32 device tensor (`out` if given);
+    de-normalisation and the zeroing of sub-pixel velocities stay with the caller.  Everything is queued on the current stream."""
+    frames = network._to_dev(frames)
+    if frames.dim() != 5 or frames.shape[1] != 6:
+        raise ValueError("predict_volume: frames must be (F,6,X,Y,Z), got %s" % (tuple(frames.shape),))
+    R = network.res_increase
+    F = frames.shape[0]
+    counts, _, extents = PatchGenerator(patch_size, R).plan(tuple(frames.shape[2:]))
+    if out is None:
+        out = torch.empty((F, 3) + extents, device=frames.device, dtype=torch.float32)    # every voxel belongs to one patch core
+    elif tuple(out.shape) != (F, 3) + extents:
+        raise ValueError("predict_volume: out must be %s, got %s" % ((F, 3) + extents, tuple(out.shape)))
+    total = F * counts[0] * counts[1] * counts[2]
+    for g0 in range(0, total, batch_size):
+        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, min(batch_size, total - g0))
+        network.ops.stitch_patches(network.forward_features(phase, pc), out, 2 * R, counts, g0)
+    return out
+
+
+DEVICE_TILER_GROUP_BYTES = 1 << 30        # frames + stitched output of one group of rows (predict_file(device_tiler=True))
+
+
+def _volume_stage(network, shape):
+    """Two pinned fp32 buffers for stitched groups + a copy stream, kept on the network between calls (the pattern of _stage)."""
+    st = getattr(network, "_predict_vol_stage", None)
+    if st is None or st[0] != tuple(shape):
+        stream = st[2] if st is not None else torch.cuda.Stream(device=network.device)
+        st = (tuple(shape), [torch.empty(tuple(shape), dtype=torch.float32).pin_memory() for _ in range(2)], stream)
+        network._predict_vol_stage = st
+    return st[1], st[2]
+
+
+def _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size, round_small_values, verbose,
+                         frames_per_group):
+    """predict_file with the tiler on the device: rows in groups whose frames and stitched output fit DEVICE_TILER_GROUP_BYTES (or
+    frames_per_group rows), one predict_volume per group; the stitched group travels to pinned host memory on the copy stream while
+    the next group computes, and is then de-normalised, zeroed and appended exactly as on the host path."""
+    dataset = ImageDataset()
+    nr_rows = dataset.get_dataset_len(input_filepath)
+    written = []
+    if nr_rows == 0:
+        return written
+    dataset.load_vectorfield(input_filepath, 0)
+    lr_shape = dataset.u.shape
+    R = res_increase
+    if frames_per_group is None:
+        per_frame = 4 * int(np.prod(lr_shape)) * (6 + 3 * R ** 3)
+        frames_per_group = max(1, DEVICE_TILER_GROUP_BYTES // per_frame)
+    fpg = max(1, min(int(frames_per_group), nr_rows))
+    out_shape = (fpg, 3) + tuple(n * R for n in lr_shape)
+    stage, copy_stream = _volume_stage(network, out_shape)
+    main = torch.cuda.current_stream(network.device)
+    counts, _, _ = PatchGenerator(patch_size, R).plan(lr_shape)
+    per_frame_patches = counts[0] * counts[1] * counts[2]
+
+    def finish(job):
+        ev, slot, rows, meta, t0, _keep = job
+        ev.synchronize()
+        host = stage[slot].numpy()
+        if verbose:
+            print("Processed rows %d-%d/%d: %d patches in %.2f secs." % (rows[0] + 1, rows[-1] + 1, nr_rows, len(rows) * per_frame_patches,
+                                                                       time.time() - t0))
+        for f, (venc, vpp, dx) in enumerate(meta):
+            vols, cols = [], []
+            for i in range(3):
+                v = host[f, i].astype(np.float64) * venc               # de-normalise (:103)
+                if round_small_values:
+                    v[np.abs(v) < vpp] = 0                             # (:104-107)
+                v = np.expand_dims(v, axis=0)
+                vols.append(v)
+                cols.append((dataset.velocity_colnames[i], v))
+            if dx is not None:
+                cols.append((dataset.dx_colname, np.expand_dims(dx / res_increase, axis=0)))
+            h5io.append_datasets(output_filepath, cols, compression='gzip')
+            written.append(tuple(vols))
+
+    pending = None
+    for k, r0 in enumerate(range(0, nr_rows, fpg)):
+        rows = list(range(r0, min(r0 + fpg, nr_rows)))
+        frames = np.empty((len(rows), 6) + tuple(lr_shape), dtype=np.float32)
+        meta = []
+        for f, nrow in enumerate(rows):
+            dataset.load_vectorfield(input_filepath, nrow)
+            for c, a in enumerate((dataset.u, dataset.v, dataset.w, dataset.mag_u, dataset.mag_v, dataset.mag_w)):
+                frames[f, c] = a
+            meta.append((dataset.venc, dataset.velocity_per_px, dataset.dx))
+        t0 = time.time()
+        vol = predict_volume(network, frames, patch_size, batch_size)
+        slot = k & 1                                                   # its previous user (group k - 2) was finished one turn ago
+        copy_stream.wait_stream(main)
+        with torch.cuda.stream(copy_stream):
+            stage[slot][:len(rows)].copy_(vol, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(copy_stream)
+        vol.record_stream(copy_stream)
+        if pending is not None:
+            finish(pending)                                            # host work of group k - 1 behind the compute of group k
+        pending = (ev, slot, rows, meta, t0, vol)
+    finish(pending)
+    return written
+
+
+_warned_device_tiler_world = False
+
+
 def predict_file(network, input_filepath, output_filepath, patch_size, res_increase, batch_size=8,
-                 round_small_values=True, verbose=True):
+                 round_small_values=True, verbose=True, device_tiler=False, frames_per_group=None):
     """predictor.py:67-115 for every row of the input file.  Returns the list of (u,v,w) volumes written (rank 0; the other ranks
-    of a data-parallel run compute their shard of every row's patches and return an empty list)."""
+    of a data-parallel run compute their shard of every row's patches and return an empty list).
+    device_tiler=True (or FDN_DEVICE_TILER=1): patchify and stitch run on the device (predict_volume) over groups of rows --
+    frames_per_group rows, default what fits DEVICE_TILER_GROUP_BYTES; same file, same returned volumes (dtype and shape).  Single
+    process only: a data-parallel run keeps the host tiler and says so once."""
+    global _warned_device_tiler_world
+    if device_tiler or os.environ.get("FDN_DEVICE_TILER", "0") not in ("", "0"):
+        if parallel.world_size() == 1:
+            return _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size,
+                                        round_small_values, verbose, frames_per_group)
+        if not _warned_device_tiler_world:
+            _warned_device_tiler_world = True
+            import warnings
+            warnings.warn("predict_file: the device tiler runs in a single process only; this data-parallel run keeps the host tiler")
     pgen = PatchGenerator(patch_size, res_increase)
     dataset = ImageDataset()
     nr_rows = dataset.get_dataset_len(input_filepath)
@@ -189,15 +311,15 @@ def predict_file(network, input_filepath, output_filepath, patch_size, res_incre
 
 def main(data_dir='../data', filename='example_data.h5', output_dir="../result", output_filename='example_result.h5',
          model_path="../models/4DFlowNet/4DFlowNet.h5", patch_size=24, res_increase=2, batch_size=8,
-         round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32"):
-    """Same hard-coded surface as predictor.py:31-47 (+ dtype)."""
+         round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32", device_tiler=False, frames_per_group=None):
+    """Same hard-coded surface as predictor.py:31-47 (+ dtype, + the device tiler switch of predict_file)."""
     parallel.init_from_env()
     network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype)
     network.load_weights(model_path)
     if not os.path.isdir(output_dir) and parallel.rank() == 0:
         os.makedirs(output_dir)
     predict_file(network, '{}/{}'.format(data_dir, filename), '{}/{}'.format(output_dir, output_filename), patch_size,
-                 res_increase, batch_size, round_small_values)
+                 res_increase, batch_size, round_small_values, device_tiler=device_tiler, frames_per_group=frames_per_group)
     if parallel.rank() == 0:
         print("Done!")
 

@@ -23,6 +23,15 @@ class PatchGenerator:
             return self.patch_size - res
         return 2 * side_pad - res
 
+    def plan(self, shape):
+        """Geometry of an LR volume of `shape` without touching its data: ((nr_x, nr_y, nr_z), HR crop padding, stitched output
+        extents) -- what patchify leaves in nr_* / padding, and the shape _patchup_with_overlap returns."""
+        side_pad = (self.patch_size - self.effective_patch_size) // 2
+        padded = [int(n) + 2 * side_pad for n in shape]
+        far = [self._far_pad(n) for n in padded]
+        nr = tuple((n + f - 2 * side_pad) // self.effective_patch_size for n, f in zip(padded, far))
+        return nr, tuple(f * self.res_increase for f in far), tuple(int(n) * self.res_increase for n in shape)
+
     def _pad_to_patch_size_with_overlap(self, img):
         side_pad = (self.patch_size - self.effective_patch_size) // 2
         img = np.pad(img, ((side_pad, side_pad),) * 3, 'constant')

@@ -259,6 +259,27 @@ int fdn_loss_metrics_div(const float* pred, const float* uh, const float* vh, co
  * out: (B,S,S,S) patches, S = patch edge. */
 int fdn_gather_patches(const void* desc, float* out, int B, int S, void* stream);
 
+/* Sliding-window inference on the device (src/Network/PatchGenerator.py:13-40,53-86,116-154 and src/predictor.py:67-115): the patches of
+ * the tiler are never materialised.  frames: (F,6,X,Y,Z) fp32, channels u,v,w,mag_u,mag_v,mag_w as ImageDataset.load_vectorfield
+ * normalises them.  The window of edge P advances by E = P - 4 over the volume padded by 2 voxels per side (+ the far pad that makes
+ * the stride tile it: nx,ny,nz patches per axis, tiler.PatchGenerator.plan).  Global patch g: frame f = g / (nx*ny*nz), then (i,j,k)
+ * with k fastest; its voxel (a,b,c) reads source (i*E + a - 2, j*E + b - 2, k*E + c - 2), 0 outside [0,X)x[0,Y)x[0,Z).
+ * The volume form of the input features: phase, pc (count,P,P,P,3) of patches g0 .. g0 + count - 1, equal bit for bit to
+ * PatchGenerator.patchify followed by the plain entry point on those patches.  Same kernel (a by-value geometry selects the path).
+ * Refused before the device is touched: NULL pointers, P <= 4, non-positive extents / counts, count <= 0, g0 < 0,
+ * g0 + count > F*nx*ny*nz. */
+int fdn_input_features_volume(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
+                              int count, float* phase, float* pc, void* stream);
+/* Stitch (src/Network/PatchGenerator.py:13-40,53-86,116-154, src/predictor.py:67-115): pred (count,S,S,S,3) fp32, the predictions of
+ * global patches g0 .. g0 + count - 1; vol (F,3,Xo,Yo,Zo) fp32.  With core = S - 2*side (side = 2 * res_increase HR voxels stripped per
+ * patch side), core voxel (a,b,c) of patch (f,i,j,k) and component m goes to vol[f][m][i*core + a][j*core + b][k*core + c] iff that
+ * lies inside (Xo,Yo,Zo): the crop of the far pad.  Patches write disjoint voxels (no atomics; any chunking gives the same volume); a
+ * patch wholly inside the cropped region writes nothing.  The values are copied unchanged: de-normalisation stays with the caller.
+ * A path of the gather kernel selected by a runtime mode.  Refused before the device is touched: NULL pointers, S <= 2*side,
+ * count <= 0, g0 < 0, g0 + count > F*nx*ny*nz, an output extent <= 0 or > n*core. */
+int fdn_stitch_patches(const float* pred, float* vol, int F, int Xo, int Yo, int Zo, int S, int side, int nx, int ny, int nz,
+                       int64_t g0, int count, void* stream);
+
 /* sum of squares of the kernel (non-bias) parameters: the l2(5e-7) regulariser value is 5e-7 * out[0].
  * src/Network/TrainerController.py:129-141.  is_kernel: one byte per parameter. */
 int fdn_l2_sumsq(const float* w, const uint8_t* is_kernel, int64_t n, float* out, void* stream);
@@ -339,6 +360,9 @@ int fdn_conv64_dgrad_fused_bf16_multi(const uint16_t* const* dz, const uint16_t*
  * gradient (`dz` of Cout=1) stay fp32. */
 int fdn_input_features_bf16(const float* u, const float* v, const float* w, const float* mu, const float* mv,
                             const float* mw, uint16_t* phase, uint16_t* pc, int64_t nvox, void* stream);
+/* The volume form with bf16 phase / pc (src/Network/PatchGenerator.py:13-40,53-86,116-154, src/predictor.py:67-115); frames stay fp32. */
+int fdn_input_features_volume_bf16(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
+                                   int count, uint16_t* phase, uint16_t* pc, void* stream);
 int fdn_conv3d_fwd_bf16(const uint16_t* x, const uint16_t* x2, const float* w, const uint16_t* wpack, const float* bias,
                         const uint16_t* residual, void* y, int N, int D, int H, int W, int Cin, int Cout, int K, int ldy,
                         int y_coff, int act, float alpha, void* stream);
