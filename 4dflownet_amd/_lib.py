@@ -47,6 +47,8 @@ SIGNATURES = {
     "fdn_gather_patches": (c_i, [c_fp, c_fp, c_i, c_i, c_fp]),
     "fdn_input_features_volume": (c_i, [c_fp] + [c_i] * 8 + [c_i64, c_i, c_fp, c_fp, c_fp]),
     "fdn_stitch_patches": (c_i, [c_fp, c_fp] + [c_i] * 9 + [c_i64, c_i, c_fp]),
+    "fdn_stitch_patches_finish": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 9 + [c_i64, c_i, c_fp]),
+    "fdn_pack_patch_cores": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp]),
     "fdn_l2_sumsq": (c_i, [c_fp, c_fp, c_i64, c_fp, c_fp]),
     "fdn_adam_step": (c_i, [c_fp] * 5 + [c_i64] + [c_f] * 5 + [c_fp, c_fp, c_fp]),
     "fdn_adam_step_dev": (c_i, [c_fp] * 5 + [c_i64, c_fp] + [c_f] * 4 + [c_fp, c_fp, c_fp]),

@@ -21,16 +21,22 @@ struct PatchDesc {          // one per (sample, output tensor); mirrored by data
 // the core of every patch (S - 2*side per axis) goes to out = (F,3,Xo,Yo,Zo) at patch coordinate * core, voxels beyond the extents (the
 // cropped far pad) are dropped.  One element (voxel, component) per thread and step: reads are contiguous, writes of different patches
 // disjoint.
+// mode 2, fdn_stitch_patches_finish: the same walk, `out` is a float64 volume and every value is finished on the way
+// (src/predictor.py:103-107, src/utils/ImageDataset.py:31): d = (double)p * venc_f, +0.0 where |d| < threshold_f, with {venc_f, threshold_f}
+// read from the device table `scale` (F,2).
+// mode 3, fdn_pack_patch_cores: the cores alone, contiguous, out = (B,cs,cs,cs,3) -- what a data-parallel rank sends to the rank that
+// stitches (the same element walk: out[i] is the element mode 1 would place).
 struct StitchGeom {
     const float* pred;
     int64_t g0;
     int32_t Xo, Yo, Zo, side;
     int32_t nx, ny, nz, pad_;
+    const double* scale;    // mode 2 only
 };
 
 __global__ __launch_bounds__(256) void gather_patches_kernel(const PatchDesc* __restrict__ desc, float* __restrict__ out, int B,
                                                               int S, int mode, StitchGeom sg) {
-    if (mode == 1) {
+    if (mode != 0) {
         const int cs = S - 2 * sg.side;                                  // core edge
         const int64_t per = (int64_t)cs * cs * cs * 3;
         const int64_t total = per * B;
@@ -40,6 +46,8 @@ __global__ __launch_bounds__(256) void gather_patches_kernel(const PatchDesc* __
             const int a = r / (cs * cs * 3); r -= a * cs * cs * 3;
             const int b = r / (cs * 3); r -= b * cs * 3;
             const int c = r / 3, comp = r - c * 3;
+            const int64_t src = (((n * S + sg.side + a) * S + sg.side + b) * S + sg.side + c) * 3 + comp;
+            if (mode == 3) { out[i] = sg.pred[src]; continue; }
             int64_t g = sg.g0 + n;
             const int pk = (int)(g % sg.nz); g /= sg.nz;
             const int pj = (int)(g % sg.ny); g /= sg.ny;
@@ -47,8 +55,15 @@ __global__ __launch_bounds__(256) void gather_patches_kernel(const PatchDesc* __
             const int64_t f = g / sg.nx;
             const int64_t x = (int64_t)pi * cs + a, y = (int64_t)pj * cs + b, z = (int64_t)pk * cs + c;
             if (x >= sg.Xo || y >= sg.Yo || z >= sg.Zo) continue;
-            const float v = sg.pred[(((n * S + sg.side + a) * S + sg.side + b) * S + sg.side + c) * 3 + comp];
-            out[(((f * 3 + comp) * sg.Xo + x) * sg.Yo + y) * sg.Zo + z] = v;
+            const float v = sg.pred[src];
+            const int64_t dst = (((f * 3 + comp) * sg.Xo + x) * sg.Yo + y) * sg.Zo + z;
+            if (mode == 2) {
+                double d = (double)v * sg.scale[2 * f];                  // de-normalise (:103)
+                if (fabs(d) < sg.scale[2 * f + 1]) d = 0.0;              // strict: a product equal to the threshold stays (:104-107)
+                ((double*)out)[dst] = d;
+            } else {
+                out[dst] = v;
+            }
         }
         return;
     }
@@ -86,26 +101,53 @@ extern "C" int fdn_gather_patches(const void* desc, float* out, int B, int S, vo
     return FDN_OK;
 }
 
-extern "C" int fdn_stitch_patches(const float* pred, float* vol, int F, int Xo, int Yo, int Zo, int S, int side, int nx, int ny, int nz,
-                                  int64_t g0, int count, void* stream) {
-    FDN_REQUIRE(pred && vol, "fdn_stitch_patches: NULL argument");
-    FDN_REQUIRE(side >= 0 && S > 2 * side && S <= 512, "fdn_stitch_patches: S=%d must exceed 2*side (side=%d) and not 512", S, side);
-    FDN_REQUIRE(F > 0 && nx > 0 && ny > 0 && nz > 0, "fdn_stitch_patches: bad frame / patch counts (F=%d, %d,%d,%d)", F, nx, ny, nz);
-    FDN_REQUIRE(count > 0, "fdn_stitch_patches: count=%d", count);
-    FDN_REQUIRE(g0 >= 0, "fdn_stitch_patches: g0=%lld", (long long)g0);
-    FDN_REQUIRE(g0 + count <= (int64_t)F * nx * ny * nz, "fdn_stitch_patches: patches [%lld, %lld) exceed F*nx*ny*nz = %lld",
+// argument checks and launch shared by fdn_stitch_patches (scale == nullptr, mode 1) and fdn_stitch_patches_finish (mode 2)
+static int stitch_launch(const char* who, const float* pred, void* vol, const double* scale, int mode, int F, int Xo, int Yo, int Zo, int S,
+                         int side, int nx, int ny, int nz, int64_t g0, int count, void* stream) {
+    FDN_REQUIRE(pred && vol && (mode == 1 || scale), "%s: NULL argument", who);
+    FDN_REQUIRE(side >= 0 && S > 2 * side && S <= 512, "%s: S=%d must exceed 2*side (side=%d) and not 512", who, S, side);
+    FDN_REQUIRE(F > 0 && nx > 0 && ny > 0 && nz > 0, "%s: bad frame / patch counts (F=%d, %d,%d,%d)", who, F, nx, ny, nz);
+    FDN_REQUIRE(count > 0, "%s: count=%d", who, count);
+    FDN_REQUIRE(g0 >= 0, "%s: g0=%lld", who, (long long)g0);
+    FDN_REQUIRE(g0 + count <= (int64_t)F * nx * ny * nz, "%s: patches [%lld, %lld) exceed F*nx*ny*nz = %lld", who,
                 (long long)g0, (long long)(g0 + count), (long long)((int64_t)F * nx * ny * nz));
     const int64_t cs = S - 2 * side;
     FDN_REQUIRE(Xo > 0 && Yo > 0 && Zo > 0 && Xo <= nx * cs && Yo <= ny * cs && Zo <= nz * cs,
-                "fdn_stitch_patches: output extents (%d,%d,%d) must be in 1..n*(S-2*side) = (%lld,%lld,%lld)", Xo, Yo, Zo,
+                "%s: output extents (%d,%d,%d) must be in 1..n*(S-2*side) = (%lld,%lld,%lld)", who, Xo, Yo, Zo,
                 (long long)(nx * cs), (long long)(ny * cs), (long long)(nz * cs));
     const int64_t total = (int64_t)count * cs * cs * cs * 3;
     int64_t nb = (total + 255) / 256;
     if (nb > 4096) nb = 4096;
     StitchGeom sg{};
-    sg.pred = pred; sg.g0 = g0; sg.Xo = Xo; sg.Yo = Yo; sg.Zo = Zo; sg.side = side; sg.nx = nx; sg.ny = ny; sg.nz = nz;
-    hipLaunchKernelGGL(gather_patches_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const PatchDesc*)nullptr, vol,
-                       count, S, 1, sg);
+    sg.pred = pred; sg.g0 = g0; sg.Xo = Xo; sg.Yo = Yo; sg.Zo = Zo; sg.side = side; sg.nx = nx; sg.ny = ny; sg.nz = nz; sg.scale = scale;
+    hipLaunchKernelGGL(gather_patches_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const PatchDesc*)nullptr,
+                       (float*)vol, count, S, mode, sg);
+    FDN_CHECK_LAUNCH("gather_patches_kernel");
+    return FDN_OK;
+}
+
+extern "C" int fdn_stitch_patches(const float* pred, float* vol, int F, int Xo, int Yo, int Zo, int S, int side, int nx, int ny, int nz,
+                                  int64_t g0, int count, void* stream) {
+    return stitch_launch("fdn_stitch_patches", pred, vol, nullptr, 1, F, Xo, Yo, Zo, S, side, nx, ny, nz, g0, count, stream);
+}
+
+extern "C" int fdn_stitch_patches_finish(const float* pred, double* vol, const double* frame_scale, int F, int Xo, int Yo, int Zo, int S,
+                                         int side, int nx, int ny, int nz, int64_t g0, int count, void* stream) {
+    return stitch_launch("fdn_stitch_patches_finish", pred, vol, frame_scale, 2, F, Xo, Yo, Zo, S, side, nx, ny, nz, g0, count, stream);
+}
+
+extern "C" int fdn_pack_patch_cores(const float* pred, float* cores, int S, int side, int count, void* stream) {
+    FDN_REQUIRE(pred && cores, "fdn_pack_patch_cores: NULL argument");
+    FDN_REQUIRE(side >= 0 && S > 2 * side && S <= 512, "fdn_pack_patch_cores: S=%d must exceed 2*side (side=%d) and not 512", S, side);
+    FDN_REQUIRE(count > 0, "fdn_pack_patch_cores: count=%d", count);
+    const int64_t cs = S - 2 * side;
+    const int64_t total = (int64_t)count * cs * cs * cs * 3;
+    int64_t nb = (total + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    StitchGeom sg{};
+    sg.pred = pred; sg.side = side;
+    hipLaunchKernelGGL(gather_patches_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const PatchDesc*)nullptr, cores,
+                       count, S, 3, sg);
     FDN_CHECK_LAUNCH("gather_patches_kernel");
     return FDN_OK;
 }

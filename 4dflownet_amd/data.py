@@ -310,6 +310,11 @@ class ImageDataset:
         with h5io.open_read(filepath) as hl:
             return hl[self.velocity_colnames[0]].shape[0]
 
+    def get_volume_shape(self, filepath):
+        """(X,Y,Z) of one row, without decoding anything."""
+        with h5io.open_read(filepath) as hl:
+            return tuple(int(n) for n in hl[self.velocity_colnames[0]].shape[1:])
+
     def load_vectorfield(self, filepath, idx):
         rd = lambda n: self._cache.get(filepath, n)
         dxa = rd(self.dx_colname)

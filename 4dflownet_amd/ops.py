@@ -75,19 +75,62 @@ def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=No
     return phase, pc
 
 
-def stitch_patches(pred, vol, side, counts, g0=0):
+def _pred_edge(pred, who):
+    if pred.dim() != 5 or pred.shape[4] != 3 or not (pred.shape[1] == pred.shape[2] == pred.shape[3]):
+        raise FdnError("%s: pred must be (count,S,S,S,3), got %s" % (who, tuple(pred.shape)))
+    return pred.shape[1]
+
+
+def _p64(t, name):
+    if not t.is_cuda:
+        raise FdnError("%s must live on the GPU; the HIP path has no CPU fallback" % name)
+    if t.dtype != torch.float64:
+        raise FdnError("%s must be float64 (got %s)" % (name, t.dtype))
+    if not t.is_contiguous():
+        raise FdnError("%s must be contiguous" % name)
+    return t.data_ptr()
+
+
+def stitch_patches(pred, vol, side, counts, g0=0, frame_scale=None):
     """Cores of the predicted patches [g0, g0 + len(pred)) into the stitched volumes: pred (count,S,S,S,3), vol (F,3,Xo,Yo,Zo), side =
     2 * res_increase HR voxels stripped per patch side; core voxels that fall into the cropped far pad are dropped (tiler.PatchGenerator.
-    _patchup_with_overlap per frame and component).  Writes of different patches are disjoint: any batching gives the same volume."""
-    if pred.dim() != 5 or pred.shape[4] != 3 or not (pred.shape[1] == pred.shape[2] == pred.shape[3]):
-        raise FdnError("stitch_patches: pred must be (count,S,S,S,3), got %s" % (tuple(pred.shape),))
+    _patchup_with_overlap per frame and component).  Writes of different patches are disjoint: any batching gives the same volume.
+    frame_scale (a float64 device tensor (F,2) of {venc, threshold} per frame): vol is float64 and every value is finished on the way,
+    p * venc with +0.0 where the magnitude is below the threshold (predictor.py:103-107; fdn_stitch_patches_finish)."""
+    S = _pred_edge(pred, "stitch_patches")
     if vol.dim() != 5 or vol.shape[1] != 3:
         raise FdnError("stitch_patches: vol must be (F,3,Xo,Yo,Zo), got %s" % (tuple(vol.shape),))
     F, _, Xo, Yo, Zo = vol.shape
     nx, ny, nz = (int(n) for n in counts)
-    check(_lib.load().fdn_stitch_patches(_p(pred, "pred"), _p(vol, "vol"), F, Xo, Yo, Zo, pred.shape[1], int(side), nx, ny, nz,
-                                         int(g0), pred.shape[0], _stream()), "fdn_stitch_patches")
+    if frame_scale is None:
+        check(_lib.load().fdn_stitch_patches(_p(pred, "pred"), _p(vol, "vol"), F, Xo, Yo, Zo, S, int(side), nx, ny, nz,
+                                             int(g0), pred.shape[0], _stream()), "fdn_stitch_patches")
+        return vol
+    if vol.dtype != torch.float64:
+        raise FdnError("stitch_patches: vol must be float64 with frame_scale (got %s)" % vol.dtype)
+    if tuple(frame_scale.shape) != (F, 2):
+        raise FdnError("stitch_patches: frame_scale must be (F,2) = (%d,2), got %s" % (F, tuple(frame_scale.shape)))
+    check(_lib.load().fdn_stitch_patches_finish(_p(pred, "pred"), _p64(vol, "vol (with frame_scale)"), _p64(frame_scale, "frame_scale"),
+                                                F, Xo, Yo, Zo, S, int(side), nx, ny, nz, int(g0), pred.shape[0], _stream()),
+          "fdn_stitch_patches_finish")
     return vol
+
+
+def pack_patch_cores(pred, side, out=None):
+    """The cores of predicted patches, contiguous: pred (count,S,S,S,3) -> (count,c,c,c,3), c = S - 2*side (fdn_pack_patch_cores).
+    stitch_patches(pack_patch_cores(pred, side), vol, 0, ...) equals stitch_patches(pred, vol, side, ...)."""
+    S = _pred_edge(pred, "pack_patch_cores")
+    side = int(side)
+    c = S - 2 * side
+    if side < 0 or c <= 0:
+        raise FdnError("pack_patch_cores: S=%d must exceed 2*side (side=%d)" % (S, side))
+    shape = (pred.shape[0], c, c, c, 3)
+    if out is None:
+        out = torch.empty(shape, device=pred.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape:
+        raise FdnError("pack_patch_cores: out must be %s, got %s" % (shape, tuple(out.shape)))
+    check(_lib.load().fdn_pack_patch_cores(_p(pred, "pred"), _p(out, "out"), S, side, pred.shape[0], _stream()), "fdn_pack_patch_cores")
+    return out
 
 
 def pack_conv64_weights(w, wp_fwd=None, wp_dgrad=None, want_dgrad=True):

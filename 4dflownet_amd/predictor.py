@@ -2,7 +2,9 @@
 de-normalise -> zero sub-pixel velocities -> append u,v,w (+dx/res_increase) to the output HDF5.
 
 With torch.distributed initialised (BASELINE cfg5) the patch list is split contiguously across ranks; every rank
-runs its share through the same pipelined HIP forward loop and sends exactly its rows to rank 0, which stitches and writes."""
+runs its share through the same pipelined HIP forward loop and sends exactly its rows to rank 0, which stitches and writes.
+With the device tiler (predict_file(device_tiler=True)) the ranks send only the cores of their predictions, and rank 0
+stitches, de-normalises and zeroes them on the device (_predict_file_device)."""
 import os
 import time
 
@@ -153,65 +155,195 @@ def predict_patches(network, velocities, magnitudes, batch_size):
     return None
 
 
-def predict_volume(network, frames, patch_size, batch_size, out=None):
+def _frame_scale_tensor(frame_scale, F, device):
+    """frame_scale of predict_volume as the (F,2) float64 device table fdn_stitch_patches_finish reads."""
+    if isinstance(frame_scale, torch.Tensor):
+        t = frame_scale.to(device=device, dtype=torch.float64).contiguous()
+    else:
+        t = torch.tensor([[float(v), float(thr)] for v, thr in frame_scale], dtype=torch.float64).reshape(-1, 2).to(device)
+    if tuple(t.shape) != (F, 2):
+        raise ValueError("frame_scale must hold (venc, threshold) for each of the %d frames, got %s" % (F, tuple(t.shape)))
+    return t
+
+
+def predict_volume(network, frames, patch_size, batch_size, out=None, frame_scale=None, patch_range=None):
     """Sliding-window inference with the tiler on the device (predictor.py:67-115 without its host work).  frames: (F,6,X,Y,Z)
     normalised fp32 (u,v,w,mag_u,mag_v,mag_w as ImageDataset.load_vectorfield leaves them), numpy or a device tensor; they are
     uploaded once.  Runs batches of `batch_size` consecutive global patches -- a batch may span two frames, so only the last one is
     ragged --: features straight from the frames (ops.input_features_volume), network.forward_features, the cores into the output
     (ops.stitch_patches).  Returns the stitched NORMALISED predictions, a (F,3,X*R,Y*R,Z*R) fp32 device tensor (`out` if given);
-    de-normalisation and the zeroing of sub-pixel velocities stay with the caller.  Everything is queued on the current stream."""
+    de-normalisation and the zeroing of sub-pixel velocities stay with the caller.
+    frame_scale (a host sequence of (venc, threshold) per frame, or that as an (F,2) float64 device tensor): the output is float64 and
+    FINISHED instead -- prediction * venc, +0.0 where its magnitude is below the threshold (predictor.py:103-107; a threshold of 0
+    zeroes nothing) -- inside the stitch launch.
+    patch_range=(lo, hi): only global patches [lo, hi) are computed and stitched (a data-parallel shard); the voxels of the other
+    patches are left as they are.  Everything is queued on the current stream."""
     frames = network._to_dev(frames)
     if frames.dim() != 5 or frames.shape[1] != 6:
         raise ValueError("predict_volume: frames must be (F,6,X,Y,Z), got %s" % (tuple(frames.shape),))
     R = network.res_increase
     F = frames.shape[0]
     counts, _, extents = PatchGenerator(patch_size, R).plan(tuple(frames.shape[2:]))
+    scale = None if frame_scale is None else _frame_scale_tensor(frame_scale, F, frames.device)
+    dtype = torch.float32 if scale is None else torch.float64
     if out is None:
-        out = torch.empty((F, 3) + extents, device=frames.device, dtype=torch.float32)    # every voxel belongs to one patch core
-    elif tuple(out.shape) != (F, 3) + extents:
-        raise ValueError("predict_volume: out must be %s, got %s" % ((F, 3) + extents, tuple(out.shape)))
+        out = torch.empty((F, 3) + extents, device=frames.device, dtype=dtype)    # every voxel belongs to one patch core
+    elif tuple(out.shape) != (F, 3) + extents or out.dtype != dtype:
+        raise ValueError("predict_volume: out must be %s %s, got %s %s" % (dtype, (F, 3) + extents, out.dtype, tuple(out.shape)))
     total = F * counts[0] * counts[1] * counts[2]
-    for g0 in range(0, total, batch_size):
-        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, min(batch_size, total - g0))
-        network.ops.stitch_patches(network.forward_features(phase, pc), out, 2 * R, counts, g0)
+    lo, hi = (0, total) if patch_range is None else (int(patch_range[0]), int(patch_range[1]))
+    if not 0 <= lo <= hi <= total:
+        raise ValueError("predict_volume: patch_range (%d, %d) outside [0, %d]" % (lo, hi, total))
+    for g0 in range(lo, hi, batch_size):
+        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, min(batch_size, hi - g0))
+        network.ops.stitch_patches(network.forward_features(phase, pc), out, 2 * R, counts, g0, frame_scale=scale)
     return out
+
+
+def shard_frame_span(lo, hi, per_frame):
+    """Frames [f0, f1) that the global patches [lo, hi) of frames of `per_frame` patches touch ((0, 0) for an empty range): what a
+    rank loads for its shard.  Patch g is patch g - f0 * per_frame of those frames."""
+    if hi <= lo:
+        return 0, 0
+    return lo // per_frame, (hi - 1) // per_frame + 1
+
+
+def predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=0):
+    """The shard of a data-parallel rank: global patches [lo, hi) in batches of `batch_size` consecutive patches, the core of every
+    prediction packed (ops.pack_patch_cores) into ONE (hi - lo, c, c, c, 3) fp32 device buffer, c = (patch_size - 4) * R -- what the
+    rank sends; the receiver stitches it with side 0 at g0 = lo.  frames as in predict_volume; they may hold only the frames the range
+    touches (shard_frame_span), first_frame being the global index of frames[0]."""
+    frames = network._to_dev(frames)
+    if frames.dim() != 5 or frames.shape[1] != 6:
+        raise ValueError("predict_cores: frames must be (F,6,X,Y,Z), got %s" % (tuple(frames.shape),))
+    R = network.res_increase
+    counts, _, _ = PatchGenerator(patch_size, R).plan(tuple(frames.shape[2:]))
+    per_frame = counts[0] * counts[1] * counts[2]
+    lo, hi, base = int(lo), int(hi), int(first_frame) * per_frame
+    if not base <= lo <= hi <= base + frames.shape[0] * per_frame:
+        raise ValueError("predict_cores: patches [%d, %d) are not in frames %d..%d (%d patches each)"
+                         % (lo, hi, first_frame, first_frame + frames.shape[0] - 1, per_frame))
+    c = (patch_size - 4) * R
+    cores = torch.empty((hi - lo, c, c, c, 3), device=frames.device, dtype=torch.float32)
+    for s in range(lo, hi, batch_size):
+        e = min(s + batch_size, hi)
+        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, s - base, e - s)
+        network.ops.pack_patch_cores(network.forward_features(phase, pc), 2 * R, out=cores[s - lo:e - lo])
+    return cores
 
 
 DEVICE_TILER_GROUP_BYTES = 1 << 30        # frames + stitched output of one group of rows (predict_file(device_tiler=True))
 
 
-def _volume_stage(network, shape):
-    """Two pinned fp32 buffers for stitched groups + a copy stream, kept on the network between calls (the pattern of _stage)."""
-    st = getattr(network, "_predict_vol_stage", None)
+def _volume_stage(network, shape, dtype=torch.float64):
+    """Two pinned buffers for stitched groups + a copy stream, kept on the network between calls (the pattern of _stage); one pair per
+    dtype -- float64 for finished groups, fp32 with FDN_DEVICE_FINISH=0 -- so that switching the finish does not re-pin."""
+    stages = getattr(network, "_predict_vol_stages", None)
+    if stages is None:
+        stages = network._predict_vol_stages = {}
+    st = stages.get(dtype)
     if st is None or st[0] != tuple(shape):
-        stream = st[2] if st is not None else torch.cuda.Stream(device=network.device)
-        st = (tuple(shape), [torch.empty(tuple(shape), dtype=torch.float32).pin_memory() for _ in range(2)], stream)
-        network._predict_vol_stage = st
+        stream = next(iter(stages.values()))[2] if stages else torch.cuda.Stream(device=network.device)
+        st = (tuple(shape), [torch.empty(tuple(shape), dtype=dtype).pin_memory() for _ in range(2)], stream)
+        stages[dtype] = st
+    network._predict_vol_stage = st
     return st[1], st[2]
+
+
+def _pinned_cores(network, shape):
+    """A pinned fp32 host buffer of `shape` for the host-staged transport of packed cores (gloo), kept on the network and grown on demand."""
+    n = int(np.prod(shape))
+    buf = getattr(network, "_predict_cores_stage", None)
+    if buf is None or buf.numel() < n:
+        buf = torch.empty(n, dtype=torch.float32).pin_memory()
+        network._predict_cores_stage = buf
+    return buf[:n].view(shape)
+
+
+def _send_cores(network, cores):
+    """A rank's packed cores to rank 0: one grouped RCCL send of the device buffer, or through pinned host memory under gloo."""
+    import torch.distributed as dist
+    if parallel._host_staged():
+        host = _pinned_cores(network, tuple(cores.shape))
+        host.copy_(cores, non_blocking=True)
+        torch.cuda.current_stream(network.device).synchronize()
+        dist.send(host, dst=0)
+        return
+    for q in dist.batch_isend_irecv([dist.P2POp(dist.isend, cores, 0)]):
+        q.wait()
+
+
+def _recv_cores(network, shapes):
+    """Rank 0: the packed cores of the peers {rank: shape} as device tensors {rank: tensor}, ordered on the current stream.  One grouped
+    RCCL launch for all peers; under gloo each buffer arrives in pinned host memory and is uploaded."""
+    import torch.distributed as dist
+    dev = torch.device(network.device)
+    got = {}
+    if parallel._host_staged():
+        for r, shape in shapes.items():
+            host = _pinned_cores(network, shape)
+            dist.recv(host, src=r)
+            got[r] = host.to(dev, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()          # the one staging buffer is reused for the next peer
+        return got
+    for r, shape in shapes.items():
+        got[r] = torch.empty(shape, device=dev, dtype=torch.float32)
+    ops_ = [dist.P2POp(dist.irecv, t, r) for r, t in got.items()]
+    for q in (dist.batch_isend_irecv(ops_) if ops_ else []):
+        q.wait()                                                  # makes the current stream wait for the transfers; no host sync
+    return got
 
 
 def _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size, round_small_values, verbose,
                          frames_per_group):
     """predict_file with the tiler on the device: rows in groups whose frames and stitched output fit DEVICE_TILER_GROUP_BYTES (or
-    frames_per_group rows), one predict_volume per group; the stitched group travels to pinned host memory on the copy stream while
-    the next group computes, and is then de-normalised, zeroed and appended exactly as on the host path."""
+    frames_per_group rows), one predict_volume per group, de-normalised and zeroed inside its stitch launches (frame_scale); the
+    finished float64 group travels to pinned host memory on the copy stream while the next group computes and is then appended exactly
+    as on the host path.  FDN_DEVICE_FINISH=0: the stitched group travels as fp32 and is finished on the host (A/B timing).
+    Data-parallel: every group's patch list is split with shard_bounds; rank r > 0 loads the rows its shard touches, runs
+    predict_cores and sends its one buffer of cores to rank 0, which stitches (and finishes) its own batches directly, posts the
+    receives after its own shard (see predict_patches), and stitches every peer's buffer with side 0 at that peer's first patch."""
+    world, rank = parallel.world_size(), parallel.rank()
+    device_finish = os.environ.get("FDN_DEVICE_FINISH", "1") not in ("", "0")
     dataset = ImageDataset()
     nr_rows = dataset.get_dataset_len(input_filepath)
     written = []
     if nr_rows == 0:
         return written
-    dataset.load_vectorfield(input_filepath, 0)
-    lr_shape = dataset.u.shape
+    lr_shape = dataset.get_volume_shape(input_filepath)
     R = res_increase
-    if frames_per_group is None:
-        per_frame = 4 * int(np.prod(lr_shape)) * (6 + 3 * R ** 3)
+    if frames_per_group is None:                                       # depends on the file alone: all ranks walk the same groups
+        per_frame = int(np.prod(lr_shape)) * (24 + (24 if device_finish else 12) * R ** 3)
         frames_per_group = max(1, DEVICE_TILER_GROUP_BYTES // per_frame)
     fpg = max(1, min(int(frames_per_group), nr_rows))
-    out_shape = (fpg, 3) + tuple(n * R for n in lr_shape)
-    stage, copy_stream = _volume_stage(network, out_shape)
-    main = torch.cuda.current_stream(network.device)
     counts, _, _ = PatchGenerator(patch_size, R).plan(lr_shape)
     per_frame_patches = counts[0] * counts[1] * counts[2]
+    core = (patch_size - 4) * R
+
+    def load(rows):
+        frames = np.empty((len(rows), 6) + lr_shape, dtype=np.float32)
+        meta = []
+        for f, nrow in enumerate(rows):
+            dataset.load_vectorfield(input_filepath, nrow)
+            for c, a in enumerate((dataset.u, dataset.v, dataset.w, dataset.mag_u, dataset.mag_v, dataset.mag_w)):
+                frames[f, c] = a
+            meta.append((dataset.venc, dataset.velocity_per_px, dataset.dx))
+        return frames, meta
+
+    if rank > 0:
+        for r0 in range(0, nr_rows, fpg):
+            nrows = min(fpg, nr_rows - r0)
+            bounds = shard_bounds(nrows * per_frame_patches, world)
+            lo, hi = bounds[rank], bounds[rank + 1]
+            if hi > lo:                                                # an empty shard neither sends nor is waited for
+                f0, f1 = shard_frame_span(lo, hi, per_frame_patches)
+                frames, _ = load(list(range(r0 + f0, r0 + f1)))
+                _send_cores(network, predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=f0))
+        return written
+
+    out_shape = (fpg, 3) + tuple(n * R for n in lr_shape)
+    stage, copy_stream = _volume_stage(network, out_shape, torch.float64 if device_finish else torch.float32)
+    main = torch.cuda.current_stream(network.device)
 
     def finish(job):
         ev, slot, rows, meta, t0, _keep = job
@@ -223,9 +355,12 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
         for f, (venc, vpp, dx) in enumerate(meta):
             vols, cols = [], []
             for i in range(3):
-                v = host[f, i].astype(np.float64) * venc               # de-normalise (:103)
-                if round_small_values:
-                    v[np.abs(v) < vpp] = 0                             # (:104-107)
+                if device_finish:
+                    v = host[f, i].copy()                              # finished on the device; the staging buffer is reused
+                else:
+                    v = host[f, i].astype(np.float64) * venc           # de-normalise (:103)
+                    if round_small_values:
+                        v[np.abs(v) < vpp] = 0                         # (:104-107)
                 v = np.expand_dims(v, axis=0)
                 vols.append(v)
                 cols.append((dataset.velocity_colnames[i], v))
@@ -237,15 +372,17 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
     pending = None
     for k, r0 in enumerate(range(0, nr_rows, fpg)):
         rows = list(range(r0, min(r0 + fpg, nr_rows)))
-        frames = np.empty((len(rows), 6) + tuple(lr_shape), dtype=np.float32)
-        meta = []
-        for f, nrow in enumerate(rows):
-            dataset.load_vectorfield(input_filepath, nrow)
-            for c, a in enumerate((dataset.u, dataset.v, dataset.w, dataset.mag_u, dataset.mag_v, dataset.mag_w)):
-                frames[f, c] = a
-            meta.append((dataset.venc, dataset.velocity_per_px, dataset.dx))
+        frames, meta = load(rows)
         t0 = time.time()
-        vol = predict_volume(network, frames, patch_size, batch_size)
+        scale = None
+        if device_finish:                                              # the doubles the host finish multiplies and compares with
+            scale = _frame_scale_tensor([(venc, vpp if round_small_values else 0.0) for venc, vpp, _ in meta], len(rows), network.device)
+        bounds = shard_bounds(len(rows) * per_frame_patches, world)
+        vol = predict_volume(network, frames, patch_size, batch_size, frame_scale=scale, patch_range=(bounds[0], bounds[1]))
+        peers = {r: (bounds[r + 1] - bounds[r], core, core, core, 3) for r in range(1, world) if bounds[r + 1] > bounds[r]}
+        if peers:                                                      # posted after the own shard (see predict_patches)
+            for r, cores in _recv_cores(network, peers).items():
+                network.ops.stitch_patches(cores, vol, 0, counts, bounds[r], frame_scale=scale)
         slot = k & 1                                                   # its previous user (group k - 2) was finished one turn ago
         copy_stream.wait_stream(main)
         with torch.cuda.stream(copy_stream):
@@ -260,25 +397,18 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
     return written
 
 
-_warned_device_tiler_world = False
-
-
 def predict_file(network, input_filepath, output_filepath, patch_size, res_increase, batch_size=8,
                  round_small_values=True, verbose=True, device_tiler=False, frames_per_group=None):
     """predictor.py:67-115 for every row of the input file.  Returns the list of (u,v,w) volumes written (rank 0; the other ranks
     of a data-parallel run compute their shard of every row's patches and return an empty list).
     device_tiler=True (or FDN_DEVICE_TILER=1): patchify and stitch run on the device (predict_volume) over groups of rows --
-    frames_per_group rows, default what fits DEVICE_TILER_GROUP_BYTES; same file, same returned volumes (dtype and shape).  Single
-    process only: a data-parallel run keeps the host tiler and says so once."""
-    global _warned_device_tiler_world
+    frames_per_group rows, default what fits DEVICE_TILER_GROUP_BYTES; same file, same returned volumes (dtype and shape).  The
+    de-normalisation and the zeroing of sub-pixel velocities run inside the stitch launch (FDN_DEVICE_FINISH=0: on the host, as before).
+    Data-parallel runs shard every group's patches over the ranks; the peers send the cores of their patches, rank 0 stitches, finishes
+    and writes (_predict_file_device)."""
     if device_tiler or os.environ.get("FDN_DEVICE_TILER", "0") not in ("", "0"):
-        if parallel.world_size() == 1:
-            return _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size,
-                                        round_small_values, verbose, frames_per_group)
-        if not _warned_device_tiler_world:
-            _warned_device_tiler_world = True
-            import warnings
-            warnings.warn("predict_file: the device tiler runs in a single process only; this data-parallel run keeps the host tiler")
+        return _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size,
+                                    round_small_values, verbose, frames_per_group)
     pgen = PatchGenerator(patch_size, res_increase)
     dataset = ImageDataset()
     nr_rows = dataset.get_dataset_len(input_filepath)

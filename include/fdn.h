@@ -279,6 +279,21 @@ int fdn_input_features_volume(const float* frames, int F, int X, int Y, int Z, i
  * count <= 0, g0 < 0, g0 + count > F*nx*ny*nz, an output extent <= 0 or > n*core. */
 int fdn_stitch_patches(const float* pred, float* vol, int F, int Xo, int Yo, int Zo, int S, int side, int nx, int ny, int nz,
                        int64_t g0, int count, void* stream);
+/* fdn_stitch_patches with the predictor's post-processing folded into the write (src/predictor.py:103-107, src/utils/ImageDataset.py:31):
+ * vol (F,3,Xo,Yo,Zo) is FLOAT64 and frame_scale a caller-owned DEVICE table (F,2) of doubles {venc_f, threshold_f}.  A core voxel of
+ * frame f with prediction p is written as d = (double)p * venc_f, or as +0.0 when fabs(d) < threshold_f (strict: a product equal to the
+ * threshold is kept; a threshold of 0 zeroes nothing, round_small_values=False) -- the bits of
+ * `v = stitched.astype(float64) * venc; v[abs(v) < velocity_per_px] = 0` on the host.  Geometry, crop rule and refusals are those of
+ * fdn_stitch_patches, plus a NULL frame_scale.  side = 0 is legal in both: cores packed by fdn_pack_patch_cores are stitched with S = core.
+ * Another runtime mode of the gather kernel. */
+int fdn_stitch_patches_finish(const float* pred, double* vol, const double* frame_scale, int F, int Xo, int Yo, int Zo,
+                              int S, int side, int nx, int ny, int nz, int64_t g0, int count, void* stream);
+/* The cores of predicted patches, contiguous: pred (count,S,S,S,3) fp32 -> cores (count,c,c,c,3), c = S - 2*side,
+ * cores[n][a][b][k][m] = pred[n][side+a][side+b][side+k][m].  The unit a data-parallel rank sends to the rank that stitches (patch 24
+ * at x2: 40^3 of 48^3 voxels, 1.73x less transport); stitching the cores with side = 0 equals stitching pred with `side`, and finishing
+ * them (src/predictor.py:103-107) is fdn_stitch_patches_finish on the receiver.  A pure copy, a runtime mode of the gather kernel.
+ * Refused before the device is touched: NULL pointers, side < 0, S <= 2*side, S > 512, count <= 0. */
+int fdn_pack_patch_cores(const float* pred, float* cores, int S, int side, int count, void* stream);
 
 /* sum of squares of the kernel (non-bias) parameters: the l2(5e-7) regulariser value is 5e-7 * out[0].
  * src/Network/TrainerController.py:129-141.  is_kernel: one byte per parameter. */

@@ -2,9 +2,12 @@
 Times predictor.predict_patches (tiler -> batched HIP forward -> gather) on the shipped example volume (12 patches) and on a
 synthetic 100x100x100 volume (125 patches); prints patches/s.  Launch under torch.distributed.run to shard patches over ranks.
 
---device-tiler [--runs N] (single process): whole-job wall time of predictor.predict_file without the HDF5 write, host tiler and device
-tiler (device_tiler=True) alternately, N >= 3 timed runs each after one warm-up of both, on the example volume and on the synthetic 100^3
-volume as a four-frame file; prints every run, the median, the spread (min .. max) and patches/s."""
+--device-tiler [--runs N]: whole-job wall time of predictor.predict_file without the HDF5 write, on the example volume and on the synthetic
+100^3 volume as a four-frame file; the legs run alternately, N >= 3 timed runs each after one warm-up of all of them; prints every run, the
+median, the spread (min .. max) and patches/s.  Single process: host tiler, device tiler with the host finish (FDN_DEVICE_FINISH=0) and
+device tiler with the finish inside the stitch launch (the default).  Under torch.distributed.run: the data-parallel host tiler (whole
+patches to rank 0, stitched on its host) and the data-parallel device tiler (cores to rank 0, stitched and finished on its device); with
+fewer devices than ranks the lines are marked oversubscribed and are no scaling numbers."""
 import importlib
 import os
 import sys
@@ -36,56 +39,82 @@ def _synthetic_file(path, frames=4, n=100):
     h5io.write_file(path, tree)
 
 
-def device_tiler_leg(net, dtype, runs):
+# (label, device_tiler, FDN_DEVICE_FINISH or None = leave unset)
+LEGS_SINGLE = (("host", False, None), ("device, host finish", True, "0"), ("device, device finish", True, "1"))
+LEGS_DP = (("dp host", False, None), ("dp device", True, "1"))
+
+
+def device_tiler_leg(net, dtype, runs, rank=0, world=1):
     """predict_file end to end (load, patchify, forward, stitch, post-processing) with the file append replaced by a no-op."""
     import statistics
     import tempfile
     build = importlib.import_module("4dflownet_amd.build")
     import subprocess
+    say = print if rank == 0 else (lambda *a, **k: None)
     commit = os.environ.get("FDN_COMMIT")                  # a snapshot of the tree without its history: the caller names the commit
     if not commit:
         r = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True)
         d = subprocess.run(["git", "-C", ROOT, "status", "--porcelain", "--untracked-files=no"], capture_output=True, text=True)
         commit = r.stdout.strip() + ("+dirty" if d.stdout.strip() else "") if r.returncode == 0 else "unknown"
-    print("# commit %s lib_source_stamp %s" % (commit, build.source_stamp()))
-    print("# tools/bench_predictor.py --device-tiler --runs %d%s: predict_file wall time without the HDF5 write, patch 24, res x2, batch 8, "
-          "8+4 ResBlocks, %s, %s" % (runs, " --bf16" if dtype != "float32" else "", dtype, torch.cuda.get_device_name(0)))
+    say("# commit %s lib_source_stamp %s" % (commit, build.source_stamp()))
+    say("# tools/bench_predictor.py --device-tiler --runs %d%s: predict_file wall time without the HDF5 write, patch 24, res x2, batch 8, "
+        "8+4 ResBlocks, %s, %s" % (runs, " --bf16" if dtype != "float32" else "", dtype, torch.cuda.get_device_name(0)))
+    legs = LEGS_SINGLE
+    if world > 1:
+        legs = LEGS_DP
+        ndev = torch.cuda.device_count()
+        say("# %d ranks on %d device(s), backend %s%s" % (world, min(ndev, world), torch.distributed.get_backend(),
+                                                          "" if ndev >= world else ": OVERSUBSCRIBED, no speed claim"))
     predictor.h5io = type("NoWrite", (), {"append_datasets": staticmethod(lambda *a, **k: None)})
     with tempfile.TemporaryDirectory() as tmp:
         synth = os.path.join(tmp, "synthetic_4x100.h5")
-        _synthetic_file(synth)
+        if world > 1:                                          # one file for all ranks: rank 0 writes it where the others find it
+            synth = os.path.join(tempfile.gettempdir(), "fdn_bench_synthetic_4x100_%s.h5" % os.environ.get("MASTER_PORT", "0"))
+        if rank == 0:
+            _synthetic_file(synth)
+        parallel.barrier()
         for name, path, patches in (("example_data.h5 (1 x 42x38x36)", os.path.join(ROOT, "tests", "golden", "data", "example_data.h5"), 12),
                                     ("synthetic (4 x 100^3)", synth, 4 * 125)):
-            times = {"host": [], "device": []}
-            for r in range(runs + 1):                          # run 0 warms both legs up (file decode, pack streams, staging buffers)
-                for leg in ("host", "device"):
-                    torch.cuda.synchronize()
+            times = dict((leg[0], []) for leg in legs)
+            for r in range(runs + 1):                          # run 0 warms every leg up (file decode, pack streams, staging buffers)
+                for leg, device, fin in legs:
+                    if fin is None:
+                        os.environ.pop("FDN_DEVICE_FINISH", None)
+                    else:
+                        os.environ["FDN_DEVICE_FINISH"] = fin
+                    torch.cuda.synchronize(); parallel.barrier()
                     t0 = time.perf_counter()
                     vols = predictor.predict_file(net, path, os.path.join(tmp, "unused.h5"), 24, 2, batch_size=8, verbose=False,
-                                                  device_tiler=(leg == "device"))
-                    torch.cuda.synchronize()
+                                                  device_tiler=device)
+                    torch.cuda.synchronize(); parallel.barrier()
                     dt = time.perf_counter() - t0
                     if r:
                         times[leg].append(dt)
                     del vols
-            for leg in ("host", "device"):
+            os.environ.pop("FDN_DEVICE_FINISH", None)
+            for leg, _, _ in legs:
                 t = times[leg]
                 med = statistics.median(t)
-                print("%-32s %-6s tiler: runs %s s; median %.3f s (min %.3f .. max %.3f) = %.1f patches/s"
-                      % (name, leg, " ".join("%.3f" % x for x in t), med, min(t), max(t), patches / med))
-            print("%-32s device / host median wall time: %.3f" % (name, statistics.median(times["device"]) / statistics.median(times["host"])))
+                say("%-32s %-22s tiler: runs %s s; median %.3f s (min %.3f .. max %.3f) = %.1f patches/s"
+                    % (name, leg, " ".join("%.3f" % x for x in t), med, min(t), max(t), patches / med))
+            base = statistics.median(times[legs[0][0]])
+            for leg, _, _ in legs[1:]:
+                say("%-32s %s / %s median wall time: %.3f" % (name, leg, legs[0][0], statistics.median(times[leg]) / base))
+        parallel.barrier()
+        if world > 1 and rank == 0:
+            os.remove(synth)
 
 
 def main():
-    rank, world, local = parallel.init_from_env()
-    torch.cuda.set_device(local)
+    ndev = max(torch.cuda.device_count(), 1)
+    # more ranks than devices (a self-test on one GPU): gloo, RCCL refuses two ranks on one device
+    rank, world, local = parallel.init_from_env(backend="gloo" if int(os.environ.get("WORLD_SIZE", "1")) > ndev else None)
+    torch.cuda.set_device(local % ndev)
     dtype = "bfloat16" if "--bf16" in sys.argv else "float32"
     net = predictor.prepare_network(24, 2, 8, 4, dtype=dtype)
     if "--device-tiler" in sys.argv:
-        if world != 1:
-            raise SystemExit("--device-tiler measures the single-process path")
         runs = int(sys.argv[sys.argv.index("--runs") + 1]) if "--runs" in sys.argv else 3
-        device_tiler_leg(net, dtype, max(runs, 3))
+        device_tiler_leg(net, dtype, max(runs, 3), rank, world)
         return
     cases = []
     ds = data.ImageDataset()
