@@ -563,6 +563,13 @@ template <typename T>
 int fdn_head_dgrad_launch(const float* dz, const float* w, const T* y_prev, int act, float alpha, T* dz_prev, float* bpart, int N,
                           int D, int H, int W, int lddz, int dz_coff, hipStream_t s, const uint16_t* ymask) {
     const int ntd = (D + H_TD - 1) / H_TD, nth = (H + H_TH - 1) / H_TH, ntw = (W + H_TW - 1) / H_TW;
+#ifdef FDN_TEST_HOOKS
+    {   // walk: the longest tile walk of any workgroup, in the classes 1 / 2 / >= 3 (one tile; the halo double buffer used once; its parity flipped back)
+        const int tiles = N * ntd * nth * ntw, grid = fdn_head_dgrad_blocks(N, D, H, W), walk = (tiles + grid - 1) / grid;
+        FDN_PLAN("fam=head_dgrad op=dgrad dt=%s N=%d D=%d H=%d W=%d mask=%d walk=%d grid=%d tiles=%d cus=%d", sizeof(T) == 2 ? "bf16" : "f32", N, D, H,
+                 W, ymask != nullptr, walk < 3 ? walk : 3, grid, tiles, fdn_plan_cus());
+    }
+#endif
     hipLaunchKernelGGL(head_dgrad_kernel<T>, dim3((unsigned)fdn_head_dgrad_blocks(N, D, H, W)), dim3(256), 0, s, dz, w, y_prev, act,
                        alpha, dz_prev, bpart, N, D, H, W, ntd, nth, ntw, lddz, dz_coff, ymask);
     FDN_CHECK_LAUNCH("head_dgrad_kernel");
@@ -899,6 +906,13 @@ template <typename T>
 int fdn_head_wgrad_launch(const T* x, const float* dz, float* partial, int N, int D, int H, int W, int lddz, int dz_coff,
                           hipStream_t s) {
     const int ntd = (D + H_TD - 1) / H_TD, nth = (H + H_TH - 1) / H_TH, ntw = (W + H_TW - 1) / H_TW;
+#ifdef FDN_TEST_HOOKS
+    {   // walk: as in fdn_head_dgrad_launch
+        const int tiles = N * ntd * nth * ntw, grid = fdn_head_wgrad_blocks(N, D, H, W, (int)sizeof(T)), walk = (tiles + grid - 1) / grid;
+        FDN_PLAN("fam=head_wgrad op=wgrad dt=%s N=%d D=%d H=%d W=%d walk=%d grid=%d tiles=%d cus=%d", sizeof(T) == 2 ? "bf16" : "f32", N, D, H, W,
+                 walk < 3 ? walk : 3, grid, tiles, fdn_plan_cus());
+    }
+#endif
     hipLaunchKernelGGL(head_wgrad_kernel<T>, dim3((unsigned)fdn_head_wgrad_blocks(N, D, H, W, (int)sizeof(T))), dim3(256), 0, s, x, dz, partial, N, D,
                        H, W, ntd, nth, ntw, lddz, dz_coff);
     FDN_CHECK_LAUNCH("head_wgrad_kernel");

@@ -11,6 +11,7 @@ family, tile / variant, grid against tiles.  Here:
   2. PLAN_CASES (below, data) names for every key one case -- the cheapest product shape that reaches it;
   3. each case runs its entry point at that shape, confirms it reaches its key, and compares the result with float64 at sampled voxels
      (fp32: 2e-5 of scale; bf16: one bf16 ulp; weight gradients: 1e-5 of sum |x||dz| on picked rows);
+     the two head gradients (fam=head_dgrad, head_wgrad: `walk` = the longest tile walk of a workgroup, 1 / 2 / >= 3) against tests/_head_ref.py;
   4. a product shape that reaches a key with no case fails test_every_product_plan_has_a_case, naming the key and the shapes.
 
 After a planner change, regenerate the table: `python tests/test_gpu_plan_coverage.py` on a GPU prints it."""
@@ -26,6 +27,7 @@ import numpy as np
 import pytest
 import torch
 
+import _head_ref as HR
 from oracle import flownet_oracle as O
 from test_gpu_fullsize import gather_rows, ref_dgrad, ref_forward, ref_wgrad_rows, sample_voxels
 
@@ -183,6 +185,16 @@ def _wgrad_check(x, dz, dw, name):
         name, float((np.abs(got - refw) / np.maximum(cond, 1e-300)).max()))
 
 
+def sign_mask_words(y, planar):
+    """The sign mask of an (N,D,H,W,64) activation as the forward kernels write it: bit c % 16 of int16 word c / 16 = (y[v][c] > 0);
+    planar (fp32 storage): [word][voxel], else (bf16 storage): [voxel][word]."""
+    N, D, H, W = y.shape[:4]
+    bits = (y.float() > 0).view(N * D * H * W, 4, 16).to(torch.int32)
+    words = (bits << torch.arange(16, device=y.device, dtype=torch.int32)).sum(dim=2)
+    words = torch.where(words >= 32768, words - 65536, words).to(torch.int16)
+    return words.t().contiguous() if planar else words.view(N, D, H, W, 4).contiguous()
+
+
 def run_case(key, case):
     """Run the case's entry point at its shape under the recorder; returns the plan keys it reached.  Asserts float64 parity."""
     dt, algo_name, N, D, H, W, nl = case
@@ -215,6 +227,24 @@ def run_case(key, case):
             o.conv3d_fwd(x, w, b, ops.ACT_NONE, out=pred, ldy=3, y_coff=1, algo=algo)
             ref = ref_forward(x, w.double().cpu().numpy(), pts, dims)[:, 0] + float(b[0])
             _close(gather_rows(pred, pts)[:, 1], ref, False, name)
+        elif fam == "head_dgrad":                           # as the product calls it: the (N,V,3) prediction gradient, ReLU, the producer's bias gradient
+            y, w, dpred = rnd(N, D, H, W, 64), wts(3, 3, 3, 64, 1), rnd(N, D, H, W, 3, dtype=torch.float32)
+            mask = sign_mask_words(y, planar=not bf) if "mask=1" in key else None
+            db = torch.full((64,), float("nan"), device="cuda")
+            out = o.conv_cout1_dgrad_folded(dpred, w, dims, None if mask is not None else y, ops.ACT_RELU, lddz=3, dz_coff=1, dbias_prev=db, mask=mask)
+            A = gather_rows(HR.head_fold(dpred[..., 1], dims), pts)
+            _close(gather_rows(out, pts), (A @ w.double().cpu().numpy().reshape(27, 64)) * (gather_rows(y, pts) > 0), bf, name)
+            if not bf:                                       # (bf16 storage: the kernel sums the values BEFORE they are rounded to bf16; test_gpu_head_walks.py has the float64 sums)
+                o64 = out.double().reshape(-1, 64)
+                assert ((db.double() - o64.sum(dim=0)).abs() <= 1e-5 * o64.abs().sum(dim=0) + 1e-30).all(), "%s: producer bias gradient" % name
+        elif fam == "head_wgrad":
+            x, dpred = rnd(N, D, H, W, 64), rnd(N, D, H, W, 3, dtype=torch.float32)
+            dw, db = o.conv3d_wgrad(x, dpred, 3, 64, 1, want_bias=True, lddz=3, dz_coff=1)
+            refw, cond = HR.head_wgrad_ref(x, dpred[..., 1]), HR.head_wgrad_bound(x, dpred[..., 1])      # (all 27 x 64 rows: the reference has them anyway)
+            assert ((dw.double() - refw).abs() <= 1e-5 * cond + 1e-30).all(), "%s: %.3e of bound" % (
+                name, float(((dw.double() - refw).abs() / cond.clamp_min(1e-300)).max()))
+            dz64 = dpred[..., 1].double()
+            assert abs(float(db[0]) - float(dz64.sum())) <= 1e-5 * float(dz64.abs().sum()), "%s: bias gradient" % name
         elif fam == "cin3_fwd":
             x, w, b = rnd(N, D, H, W, 3), wts(3, 3, 3, 3, 64), wts(64)
             y = o.conv3d_fwd(x, w, b, ops.ACT_RELU, algo=algo)
@@ -400,6 +430,11 @@ PLAN_CASES = {
     'fdn_conv3d_fwd_bf16 fam=head_fwd op=fwd dt=bf16 iters=33 rounds=several tail=partial': ('bf16', 'auto', 2, 128, 128, 128, 0),
     'fdn_conv3d_fwd_bf16 fam=head_fwd op=fwd dt=bf16 iters=48 rounds=several tail=full': ('bf16', 'auto', 3, 128, 128, 128, 0),
     'fdn_conv3d_fwd_bf16 fam=head_fwd op=fwd dt=bf16 iters=66 rounds=several tail=partial': ('bf16', 'auto', 4, 128, 128, 128, 0),
+    'fdn_conv3d_wgrad fam=head_wgrad op=wgrad dt=f32 walk=1 rounds=one tail=partial': ('f32', 'auto', 1, 16, 16, 16, 0),
+    'fdn_conv3d_wgrad fam=head_wgrad op=wgrad dt=f32 walk=1 rounds=several tail=partial': ('f32', 'auto', 1, 48, 48, 48, 0),
+    'fdn_conv3d_wgrad fam=head_wgrad op=wgrad dt=f32 walk=2 rounds=several tail=partial': ('f32', 'auto', 2, 48, 48, 48, 0),
+    'fdn_conv3d_wgrad fam=head_wgrad op=wgrad dt=f32 walk=3 rounds=several tail=full': ('f32', 'auto', 1, 128, 128, 128, 0),
+    'fdn_conv3d_wgrad fam=head_wgrad op=wgrad dt=f32 walk=3 rounds=several tail=partial': ('f32', 'auto', 3, 48, 48, 48, 0),
     'fdn_conv3d_wgrad fam=wgrad_direct op=wgrad dt=f32 splits=108 rounds=several tail=full': ('f32', 'direct', 2, 24, 24, 24, 0),
     'fdn_conv3d_wgrad fam=wgrad_direct op=wgrad dt=f32 splits=128 rounds=several tail=full': ('f32', 'direct', 1, 32, 32, 32, 0),
     'fdn_conv3d_wgrad fam=wgrad_direct op=wgrad dt=f32 splits=16 rounds=one tail=full': ('f32', 'direct', 1, 16, 16, 16, 0),
@@ -414,6 +449,8 @@ PLAN_CASES = {
     'fdn_conv3d_wgrad_batch fam=wgrad_wino_batch op=wgrad dt=f32 layers=8 splits=8 rounds=one tail=full': ('f32', 'auto', 1, 24, 24, 24, 8),
     'fdn_conv3d_wgrad_batch fam=wgrad_wino_batch op=wgrad dt=f32 layers=9 splits=7 rounds=one tail=full': ('f32', 'auto', 7, 24, 24, 24, 11),
     'fdn_conv3d_wgrad_batch fam=wgrad_wino_batch op=wgrad dt=f32 layers=9 splits=7 rounds=one tail=partial': ('f32', 'auto', 1, 24, 24, 24, 11),
+    'fdn_conv3d_wgrad_bf16 fam=head_wgrad op=wgrad dt=bf16 walk=3 rounds=several tail=full': ('bf16', 'auto', 3, 128, 128, 128, 0),
+    'fdn_conv3d_wgrad_bf16 fam=head_wgrad op=wgrad dt=bf16 walk=3 rounds=several tail=partial': ('bf16', 'auto', 1, 128, 128, 128, 0),
     'fdn_conv3d_wgrad_bf16 fam=wgrad_bf16_dma op=wgrad dt=bf16 splits=168 nseg=4 rounds=several tail=partial': ('bf16', 'auto', 1, 128, 128, 128, 0),
     'fdn_conv3d_wgrad_bf16_batch fam=wgrad_bf16_batch op=wgrad dt=bf16 layers=4 splits=40 nseg=11 rounds=several tail=partial': ('bf16', 'auto', 1, 32, 32, 32, 8),
     'fdn_conv3d_wgrad_bf16_batch fam=wgrad_bf16_batch op=wgrad dt=bf16 layers=4 splits=40 nseg=3 rounds=several tail=partial': ('bf16', 'auto', 4, 32, 32, 32, 8),
@@ -512,6 +549,17 @@ PLAN_CASES = {
     'fdn_conv64_fwd_mask fam=wino2d op=fwd dt=f32 hm=4 split=0 mb=1 tile=8x1x2 ymask=1 fmask=0 nsrc=1 rounds=several tail=partial': ('f32', 'auto', 8, 24, 24, 24, 0),
     'fdn_conv64_fwd_mask fam=wino2d op=fwd dt=f32 hm=4 split=0 mb=2 tile=16x1x2 ymask=1 fmask=0 nsrc=1 rounds=several tail=partial': ('f32', 'auto', 2, 48, 48, 48, 0),
     'fdn_conv64_fwd_mask fam=wino2d op=fwd dt=f32 hm=4 split=0 mb=2 tile=32x1x1 ymask=1 fmask=0 nsrc=1 rounds=several tail=full': ('f32', 'auto', 1, 128, 128, 128, 0),
+    'fdn_conv_cout1_dgrad_folded fam=head_dgrad op=dgrad dt=f32 mask=0 walk=1 rounds=one tail=partial': ('f32', 'direct', 1, 16, 16, 16, 0),
+    'fdn_conv_cout1_dgrad_folded fam=head_dgrad op=dgrad dt=f32 mask=0 walk=1 rounds=several tail=partial': ('f32', 'direct', 1, 48, 48, 48, 0),
+    'fdn_conv_cout1_dgrad_folded fam=head_dgrad op=dgrad dt=f32 mask=0 walk=2 rounds=several tail=partial': ('f32', 'direct', 3, 48, 48, 48, 0),
+    'fdn_conv_cout1_dgrad_folded fam=head_dgrad op=dgrad dt=f32 mask=0 walk=3 rounds=several tail=full': ('f32', 'direct', 1, 128, 128, 128, 0),
+    'fdn_conv_cout1_dgrad_folded fam=head_dgrad op=dgrad dt=f32 mask=0 walk=3 rounds=several tail=partial': ('f32', 'direct', 5, 48, 48, 48, 0),
+    'fdn_conv_cout1_dgrad_folded_bf16_mask fam=head_dgrad op=dgrad dt=bf16 mask=1 walk=3 rounds=several tail=full': ('bf16', 'auto', 1, 128, 128, 128, 0),
+    'fdn_conv_cout1_dgrad_folded_mask fam=head_dgrad op=dgrad dt=f32 mask=1 walk=1 rounds=one tail=partial': ('f32', 'auto', 1, 16, 16, 16, 0),
+    'fdn_conv_cout1_dgrad_folded_mask fam=head_dgrad op=dgrad dt=f32 mask=1 walk=1 rounds=several tail=partial': ('f32', 'auto', 1, 48, 48, 48, 0),
+    'fdn_conv_cout1_dgrad_folded_mask fam=head_dgrad op=dgrad dt=f32 mask=1 walk=2 rounds=several tail=partial': ('f32', 'auto', 3, 48, 48, 48, 0),
+    'fdn_conv_cout1_dgrad_folded_mask fam=head_dgrad op=dgrad dt=f32 mask=1 walk=3 rounds=several tail=full': ('f32', 'auto', 1, 128, 128, 128, 0),
+    'fdn_conv_cout1_dgrad_folded_mask fam=head_dgrad op=dgrad dt=f32 mask=1 walk=3 rounds=several tail=partial': ('f32', 'auto', 5, 48, 48, 48, 0),
     'fdn_upsample_trilinear_bwd fam=upsample_bwd op=bwd dt=f32 R=2 hb=2 rounds=several tail=full': ('f32', 'auto', 8, 24, 24, 24, 0),
     'fdn_upsample_trilinear_bwd fam=upsample_bwd op=bwd dt=f32 R=2 hb=2 rounds=several tail=partial': ('f32', 'auto', 1, 24, 24, 24, 0),
     'fdn_upsample_trilinear_bwd fam=upsample_bwd op=bwd dt=f32 R=4 hb=2 rounds=several tail=full': ('f32', 'auto', 1, 32, 32, 32, 0),
