@@ -346,8 +346,166 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return s;   // valid in thread 0
 }
 
-__global__ __launch_bounds__(256) void mask_sums_kernel(const float* __restrict__ mask, float* __restrict__ scratch, int64_t V) {
+// ---------------------------------------------------------------------------------------------
+// Whole-volume evaluation (fdn_volume_metrics): a path of the three loss kernels selected by one by-value int, `vm` (0: the training
+// paths above and below, untouched; else VM_MODE(pass, pred_is_f64, per_frame_mask)).  The operands travel in the kernels' existing
+// parameters -- four bytes more per launch: the training call is bound by its launches -- and each kernel views them as a VolumeMetrics.  pred (F,3,X,Y,Z) fp32 or float64, truth (F,3,X,Y,Z), mask
+// (mask_frames,X,Y,Z); everything is summed in double.  part: per-block partials (F, gridDim.x, 26), every column written by
+// exactly one pass; loss_finalize_kernel adds them over the blocks in a fixed order.
+//   mask_sums_kernel  pass 1: columns 0-2 (sum m, sum nf, sum fl)
+//   loss_main_kernel  pass 1: columns 3-8 (q, corr, e_c^2)      pass 2: columns 9-10 (d: the pass that gathers the stencil neighbours)
+//                     pass 3 + c: columns 11 + 5c .. 15 + 5c (the regression moments of component c over the fl voxels)
+// One pass holding all 26 double accumulators would take loss_main_kernel past 72 VGPRs and the training paths from seven waves per
+// SIMD to fewer; each column is accumulated by the same threads in the same order whatever the grouping.
+// ---------------------------------------------------------------------------------------------
+struct VolumeMetrics {
+    const void* pred;
+    const float* truth;
+    const float* mask;
+    double* part;
+    double* out;
+    int32_t pass, pred_is_f64, per_frame_mask, X, Y, Z;
+};
+#define VM_MODE(pass, f64, per_frame) ((pass) | ((f64) << 8) | ((per_frame) << 9))
+#define VM_PASS(vm) ((vm) & 0xff)
+#define VM_F64(vm) (((vm) >> 8) & 1)
+#define VM_PER_FRAME(vm) (((vm) >> 9) & 1)
+
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const int wv = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[wv] = v;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s += red[k];
+    return s;   // valid in thread 0
+}
+
+__device__ __forceinline__ double vm_pred(const VolumeMetrics& a, int64_t i) {
+    return a.pred_is_f64 ? ((const double*)a.pred)[i] : (double)((const float*)a.pred)[i];
+}
+
+// (Da e)[k] = e[clamp(k-1)] - e[clamp(k+1)], e = pred - truth, for the voxel at offset i of a component plane starting at `base`,
+// at position p of an axis of extent n and voxel stride s.  Both neighbours stay inside the plane; 0 on an axis of extent 1.
+__device__ __forceinline__ double vm_axis_diff(const VolumeMetrics& a, int64_t base, int64_t i, int p, int n, int64_t s) {
+    const int64_t lo = base + i - (p > 0 ? s : 0), hi = base + i + (p < n - 1 ? s : 0);
+    return (vm_pred(a, lo) - (double)a.truth[lo]) - (vm_pred(a, hi) - (double)a.truth[hi]);
+}
+
+__device__ __forceinline__ void volume_mask_sums(const VolumeMetrics& a, double* red) {
+    const int f = blockIdx.y;
+    const int64_t V = (int64_t)a.X * a.Y * a.Z;
+    const float* mask = a.mask + (a.per_frame_mask ? (int64_t)f * V : 0);
+    double sm = 0.0, snf = 0.0, sfl = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (int64_t)gridDim.x * blockDim.x) {
+        const float m = mask[i];
+        sm += (double)m;
+        snf += m < 0.5f ? 1.0 : 0.0;
+        sfl += m == 1.0f ? 1.0 : 0.0;
+    }
+    const double s0 = block_sum_d(sm, red);
+    const double s1 = block_sum_d(snf, red);
+    const double s2 = block_sum_d(sfl, red);
+    if (threadIdx.x == 0) {
+        double* part = a.part + ((size_t)f * gridDim.x + blockIdx.x) * 26;
+        part[0] = s0; part[1] = s1; part[2] = s2;
+    }
+}
+
+__device__ __forceinline__ void volume_main(const VolumeMetrics& a, double* red) {
+    const int f = blockIdx.y;
+    const int64_t YZ = (int64_t)a.Y * a.Z, V = (int64_t)a.X * YZ;
+    const float* mask = a.mask + (a.per_frame_mask ? (int64_t)f * V : 0);
+    double* part = a.part + ((size_t)f * gridDim.x + blockIdx.x) * 26;
+    const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    if (a.pass == 1) {
+        const int64_t bu = (int64_t)f * 3 * V, bv = bu + V, bw = bv + V;
+        double sqm = 0.0, sqn = 0.0, srel = 0.0, seu = 0.0, sev = 0.0, sew = 0.0;
+        for (int64_t i = first; i < V; i += step) {
+            const float mf = mask[i];
+            const double m = (double)mf;
+            const bool nf = mf < 0.5f, fl = mf == 1.0f;
+            const double tu = (double)a.truth[bu + i], tv = (double)a.truth[bv + i], tw = (double)a.truth[bw + i];
+            const double eu = vm_pred(a, bu + i) - tu, ev = vm_pred(a, bv + i) - tv, ew = vm_pred(a, bw + i) - tw;
+            const double qu = eu * eu, qv = ev * ev, qw = ew * ew;
+            const double q = qu + qv + qw;
+            sqm += q * m;
+            sqn += nf ? q : 0.0;
+            // relative error (loss_utils.py:64-92) in double; rint == round-half-to-even == tf.round
+            const double diff = sqrt(q);
+            const double actual = sqrt(tu * tu + tv * tv + tw * tw);
+            double rel = diff / (actual + 1e-5);
+            rel = fmin(fmax(rel, 0.0), 1.0);
+            double corr = actual != 0.0 ? rel : diff;
+            corr = rint(corr * 1e4) / 1e4;
+            srel += fl ? corr : 0.0;
+            seu += fl ? qu : 0.0;
+            sev += fl ? qv : 0.0;
+            sew += fl ? qw : 0.0;
+        }
+        const double r3 = block_sum_d(sqm, red), r4 = block_sum_d(sqn, red), r5 = block_sum_d(srel, red);
+        const double r6 = block_sum_d(seu, red), r7 = block_sum_d(sev, red), r8 = block_sum_d(sew, red);
+        if (threadIdx.x == 0) { part[3] = r3; part[4] = r4; part[5] = r5; part[6] = r6; part[7] = r7; part[8] = r8; }
+        return;
+    }
+    if (a.pass == 2) {                                               // the pass that gathers the stencil neighbours
+        const int64_t bu = (int64_t)f * 3 * V, bv = bu + V, bw = bv + V;
+        double sdm = 0.0, sdn = 0.0;
+        for (int64_t i = first; i < V; i += step) {
+            const float mf = mask[i];
+            const unsigned iv = (unsigned)i;                       // V < 2^31 (fdn_volume_metrics)
+            const unsigned r = iv / (unsigned)a.Z;
+            const int pz = (int)(iv - r * (unsigned)a.Z), py = (int)(r % (unsigned)a.Y), px = (int)(r / (unsigned)a.Y);
+            const double gu = vm_axis_diff(a, bu, i, px, a.X, YZ);
+            const double gv = vm_axis_diff(a, bv, i, py, a.Y, a.Z);
+            const double gw = vm_axis_diff(a, bw, i, pz, a.Z, 1);
+            const double d = gu * gu + gv * gv + gw * gw;
+            sdm += d * (double)mf;
+            sdn += mf < 0.5f ? d : 0.0;
+        }
+        const double r9 = block_sum_d(sdm, red), r10 = block_sum_d(sdn, red);
+        if (threadIdx.x == 0) { part[9] = r9; part[10] = r10; }
+        return;
+    }
+    const int c = a.pass - 3;                                       // the regression moments of one component over the fl voxels
+    const int64_t base = ((int64_t)f * 3 + c) * V;
+    double st = 0.0, sp = 0.0, stt = 0.0, spp = 0.0, stp = 0.0;
+    for (int64_t i = first; i < V; i += step) {
+        if (mask[i] == 1.0f) {
+            const double t = (double)a.truth[base + i], p = vm_pred(a, base + i);
+            st += t; sp += p; stt += t * t; spp += p * p; stp += t * p;
+        }
+    }
+    const double r0 = block_sum_d(st, red), r1 = block_sum_d(sp, red), r2 = block_sum_d(stt, red);
+    const double r3 = block_sum_d(spp, red), r4 = block_sum_d(stp, red);
+    if (threadIdx.x == 0) {
+        double* o = part + 11 + 5 * c;
+        o[0] = r0; o[1] = r1; o[2] = r2; o[3] = r3; o[4] = r4;
+    }
+}
+
+// one wave per frame, column by column: lane t adds the partials of blocks t, t + 64, ... in block order, then the shuffle tree
+__device__ __forceinline__ void volume_finalize(const VolumeMetrics& a, int nblk) {
+    const int f = blockIdx.x;
+    const double* part = a.part + (size_t)f * nblk * 26;
+    for (int col = 0; col < 26; ++col) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < nblk; b += 64) s += part[(size_t)b * 26 + col];
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        if (threadIdx.x == 0) a.out[(size_t)f * 26 + col] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void mask_sums_kernel(const float* __restrict__ mask, float* __restrict__ scratch, int64_t V,
+                                                         int vm) {
     __shared__ float red[4];
+    __shared__ double redd[4];
+    if (vm) {                                                        // scratch: the doubles of fdn_volume_metrics; V < 2^31 voxels per frame
+        volume_mask_sums(VolumeMetrics{nullptr, nullptr, mask, (double*)scratch, nullptr, VM_PASS(vm), 0, VM_PER_FRAME(vm), (int)V, 1, 1}, redd);
+        return;
+    }
     const int n = blockIdx.y;
     float sm = 0.f, snf = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (int64_t)gridDim.x * blockDim.x) {
@@ -394,8 +552,13 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
                                                          const float* __restrict__ vh, const float* __restrict__ wh,
                                                          const float* __restrict__ mask, float* __restrict__ scratch,
                                                          float* __restrict__ dpred, int64_t V, int D, int H, int W, float div_w,
-                                                         int nparts) {
+                                                         int nparts, int vm) {
     __shared__ float red[4];
+    __shared__ double redd[4];
+    if (vm) {                                                        // pred: fp32 or float64; uh: truth; scratch: doubles; D,H,W = X,Y,Z
+        volume_main(VolumeMetrics{pred, uh, mask, (double*)scratch, nullptr, VM_PASS(vm), VM_F64(vm), VM_PER_FRAME(vm), D, H, W}, redd);
+        return;
+    }
     const int n = blockIdx.y;
     const float inv_f = 1.f / (scratch[n * 8 + 0] + 1.f);
     const float inv_nf = 1.f / (scratch[n * 8 + 1] + 1.f);
@@ -483,7 +646,11 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
 // metric stays run-to-run identical (one THREAD per sample walked the 256 partials as a chain of dependent loads: 24 us).
 // nparts 3: out (N,4); nparts 5: out (N,5), column 4 = div_w * (sum m d / (sum m + 1) + sum nf d / (sum nf + 1)).
 __global__ __launch_bounds__(64) void loss_finalize_kernel(const float* __restrict__ scratch, float* __restrict__ out, int N, int nblk,
-                                                           int nparts, float div_w) {
+                                                           int nparts, float div_w, int vm) {
+    if (vm) {                                                        // scratch, out: the doubles of fdn_volume_metrics
+        volume_finalize(VolumeMetrics{nullptr, nullptr, nullptr, (double*)scratch, (double*)out, VM_PASS(vm), 0, 0, 0, 0, 0}, nblk);
+        return;
+    }
     const int n = blockIdx.x;
     const float* part = scratch + (size_t)N * 8 + (size_t)n * nblk * nparts;
     float sf = 0.f, sn = 0.f, sr = 0.f, sdf = 0.f, sdn = 0.f;
@@ -752,11 +919,11 @@ static int loss_launch(const char* who, const float* pred, const float* uh, cons
     if (e != hipSuccess) { fdn_set_error("%s: memset: %s", who, hipGetErrorString(e)); return FDN_ERR_HIP; }
     const int gx = grid_for(V, FDN_LOSS_BLOCKS);
     // (16 blocks per sample: with 256 the 2 x 256 x N atomics on 2 N words took longer than reading the mask -- 29 us at cfg2)
-    hipLaunchKernelGGL(mask_sums_kernel, dim3(gx < 16 ? gx : 16, N), dim3(256), 0, s, mask, scratch, V);
+    hipLaunchKernelGGL(mask_sums_kernel, dim3(gx < 16 ? gx : 16, N), dim3(256), 0, s, mask, scratch, V, 0);
     FDN_CHECK_LAUNCH("mask_sums_kernel");
-    hipLaunchKernelGGL(loss_main_kernel, dim3(gx, N), dim3(256), 0, s, pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts);
+    hipLaunchKernelGGL(loss_main_kernel, dim3(gx, N), dim3(256), 0, s, pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts, 0);
     FDN_CHECK_LAUNCH("loss_main_kernel");
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(N), dim3(64), 0, s, (const float*)scratch, out, N, gx, nparts, div_w);
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(N), dim3(64), 0, s, (const float*)scratch, out, N, gx, nparts, div_w, 0);
     FDN_CHECK_LAUNCH("loss_finalize_kernel");
     return FDN_OK;
 }
@@ -778,6 +945,34 @@ extern "C" int fdn_loss_metrics_div(const float* pred, const float* uh, const fl
                 (double)div_weight);
     return loss_launch("fdn_loss_metrics_div", pred, uh, vh, wh, mask, out, dpred, scratch, N, (int64_t)D * H * W, D, H, W, div_weight, 5,
                        stream);
+}
+
+extern "C" int fdn_volume_metrics(const void* pred, int pred_is_f64, const float* truth, const float* mask, int mask_frames,
+                                  double* out, double* scratch, int F, int X, int Y, int Z, void* stream) {
+    FDN_REQUIRE(pred, "fdn_volume_metrics: pred is NULL");
+    FDN_REQUIRE(truth, "fdn_volume_metrics: truth is NULL");
+    FDN_REQUIRE(mask, "fdn_volume_metrics: mask is NULL");
+    FDN_REQUIRE(out, "fdn_volume_metrics: out is NULL");
+    FDN_REQUIRE(scratch, "fdn_volume_metrics: scratch is NULL");
+    FDN_REQUIRE(F > 0 && X > 0 && Y > 0 && Z > 0, "fdn_volume_metrics: extents F=%d X=%d Y=%d Z=%d must be positive", F, X, Y, Z);
+    FDN_REQUIRE((int64_t)X * Y * Z <= (int64_t)INT32_MAX, "fdn_volume_metrics: X*Y*Z = %d x %d x %d voxels per frame exceed 2^31 - 1", X, Y,
+                Z);
+    FDN_REQUIRE(mask_frames == 1 || mask_frames == F, "fdn_volume_metrics: mask_frames=%d must be 1 or F=%d", mask_frames, F);
+    FDN_REQUIRE(pred_is_f64 == 0 || pred_is_f64 == 1, "fdn_volume_metrics: pred_is_f64=%d must be 0 or 1", pred_is_f64);
+    hipStream_t s = (hipStream_t)stream;
+    const int gx = grid_for((int64_t)X * Y * Z, FDN_LOSS_BLOCKS);
+    const int f64 = pred_is_f64, per_frame = mask_frames != 1 ? 1 : 0;
+    hipLaunchKernelGGL(mask_sums_kernel, dim3(gx, F), dim3(256), 0, s, mask, (float*)scratch, (int64_t)X * Y * Z, VM_MODE(1, 0, per_frame));
+    FDN_CHECK_LAUNCH("mask_sums_kernel (volume metrics)");
+    for (int pass = 1; pass <= 5; ++pass) {                              // columns 3-8, 9-10, then the five moments of u, v, w
+        hipLaunchKernelGGL(loss_main_kernel, dim3(gx, F), dim3(256), 0, s, (const float*)pred, truth, (const float*)nullptr,
+                           (const float*)nullptr, mask, (float*)scratch, (float*)nullptr, (int64_t)X * Y * Z, X, Y, Z, 0.f, 0,
+                           VM_MODE(pass, f64, per_frame));
+        FDN_CHECK_LAUNCH("loss_main_kernel (volume metrics)");
+    }
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(F), dim3(64), 0, s, (const float*)scratch, (float*)out, F, gx, 0, 0.f, VM_MODE(1, 0, 0));
+    FDN_CHECK_LAUNCH("loss_finalize_kernel (volume metrics)");
+    return FDN_OK;
 }
 
 extern "C" int fdn_l2_sumsq(const float* w, const uint8_t* is_kernel, int64_t n, float* out, void* stream) {

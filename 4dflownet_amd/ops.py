@@ -422,6 +422,53 @@ def _loss_metrics_div(pred, uh, vh, wh, mask, div_weight, want_grad, out, dpred,
     return out, (dpred if want_grad else None)
 
 
+VOLUME_METRICS_COLUMNS = 26           # FDN_VOLUME_METRICS_COLUMNS
+_volume_metrics_scratch = {}          # device -> float64 buffer of per-block partials, grown on demand
+
+
+def volume_metrics_scratch_doubles(F):
+    """FDN_VOLUME_METRICS_SCRATCH_DOUBLES(F)."""
+    return F * VOLUME_METRICS_COLUMNS * 256
+
+
+def volume_metrics(pred, truth, mask, out=None, scratch=None):
+    """The 26 sums per frame of a stitched prediction against the high-resolution truth (fdn_volume_metrics; the columns are
+    predictor.VOLUME_SUM_NAMES, predictor.metrics_from_sums turns them into metrics).  pred (F,3,X,Y,Z) fp32 or float64 -- what
+    predict_volume returns --, truth (F,3,X,Y,Z) fp32 in the same units, mask (1,X,Y,Z) or (F,X,Y,Z) fp32.  Returns out, the (F,26)
+    float64 device tensor.  The per-block partials live in one buffer per device kept on this module (calls on one device are ordered
+    by its stream); scratch= (float64, volume_metrics_scratch_doubles(F) elements) replaces it."""
+    if pred.dim() != 5 or pred.shape[1] != 3:
+        raise FdnError("volume_metrics: pred must be (F,3,X,Y,Z), got %s" % (tuple(pred.shape),))
+    if pred.dtype not in (torch.float32, torch.float64):
+        raise FdnError("volume_metrics: pred must be float32 or float64 (got %s)" % pred.dtype)
+    F, _, X, Y, Z = pred.shape
+    if tuple(truth.shape) != tuple(pred.shape):
+        raise FdnError("volume_metrics: truth must be %s like pred, got %s" % (tuple(pred.shape), tuple(truth.shape)))
+    if mask.dim() != 4 or tuple(mask.shape[1:]) != (X, Y, Z) or mask.shape[0] not in (1, F):
+        raise FdnError("volume_metrics: mask must be (1,%d,%d,%d) or (%d,%d,%d,%d), got %s" % (X, Y, Z, F, X, Y, Z, tuple(mask.shape)))
+    p_pred = _p64(pred, "pred") if pred.dtype == torch.float64 else _p(pred, "pred")
+    p_truth, p_mask = _p(truth, "truth"), _p(mask, "mask")
+    if truth.dtype != torch.float32 or mask.dtype != torch.float32:
+        raise FdnError("volume_metrics: truth and mask must be float32 (got %s, %s)" % (truth.dtype, mask.dtype))
+    if truth.device != pred.device or mask.device != pred.device:
+        raise FdnError("volume_metrics: pred, truth and mask must live on one device")
+    if out is None:
+        out = torch.empty((F, VOLUME_METRICS_COLUMNS), device=pred.device, dtype=torch.float64)
+    elif tuple(out.shape) != (F, VOLUME_METRICS_COLUMNS) or out.device != pred.device:
+        raise FdnError("volume_metrics: out must be (%d,%d) on %s, got %s on %s" % (F, VOLUME_METRICS_COLUMNS, pred.device,
+                                                                                  tuple(out.shape), out.device))
+    need = volume_metrics_scratch_doubles(F)
+    if scratch is None:
+        scratch = _volume_metrics_scratch.get(pred.device)
+        if scratch is None or scratch.numel() < need:
+            scratch = _volume_metrics_scratch[pred.device] = torch.empty((need,), device=pred.device, dtype=torch.float64)
+    elif scratch.numel() < need or scratch.device != pred.device:
+        raise FdnError("volume_metrics: scratch needs %d float64 elements on %s" % (need, pred.device))
+    check(_lib.load().fdn_volume_metrics(p_pred, int(pred.dtype == torch.float64), p_truth, p_mask, mask.shape[0], _p64(out, "out"),
+                                         _p64(scratch, "scratch"), F, X, Y, Z, _stream()), "fdn_volume_metrics")
+    return out
+
+
 def l2_sumsq(w_flat, is_kernel, out=None):
     if out is None:
         out = torch.empty((1,), device=w_flat.device, dtype=torch.float32)

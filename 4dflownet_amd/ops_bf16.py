@@ -8,7 +8,7 @@ import torch
 from . import _lib
 from ._lib import FdnError, check
 from .ops import (ACT_NONE, ACT_RELU, ACT_LEAKY, LEAKY_ALPHA, _stream, _volume_geometry, loss_metrics, l2_sumsq, adam_step,  # noqa: F401
-                  stitch_patches, pack_patch_cores)
+                  stitch_patches, pack_patch_cores, volume_metrics)
 
 BF16 = torch.bfloat16
 ACT_DTYPE = BF16

@@ -295,16 +295,21 @@ def _recv_cores(network, shapes):
 
 
 def _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size, round_small_values, verbose,
-                         frames_per_group):
+                         frames_per_group, on_group=None, device_finish=None):
     """predict_file with the tiler on the device: rows in groups whose frames and stitched output fit DEVICE_TILER_GROUP_BYTES (or
     frames_per_group rows), one predict_volume per group, de-normalised and zeroed inside its stitch launches (frame_scale); the
     finished float64 group travels to pinned host memory on the copy stream while the next group computes and is then appended exactly
     as on the host path.  FDN_DEVICE_FINISH=0: the stitched group travels as fp32 and is finished on the host (A/B timing).
     Data-parallel: every group's patch list is split with shard_bounds; rank r > 0 loads the rows its shard touches, runs
     predict_cores and sends its one buffer of cores to rank 0, which stitches (and finishes) its own batches directly, posts the
-    receives after its own shard (see predict_patches), and stitches every peer's buffer with side 0 at that peer's first patch."""
+    receives after its own shard (see predict_patches), and stitches every peer's buffer with side 0 at that peer's first patch.
+    on_group(rows, vol): called on rank 0 for every group once it is stitched (the peers' cores included), before the copy-out, with the
+    row numbers and the group's (len(rows),3,X*R,Y*R,Z*R) device tensor; what it queues on the current stream runs before the next group
+    (evaluate_file).  output_filepath=None: no staging buffers, no copy to the host and no file; nothing is returned per row.
+    device_finish: overrides FDN_DEVICE_FINISH."""
     world, rank = parallel.world_size(), parallel.rank()
-    device_finish = os.environ.get("FDN_DEVICE_FINISH", "1") not in ("", "0")
+    if device_finish is None:
+        device_finish = os.environ.get("FDN_DEVICE_FINISH", "1") not in ("", "0")
     dataset = ImageDataset()
     nr_rows = dataset.get_dataset_len(input_filepath)
     written = []
@@ -341,9 +346,11 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
                 _send_cores(network, predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=f0))
         return written
 
-    out_shape = (fpg, 3) + tuple(n * R for n in lr_shape)
-    stage, copy_stream = _volume_stage(network, out_shape, torch.float64 if device_finish else torch.float32)
-    main = torch.cuda.current_stream(network.device)
+    write = output_filepath is not None
+    if write:
+        out_shape = (fpg, 3) + tuple(n * R for n in lr_shape)
+        stage, copy_stream = _volume_stage(network, out_shape, torch.float64 if device_finish else torch.float32)
+        main = torch.cuda.current_stream(network.device)
 
     def finish(job):
         ev, slot, rows, meta, t0, _keep = job
@@ -383,6 +390,10 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
         if peers:                                                      # posted after the own shard (see predict_patches)
             for r, cores in _recv_cores(network, peers).items():
                 network.ops.stitch_patches(cores, vol, 0, counts, bounds[r], frame_scale=scale)
+        if on_group is not None:
+            on_group(rows, vol)
+        if not write:
+            continue
         slot = k & 1                                                   # its previous user (group k - 2) was finished one turn ago
         copy_stream.wait_stream(main)
         with torch.cuda.stream(copy_stream):
@@ -393,7 +404,8 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
         if pending is not None:
             finish(pending)                                            # host work of group k - 1 behind the compute of group k
         pending = (ev, slot, rows, meta, t0, vol)
-    finish(pending)
+    if pending is not None:
+        finish(pending)
     return written
 
 
@@ -439,6 +451,115 @@ def predict_file(network, input_filepath, output_filepath, patch_size, res_incre
     return written
 
 
+# the columns of ops.volume_metrics (fdn_volume_metrics): sums over one frame; m the mask, nf = [m < 0.5], fl = [m == 1], e = prediction -
+# truth, q = |e|^2, corr the relative error of loss_utils.py:64-92, d the squared clamped central differences of e (the divergence term)
+VOLUME_SUM_NAMES = (("sum_m", "sum_nf", "sum_fl", "sum_q_m", "sum_q_nf", "sum_corr_fl", "sum_eu2_fl", "sum_ev2_fl", "sum_ew2_fl",
+                     "sum_d_m", "sum_d_nf") +
+                    tuple(n.replace("c", c) for c in "uvw" for n in ("sum_tc_fl", "sum_pc_fl", "sum_tc2_fl", "sum_pc2_fl", "sum_tcpc_fl")))
+METRIC_NAMES = (("mse", "rel_error", "div", "rmse_u", "rmse_v", "rmse_w", "rmse") + tuple("k_" + c for c in "uvw") +
+                tuple("b_" + c for c in "uvw") + tuple("r2_" + c for c in "uvw") + ("n_fluid",))
+
+
+def metrics_from_sums(sums):
+    """Per frame a dict of METRIC_NAMES from the (F,26) sums of ops.volume_metrics (VOLUME_SUM_NAMES), on the host in float64:
+    mse = S3/(S0+1) + S4/(S1+1) (TrainerController.py:101-107); rel_error = 100 S5/(S0+1) in % (loss_utils.py:97-101); div the divergence
+    term with the same two means; rmse_c = sqrt(S_{6+c}/S2) and rmse = sqrt((S6+S7+S8)/S2) over the fluid voxels (m == 1); k_c, b_c, r2_c
+    slope, intercept and R^2 of the least-squares line of prediction on truth over the fluid voxels; n_fluid = S2.  Without fluid voxels
+    the RMSEs are 0 and the regression values NaN; they are NaN as well when the truth has no variance the moments can resolve."""
+    sums = np.asarray(sums, dtype=np.float64).reshape(-1, len(VOLUME_SUM_NAMES))
+    nan = float("nan")
+    res = []
+    for S in sums:
+        n = S[2]
+        d = {"mse": S[3] / (S[0] + 1) + S[4] / (S[1] + 1), "rel_error": 100.0 * S[5] / (S[0] + 1),
+             "div": S[9] / (S[0] + 1) + S[10] / (S[1] + 1)}
+        for c, name in enumerate("uvw"):
+            d["rmse_" + name] = float(np.sqrt(S[6 + c] / n)) if n > 0 else 0.0
+        d["rmse"] = float(np.sqrt((S[6] + S[7] + S[8]) / n)) if n > 0 else 0.0
+        for c, name in enumerate("uvw"):
+            st, sp, stt, spp, stp = S[11 + 5 * c:16 + 5 * c]
+            k = b = r2 = nan
+            if n > 0:
+                sxx, syy, sxy = stt - st * st / n, spp - sp * sp / n, stp - st * sp / n
+                if sxx > 1e-12 * stt:          # below that the variance is the rounding of the moments' cancellation
+                    k = sxy / sxx
+                    b = sp / n - k * st / n
+                    r2 = sxy * sxy / (sxx * syy) if syy > 0 else nan
+            d["k_" + name], d["b_" + name], d["r2_" + name] = float(k), float(b), float(r2)
+        d["n_fluid"] = float(n)
+        res.append({key: float(d[key]) for key in METRIC_NAMES})
+    return res
+
+
+def write_metrics_csv(csv_path, metrics, first_row=0):
+    """One header line `row,` + METRIC_NAMES and one line per row; %.17g, so the numbers read back exactly."""
+    with open(csv_path, "w") as f:
+        f.write("row," + ",".join(METRIC_NAMES) + "\n")
+        for i, m in enumerate(metrics):
+            f.write("%d," % (first_row + i) + ",".join("%.17g" % m[key] for key in METRIC_NAMES) + "\n")
+
+
+def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase, batch_size=8, round_small_values=True,
+                  output_filepath=None, csv_path=None, frames_per_group=None, verbose=True, return_sums=False):
+    """Predict every row of the low-resolution file with the tiler on the device (_predict_file_device) and score the finished float64
+    prediction, in m/s, against u, v, w of the same row of the high-resolution file (m/s as well: nothing is rescaled), where the
+    prediction already is: ops.volume_metrics on every stitched group, 26 doubles per row to the host, metrics_from_sums there.  The
+    HR file's mask holds one row (used for every frame) or one per row.  Returns the list of per-row dicts (METRIC_NAMES); with
+    return_sums=True (metrics, sums) with sums the (rows,26) float64 array (VOLUME_SUM_NAMES).
+    output_filepath=None: the prediction never leaves the device (no staging copy, no HDF5 write).  Given: the file
+    predict_file(device_tiler=True) writes.  csv_path: write_metrics_csv.  Data-parallel: the peers send their cores as in
+    _predict_file_device; rank 0 evaluates (and writes) and returns the list, the other ranks return [].
+    ValueError, before any GPU work: the two files hold different numbers of rows, the HR volume is not res_increase x the LR volume, or
+    the mask has neither one row nor one per row."""
+    dataset = ImageDataset()
+    nr_rows = dataset.get_dataset_len(input_filepath)
+    hr_rows = dataset.get_dataset_len(hr_filepath)
+    if hr_rows != nr_rows:
+        raise ValueError("evaluate_file: %s holds %d rows, %s holds %d" % (input_filepath, nr_rows, hr_filepath, hr_rows))
+    lr_shape, hr_shape = dataset.get_volume_shape(input_filepath), dataset.get_volume_shape(hr_filepath)
+    if hr_shape != tuple(n * res_increase for n in lr_shape):
+        raise ValueError("evaluate_file: the high-resolution volume %s is not %d x the low-resolution volume %s"
+                         % (hr_shape, res_increase, lr_shape))
+    with h5io.open_read(hr_filepath) as hl:
+        mask_shape = tuple(int(n) for n in hl["mask"].shape)
+    if mask_shape[1:] != hr_shape or mask_shape[0] not in (1, nr_rows):
+        raise ValueError("evaluate_file: the mask of %s is %s, expected (1 or %d,) + %s" % (hr_filepath, mask_shape, nr_rows, hr_shape))
+    rd = lambda name: dataset._cache.get(hr_filepath, name)
+    dev = torch.device(network.device)
+    shared_mask = []                                                    # a one-row mask is uploaded once
+    collected = []                                                      # (first row, (n,26) device tensor): read back at the end
+
+    def score(rows, vol):
+        truth = np.empty((len(rows), 3) + hr_shape, dtype=np.float32)
+        for c, name in enumerate(dataset.velocity_colnames):
+            truth[:, c] = rd(name)[rows[0]:rows[-1] + 1]
+        if mask_shape[0] == 1:
+            if not shared_mask:
+                shared_mask.append(torch.from_numpy(np.ascontiguousarray(rd("mask"), dtype=np.float32)).to(dev))
+            mask = shared_mask[0]
+        else:
+            mask = torch.from_numpy(np.ascontiguousarray(rd("mask")[rows[0]:rows[-1] + 1], dtype=np.float32)).to(dev)
+        collected.append((rows[0], network.ops.volume_metrics(vol, torch.from_numpy(truth).to(dev), mask)))
+
+    t0 = time.time()
+    _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size, round_small_values,
+                         verbose and output_filepath is not None, frames_per_group, on_group=score, device_finish=True)
+    if parallel.rank() != 0:
+        return ([], np.empty((0, len(VOLUME_SUM_NAMES)))) if return_sums else []
+    sums = np.empty((nr_rows, len(VOLUME_SUM_NAMES)), dtype=np.float64)
+    for r0, t in collected:
+        sums[r0:r0 + t.shape[0]] = t.cpu().numpy()
+    metrics = metrics_from_sums(sums)
+    if verbose:
+        for i, m in enumerate(metrics):
+            print("Row %d/%d: rel. error %.3f %%, RMSE %.5f m/s, slope u/v/w %.4f/%.4f/%.4f, R2 %.4f/%.4f/%.4f" % (
+                i + 1, nr_rows, m["rel_error"], m["rmse"], m["k_u"], m["k_v"], m["k_w"], m["r2_u"], m["r2_v"], m["r2_w"]))
+        print("Evaluated %d rows in %.2f secs." % (nr_rows, time.time() - t0))
+    if csv_path is not None:
+        write_metrics_csv(csv_path, metrics)
+    return (metrics, sums) if return_sums else metrics
+
+
 def main(data_dir='../data', filename='example_data.h5', output_dir="../result", output_filename='example_result.h5',
          model_path="../models/4DFlowNet/4DFlowNet.h5", patch_size=24, res_increase=2, batch_size=8,
          round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32", device_tiler=False, frames_per_group=None):
@@ -450,6 +571,24 @@ def main(data_dir='../data', filename='example_data.h5', output_dir="../result",
         os.makedirs(output_dir)
     predict_file(network, '{}/{}'.format(data_dir, filename), '{}/{}'.format(output_dir, output_filename), patch_size,
                  res_increase, batch_size, round_small_values, device_tiler=device_tiler, frames_per_group=frames_per_group)
+    if parallel.rank() == 0:
+        print("Done!")
+
+
+def evaluate_main(data_dir='../data', filename='example_data.h5', hr_filename='example_data_HR.h5', output_dir="../result",
+                  csv_filename='example_metrics.csv', output_filename=None, model_path="../models/4DFlowNet/4DFlowNet.h5", patch_size=24,
+                  res_increase=2, batch_size=8, round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32",
+                  frames_per_group=None):
+    """The surface of main() for scoring a checkpoint: + hr_filename, the ground truth beside `filename`, and csv_filename; the
+    prediction itself is written only with output_filename."""
+    parallel.init_from_env()
+    network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype)
+    network.load_weights(model_path)
+    if not os.path.isdir(output_dir) and parallel.rank() == 0:
+        os.makedirs(output_dir)
+    evaluate_file(network, '{}/{}'.format(data_dir, filename), '{}/{}'.format(data_dir, hr_filename), patch_size, res_increase, batch_size,
+                  round_small_values, output_filepath=None if output_filename is None else '{}/{}'.format(output_dir, output_filename),
+                  csv_path='{}/{}'.format(output_dir, csv_filename) if parallel.rank() == 0 else None, frames_per_group=frames_per_group)
     if parallel.rank() == 0:
         print("Done!")
 

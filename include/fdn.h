@@ -251,6 +251,28 @@ int fdn_loss_metrics(const float* pred, const float* uh, const float* vh, const 
 int fdn_loss_metrics_div(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask,
                          float div_weight, float* out, float* dpred, float* scratch, int N, int D, int H, int W, void* stream);
 
+/* Whole-volume evaluation of a stitched prediction against the high-resolution truth: 26 sums per frame, from which the host derives the
+ * reference's loss and metric (src/Network/TrainerController.py:96-107, src/Network/loss_utils.py:64-101), the divergence term, RMSE
+ * and the regression line of prediction on truth.  pred (F,3,X,Y,Z) planar, fp32 (pred_is_f64 = 0) or float64 (1) -- what
+ * predict_volume returns --; truth (F,3,X,Y,Z) fp32 in the same units; mask (mask_frames,X,Y,Z) fp32, mask_frames = 1 (one mask for
+ * all frames) or F.  All arithmetic is in double (fp32 inputs convert exactly).  Per voxel, with p_c, t_c the prediction and truth of
+ * component c and m the mask: e_c = p_c - t_c, q = e_u^2 + e_v^2 + e_w^2, nf = [m < 0.5] (TrainerController.py:96), fl = [m == 1.0]
+ * (loss_utils.py:91); corr the relative error of loss_utils.py:64-92: diff = sqrt(q), actual = sqrt(sum t_c^2),
+ * rel = clip(diff / (actual + 1e-5), 0, 1), corr = actual != 0 ? rel : diff, corr = rint(corr * 1e4) / 1e4; g_c = (Da e_c), the clamped
+ * central difference of fdn_loss_metrics_div (e[clamp(k-1)] - e[clamp(k+1)]) along the axis paired with the component (u: X, v: Y,
+ * w: Z; 0 on an axis of extent 1), d = sum_c g_c^2.  out (F,26) float64 on the device, sums over the frame:
+ *   0,1,2: m, nf, fl    3,4: q m, q nf    5: corr fl    6,7,8: e_c^2 fl (c = u,v,w)    9,10: d m, d nf
+ *   11+5c .. 15+5c: t_c fl, p_c fl, t_c^2 fl, p_c^2 fl, t_c p_c fl.
+ * scratch: FDN_VOLUME_METRICS_SCRATCH_DOUBLES(F) caller-owned doubles of per-block partials, added in a fixed order (no atomics): two
+ * calls give identical bits.  A path of the three loss kernels selected by a by-value argument; the main kernel runs once per group of
+ * columns (3-8, 9-10, then the five moments of each component), and no column depends on that grouping.  At most FDN_LOSS_BLOCKS blocks per
+ * frame.  Refused before the device is touched: NULL operands, non-positive extents, X*Y*Z > 2^31 - 1, mask_frames not in {1, F},
+ * pred_is_f64 not in {0, 1}. */
+#define FDN_VOLUME_METRICS_COLUMNS 26
+#define FDN_VOLUME_METRICS_SCRATCH_DOUBLES(F) ((F) * FDN_VOLUME_METRICS_COLUMNS * FDN_LOSS_BLOCKS)
+int fdn_volume_metrics(const void* pred, int pred_is_f64, const float* truth, const float* mask, int mask_frames,
+                       double* out, double* scratch, int F, int X, int Y, int Z, void* stream);
+
 /* On-device input pipeline: the per-sample slicing / np.rot90 / sign / normalisation / mask threshold of
  * PatchHandler3D.load_patches_from_index_file (src/Network/PatchHandler3D.py:49-160) as one gather per output
  * tensor.  desc: B device-resident descriptors of 56 bytes each
