@@ -695,10 +695,24 @@ __global__ __launch_bounds__(1024) void l2_sumsq_kernel(const float* __restrict_
 // sumsq != null: block b also writes sum(w_new^2) over its kernel (non-bias) elements to sumsq[b] (fixed order: the
 // regulariser value of the NEXT step's loss, so fdn_l2_sumsq does not have to stream the parameters again).
 // lr_t_dev != null: the step size is lr_t_dev[0], read on the device (fdn_adam_step_dev: a captured launch must not bake it in).
+// accum != 0 (fdn_grad_accumulate): the sum of micro-batch gradient buffers as a path of this kernel selected by one by-value int --
+// w[i] = g[i] (ACCUM_FIRST) or w[i] + g[i] (ACCUM_ADD); m .. sumsq are not read.  Scalar accesses: w and g are bucket slices at any
+// float offset, and the 13.4 MB of cfg2 are not where the step's time is.
+#define ACCUM_FIRST 1
+#define ACCUM_ADD 2
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, const uint8_t* __restrict__ isk, int64_t n, float lr_t_host,
                                                    const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float l2s_host,
-                                                   const float* __restrict__ l2s_dev, float* __restrict__ sumsq) {
+                                                   const float* __restrict__ l2s_dev, float* __restrict__ sumsq, int accum) {
+    if (accum) {                                                     // fdn_grad_accumulate: w is the accumulator, g one micro-batch's gradients;
+        const bool first = accum == ACCUM_FIRST;                     // nothing else is read.  Uniform, ahead of the Adam path's first load
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+            const float gi = g[i];
+            if (first) w[i] = gi;                                    // a bit copy: the accumulator's old contents are never loaded
+            else w[i] = w[i] + gi;                                   // one IEEE fp32 add
+        }
+        return;
+    }
     const float lr_t = lr_t_dev ? lr_t_dev[0] : lr_t_host;
     const float l2s = l2s_dev ? l2s_host * l2s_dev[0] : l2s_host;
     float ss = 0.f;
@@ -997,7 +1011,7 @@ extern "C" int fdn_adam_step(float* w, const float* g, float* m, float* v, const
     // fixed grid of FDN_ADAM_PARTIALS blocks when partials are requested (blocks beyond the data write 0)
     const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);
     hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       lr_t, (const float*)nullptr, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials);
+                       lr_t, (const float*)nullptr, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0);
     FDN_CHECK_LAUNCH("adam_kernel");
     return FDN_OK;
 }
@@ -1010,8 +1024,25 @@ extern "C" int fdn_adam_step_dev(float* w, const float* g, float* m, float* v, c
     FDN_REQUIRE(n > 0, "fdn_adam_step_dev: n=%lld must be positive", (long long)n);
     const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);
     hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       0.f, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials);
+                       0.f, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0);
     FDN_CHECK_LAUNCH("adam_kernel");
+    return FDN_OK;
+}
+
+extern "C" int fdn_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream) {
+    FDN_REQUIRE(acc, "fdn_grad_accumulate: acc is NULL");
+    FDN_REQUIRE(g, "fdn_grad_accumulate: g is NULL");
+    FDN_REQUIRE(n > 0, "fdn_grad_accumulate: n=%lld must be positive", (long long)n);
+    FDN_REQUIRE(first == 0 || first == 1, "fdn_grad_accumulate: first=%d must be 0 or 1", first);
+    // (compared as integers: the two pointers need not belong to one allocation; n floats from either never wrap, checked first)
+    const uintptr_t a = (uintptr_t)acc, b = (uintptr_t)g, bytes = (uintptr_t)n * sizeof(float);
+    FDN_REQUIRE((uint64_t)n <= (UINTPTR_MAX - (a > b ? a : b)) / sizeof(float), "fdn_grad_accumulate: n=%lld floats run past the address space", (long long)n);
+    FDN_REQUIRE((a > b ? a - b : b - a) >= bytes, "fdn_grad_accumulate: acc and g overlap (%lld bytes apart, n=%lld floats): an in-place call would double the buffer",
+                (long long)(a > b ? a - b : b - a), (long long)n);
+    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, acc, g, (float*)nullptr, (float*)nullptr,
+                       (const uint8_t*)nullptr, n, 0.f, (const float*)nullptr, 0.f, 0.f, 0.f, 0.f, (const float*)nullptr, (float*)nullptr,
+                       first ? ACCUM_FIRST : ACCUM_ADD);
+    FDN_CHECK_LAUNCH("adam_kernel (grad accumulate)");
     return FDN_OK;
 }
 

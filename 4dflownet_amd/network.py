@@ -553,7 +553,14 @@ class FlowNetModel:
         """Fill self.flat_g with d(sum_b loss_b)/d(params) given dpred (B,PR,PR,PR,3); L2 is NOT included here
         (it is folded into the Adam kernel).  Consumes the cache of the last forward(training=True).
         grad_ready(lo, hi), if given, is called once per entry of self.grad_buckets, in that order, as soon as every launch that
-        writes flat_g_ext[lo:hi] has been enqueued on the current stream."""
+        writes flat_g_ext[lo:hi] has been enqueued.
+        STREAM of the callback: with overlap_wgrad on (and a weight-gradient stream in existence) it runs with that SIDE stream
+        current, right after the side stream has been made to wait for the main one -- so what it launches is ordered behind every
+        writer of the bucket on both streams, and the dgrad chain on the main stream does not stop for it.  Otherwise it runs on the
+        main stream.  The JOIN (main waits for side, _join_side) sits after the last weight gradient and BEFORE the callbacks of the
+        buckets still open at that point: those callbacks again put work on the side stream, which backward() does not join.  A caller
+        whose callback launches more than a collective it later waits for (the trainer's accumulate of a bucket, accum_steps > 1) joins
+        once more itself (_join_side) before the main stream consumes the result."""
         def bucket_done(k):
             self._flush_wgrads()                            # the batched weight gradients of this bucket's layers
             if grad_ready is not None and k < len(self.grad_buckets):

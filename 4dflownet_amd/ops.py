@@ -499,6 +499,19 @@ def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_
           "fdn_adam_step")
 
 
+def grad_accumulate(acc, g, first):
+    """acc = g (first: a bit copy, whatever acc held) or acc += g (one fp32 add per element), on the current stream: the sum of the
+    micro-batch gradient buffers of one optimiser step (fdn_grad_accumulate).  fp32 contiguous device tensors of equal numel that do
+    not overlap; slices at any float offset are fine."""
+    if acc.numel() != g.numel():
+        raise FdnError("grad_accumulate: acc holds %d elements, g %d" % (acc.numel(), g.numel()))
+    for name, t in (("acc", acc), ("g", g)):
+        if t.dtype != torch.float32:
+            raise FdnError("grad_accumulate: %s must be float32 (got %s)" % (name, t.dtype))
+    check(_lib.load().fdn_grad_accumulate(_p(acc, "acc"), _p(g, "g"), acc.numel(), 1 if first else 0, _stream()), "fdn_grad_accumulate")
+    return acc
+
+
 def l2_sumsq_partials(w_flat, is_kernel, partials):
     """ADAM_PARTIALS per-block sums of the kernel parameters' squares (what adam_step leaves behind), for parameters no Adam step has touched."""
     if partials.numel() < ADAM_PARTIALS:

@@ -7,7 +7,8 @@ Differences that are deliberate and documented in DESIGN.md:
     steps and TF2 scalar encoding, no TensorFlow dependency;
   * metrics accumulate on the device and are only synchronised when .result() is read, so a training loop that
     does not print every step never stalls the GPU (the reference forces a sync per step, :290);
-  * with torch.distributed initialised, train_step sum-all-reduces the flat gradient over RCCL before Adam."""
+  * with torch.distributed initialised, train_step sum-all-reduces the flat gradient over RCCL before Adam;
+  * accum_steps = K > 1 (no counterpart in the reference): K train_step calls form ONE optimiser step on the sum of their gradients."""
 import datetime
 import os
 import pickle
@@ -74,16 +75,27 @@ class _Optimizer:
 class TrainerController:
     def __init__(self, patch_size, res_increase, initial_learning_rate=1e-4, quicksave_enable=True,
                  network_name='4DFlowNet', low_resblock=8, hi_resblock=4, device=None, seed=0, dtype='float32',
-                 bucketed_allreduce=None, conv_algo=None, div_weight=0):
+                 bucketed_allreduce=None, conv_algo=None, div_weight=0, accum_steps=1):
         """Reference arguments: TrainerController.py:18.  Extra (keyword-only in spirit): device, seed (Glorot draw), dtype
         (activation storage, 'float32' | 'bfloat16'), bucketed_allreduce (data parallel only: True = one asynchronous SUM
         all-reduce per gradient bucket started inside backward -- the default --, False = ONE all-reduce of the whole buffer
         after backward; env FDN_DP_BUCKETED=0 selects the latter when the argument is None), conv_algo ('auto' | 'direct' |
         {layer name: ...}: algorithm of the 64->64 layers, see FlowNetModel), div_weight (weight of the divergence loss,
         TrainerController.py:23,84-127 with :111-120 live; 0 = the reference's shipped loss.  The attribute of the same name is
-        read on every step, so setting it later works too)."""
+        read on every step, so setting it later works too), accum_steps (gradient accumulation: K >= 1 consecutive train_step
+        calls -- micro-batches -- form ONE optimiser step on the sum of their gradient buffers, batch-size slot included, which is the
+        reference's step on the concatenated batch: tape.gradient of the (B,) loss vector is the gradient of sum_b loss_b and no layer
+        couples samples, TrainerController.py:223,245-249.  1 = every call is an optimiser step, nothing is allocated or launched for
+        accumulation.  The attribute of the same name is read when a group starts: a change made mid-group applies from the next
+        group.  See train_step and apply_accumulated)."""
         self.div_weight = div_weight   # TrainerController.py:23
         self._checked_div_weight()
+        self.accum_steps = accum_steps
+        self._checked_accum_steps()
+        self.accum_g_ext = None        # the accumulator, (n_params + 1,) like model.flat_g_ext: allocated by the first micro-step of a group of K > 1
+        self._accum_k = 1              # accum_steps as read when the running group started
+        self._accum_count = 0          # micro-steps of the running group so far (0: no group is open)
+        self._accum_has = False        # the accumulator holds a contribution of the running group (an empty shard contributes nothing)
         self.non_fluid_weight = 1
         self.res_increase = res_increase
         self.patch_size = patch_size
@@ -141,6 +153,12 @@ class TrainerController:
             raise ValueError("div_weight must be a finite number >= 0, got %r" % (w,))
         return wf
 
+    def _checked_accum_steps(self):
+        k = self.accum_steps
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError("accum_steps must be an integer >= 1, got %r" % (k,))
+        return int(k)
+
     def calculate_and_update_metrics(self, hires, predictions, mask, metric_set, want_grad):
         """TrainerController.py:84-127 (loss_function, the divergence term live when div_weight != 0), :243-256 (metrics)."""
         div_weight = self._checked_div_weight()
@@ -159,7 +177,18 @@ class TrainerController:
         return loss, dpred
 
     def train_step(self, data_pairs):
-        """TrainerController.py:209-225: forward, loss (+L2), gradient of sum_b loss_b, Adam."""
+        """TrainerController.py:209-225: forward, loss (+L2), gradient of sum_b loss_b, Adam.
+
+        With accum_steps = K > 1 every call handles one micro-batch: forward, loss, metrics and backward as always (the weights do not
+        move inside a group, so the L2 term and the per-sample losses are those of the big batch), and model.flat_g_ext is left holding
+        this micro-batch's own local gradient and batch size.  Calls 1 .. K-1 add it into self.accum_g_ext (fdn_grad_accumulate) and
+        stop there: no collective, no Adam launch, optimizer.iterations / flat_w / m / v / weights_version / the packs untouched.  Call K
+        accumulates, all-reduces the ACCUMULATOR over the ranks if data parallel, and runs Adam on it (its trailing slot = the group's
+        global batch size), one iteration.  apply_accumulated() closes a group early."""
+        if self._accum_count == 0:                                  # a group starts: this is where accum_steps is read
+            self._accum_k = self._checked_accum_steps()
+        if self._accum_k > 1:
+            return self._train_micro_step(data_pairs)
         inputs, hires, venc, mask = self._unpack(data_pairs)
         B = inputs[0].shape[0]
         m = self.model
@@ -187,6 +216,18 @@ class TrainerController:
                     reduce_bucket(lo, hi)
         if dp and not self.bucketed_allreduce:             # the plain form: one collective over the whole buffer after backward
             pending.append(parallel.allreduce_sum_start(m.flat_g_ext))
+        self._wait_allreduce(pending, dp)
+        opt = self.optimizer
+        opt.iterations += 1
+        # L2 regulariser gradient: the (B,) loss vector carries the scalar L2 term B times (:249) -> B_global * 2*lambda*w
+        ops.adam_step(m.flat_w, m.flat_g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
+                      2.0 * L2_LAMBDA, m.batch_slot, sumsq_partials=self._l2_partials)
+        m.weights_changed()
+        self._l2_version = m.weights_version
+        return loss
+
+    def _wait_allreduce(self, pending, dp):
+        """The current stream waits for the collectives in `pending` (no host synchronisation under nccl)."""
         if dp and self.profile_allreduce:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -196,14 +237,88 @@ class TrainerController:
             e1.record()
             self.allreduce_wait_events.append((e0, e1))
             del self.allreduce_wait_events[:-4096]          # a diagnostic left on outside the bench must not grow without bound
+
+    # ------------------------------------------------------------------ gradient accumulation (accum_steps > 1)
+    def _train_micro_step(self, data_pairs):
+        """One micro-batch of a group of self._accum_k (see train_step).  Stream order: on calls 1 .. K-1, and on the closing call
+        without per-bucket collectives, ONE accumulate launch of the whole buffer is issued on the main stream after backward() has
+        returned, i.e. behind its join of the weight-gradient stream.  On the closing call of a data-parallel run with
+        bucketed_allreduce the accumulate of bucket [lo, hi) is issued inside backward()'s grad_ready callback, on the stream that
+        callback runs on (the weight-gradient stream once it has been made to wait for the main one, see FlowNetModel.backward): behind
+        every writer of the bucket and behind the earlier micro-steps' accumulates, ahead of the bucket's all-reduce, which is started
+        from the same stream right after it; the main stream then waits for the collectives and joins that stream before Adam."""
+        inputs, hires, venc, mask = self._unpack(data_pairs)
+        B = inputs[0].shape[0]
+        m = self.model
+        m.batch_slot.fill_(float(B))
+        if self.accum_g_ext is None:
+            self.accum_g_ext = torch.empty_like(m.flat_g_ext)       # (never memset: the first contribution of a group is a copy)
+        acc = self.accum_g_ext
+        closing = self._accum_count + 1 >= self._accum_k
+        first = not self._accum_has
+        pending = None
+        on_bucket = None
+        if closing and self.bucketed_allreduce and parallel.world_size() > 1:
+            pending = []
+
+            def on_bucket(lo, hi):
+                if B > 0:
+                    ops.grad_accumulate(acc[lo:hi], m.flat_g_ext[lo:hi], first)
+                pending.append(parallel.allreduce_sum_start(acc[lo:hi]))
+        if B > 0:
+            pred = m.forward(inputs, training=True)
+            loss, dpred = self.calculate_and_update_metrics(hires, pred, mask, 'train', True)
+            m.backward(dpred, grad_ready=on_bucket)
+            if on_bucket is None:
+                ops.grad_accumulate(acc, m.flat_g_ext, first)
+            self._accum_has = True
+        else:                                   # an empty shard contributes nothing; the rank still joins the group's collectives
+            m.flat_g.zero_()
+            loss = None
+            if on_bucket is not None:
+                if first:                       # every micro-batch of this rank's group was empty: it reduces zeros
+                    acc.zero_()
+                    self._accum_has = True
+                for lo, hi in m.grad_buckets:
+                    on_bucket(lo, hi)
+        self._accum_count += 1
+        if closing:
+            self._apply_group(pending)
+        return loss
+
+    def _apply_group(self, pending=None):
+        """Reduce the accumulator over the ranks (pending: the per-bucket collectives the closing micro-step has already started; None:
+        one all-reduce of the whole buffer here) and run ONE Adam step on it."""
+        m, acc = self.model, self.accum_g_ext
+        dp = parallel.world_size() > 1
+        if pending is None:
+            pending = []
+            if not self._accum_has:
+                acc.zero_()
+            if dp:
+                pending.append(parallel.allreduce_sum_start(acc))
+        self._wait_allreduce(pending, dp)
+        m._join_side()                          # what the grad_ready callbacks put on the weight-gradient stream: ahead of Adam whatever the transport
         opt = self.optimizer
         opt.iterations += 1
-        # L2 regulariser gradient: the (B,) loss vector carries the scalar L2 term B times (:249) -> B_global * 2*lambda*w
-        ops.adam_step(m.flat_w, m.flat_g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
-                      2.0 * L2_LAMBDA, m.batch_slot, sumsq_partials=self._l2_partials)
+        n = m.n_params
+        ops.adam_step(m.flat_w, acc[:n], opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
+                      2.0 * L2_LAMBDA, acc[n:n + 1], sumsq_partials=self._l2_partials)
         m.weights_changed()
         self._l2_version = m.weights_version
-        return loss
+        self._accum_count = 0
+        self._accum_has = False
+
+    def apply_accumulated(self):
+        """Apply whatever the running group has accumulated as a shorter group: one accumulator all-reduce if data parallel (every
+        rank must call it: the ranks see the same number of micro-steps), one Adam step, one iteration.  A strict no-op when nothing
+        is pending (accum_steps == 1, or the last train_step closed its group): returns False and touches no state.  train_network
+        calls it after the last training batch of every epoch, so no gradient crosses a validation pass, a best-model save or an
+        epoch boundary."""
+        if self._accum_count == 0:
+            return False
+        self._apply_group()
+        return True
 
     def test_step(self, data_pairs):
         """TrainerController.py:227-239: forward + metrics, no L2, no update."""
@@ -340,6 +455,7 @@ class TrainerController:
                     print("\rEpoch %d Train batch %d/%d | loss: %.5f (%.1f %%) - %.1f secs" % (
                         epoch + 1, i + 1, total_batch_train, self.loss_metrics['train_loss'].result(),
                         self.loss_metrics['train_accuracy'].result(), time.time() - start_loop), end='')
+            self.apply_accumulated()                       # accum_steps > 1: a ragged last group is applied before validation
             for i, data_pairs in enumerate(self.device_batches(valset)):
                 self.test_step(data_pairs)
                 if verbose and is0:
@@ -393,7 +509,10 @@ class TrainerController:
         three heads interleave (network.keras_layer_order).  The pickle is written (and read back by restore_model) in that order, so
         a restart file can travel between the reference and this implementation.  [TF]: the order is restated from Keras' published
         graph-sorting algorithm, TensorFlow is absent here; tests/test_tf_golden.py checks it against real variable names the day
-        tests/golden/tf_golden.npz exists.  Several layers share a shape, so a wrong order cannot be detected from shapes alone."""
+        tests/golden/tf_golden.npz exists.  Several layers share a shape, so a wrong order cannot be detected from shapes alone.
+
+        Gradient accumulation: a partial group is never checkpointed -- the accumulator is not part of the files.  train_network applies
+        the pending group before it gets here; a caller of its own does the same with apply_accumulated()."""
         self.model.save('%s-best.h5' % self.model_path)
         tv = self.model.trainable_variables
         sizes = [t.numel() for t in tv]
@@ -413,7 +532,8 @@ class TrainerController:
             f.write("\n".join(names[i] for i in order) + "\n")
 
     def restore_model(self, old_model_dir, old_model_file):
-        """TrainerController.py:365-394.  optimizer.pkl slots are in Keras trainable_variables order (see save_best_model)."""
+        """TrainerController.py:365-394.  optimizer.pkl slots are in Keras trainable_variables order (see save_best_model).
+        A checkpoint never holds a partial accumulation group: a group that is open here is dropped, the next train_step starts one."""
         with open("%s/optimizer.pkl" % old_model_dir, 'rb') as f:
             opt_weights = pickle.load(f)
         tv = self.model.trainable_variables
@@ -450,6 +570,8 @@ class TrainerController:
         self.optimizer.m.copy_(flat(m))
         self.optimizer.v.copy_(flat(v))
         self.model.load_weights("%s/%s" % (old_model_dir, old_model_file))
+        self._accum_count = 0
+        self._accum_has = False
 
     def quicksave(self, testset, epoch_nr):
         """TrainerController.py:415-454: predict the first benchmark batch, append to quicksave_<name>.h5."""

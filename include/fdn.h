@@ -341,6 +341,14 @@ int fdn_adam_step_dev(float* w, const float* g, float* m, float* v, const uint8_
                       const float* lr_t_dev, float b1, float b2, float eps, float l2_grad_scale,
                       const float* l2_scale_dev, float* sumsq_partials, void* stream);
 int fdn_sum_partials(const float* partials, int n, float* out, void* stream);
+/* acc[i] = first ? g[i] : acc[i] + g[i], i in [0, n).  One fp32 add per element (IEEE, round-to-nearest-even):
+ * first = 1 is a bit copy (no memset of acc is needed), first = 0 equals numpy's float32 acc + g bit for bit.
+ * The sum of the micro-batch gradients of one optimiser step: TrainerController.py:223 (tape.gradient of the (B,)
+ * loss vector = gradient of sum_b loss_b), :245-249 (L2 counted once per sample: the batch-size slot adds up too).
+ * acc and g may sit at any float offset (gradient-bucket slices).  A path of the Adam kernel selected by a by-value argument.
+ * Refused before the device is touched: NULL acc or g, n <= 0, first not in {0, 1}, ranges that overlap (|acc - g| < n floats:
+ * an in-place call would double a buffer silently). */
+int fdn_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream);
 /* The same FDN_ADAM_PARTIALS per-block sums for parameters no fdn_adam_step has touched yet (first step, after loading a
  * checkpoint): the multi-block form of fdn_l2_sumsq, which needs no scratch and runs as ONE block.  Follow with fdn_sum_partials. */
 int fdn_l2_sumsq_partials(const float* w, const uint8_t* is_kernel, int64_t n, float* sumsq_partials, void* stream);

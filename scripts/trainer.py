@@ -39,6 +39,7 @@ if __name__ == "__main__":
     initial_learning_rate = 2e-4
     epochs = 60
     batch_size = 20
+    accum_steps = 1          # optimiser step = accum_steps consecutive batches of batch_size (x ranks); 1 = the reference's schedule
     mask_threshold = 0.6
     network_name = '4DFlowNet'
     patch_size = 16
@@ -61,7 +62,7 @@ if __name__ == "__main__":
 
     print("4DFlowNet Patch %d, lr %s, batch %d" % (patch_size, initial_learning_rate, batch_size))
     network = trainer.TrainerController(patch_size, res_increase, initial_learning_rate, QUICKSAVE, network_name,
-                                        low_resblock, hi_resblock)
+                                        low_resblock, hi_resblock, accum_steps=accum_steps)
     network.init_model_dir()
     if restore:
         print("Restoring model %s..." % model_file)
