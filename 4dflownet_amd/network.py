@@ -112,7 +112,7 @@ class FlowNetModel:
             raise ValueError("dtype must be 'float32' or 'bfloat16'")
         self.dtype = dtype
         self.ops = ops if dtype == "float32" else ops_bf16
-        self.act_dtype = torch.float32 if dtype == "float32" else torch.bfloat16
+        self.act_dtype = self.ops.ACT_DTYPE
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.res_increase = int(res_increase)
         self.low_resblock = int(low_resblock)
@@ -129,11 +129,10 @@ class FlowNetModel:
         self.layers = []
         off = 0
         n64 = sum(1 for _, k, ci, co, _ in self.specs if (k, ci, co) == (3, 64, 64))
-        pack_elems = ops.CONV64_PACK_FLOATS if dtype == "float32" else 27 * 64 * 64
         # (zero-filled: a pack holds five streams and only the ones the model's grids read are kept current -- _pack_streams below; the others
         # stay zero, not garbage.  The packs are private to forward() / backward(): read L.wp_f / L.wp_d elsewhere only through
         # _require_pack_streams, or re-pack everything with ops.pack_conv64_weights_batch(..., streams=None).)
-        self._packs = torch.zeros((n64, 2, pack_elems), device=self.device, dtype=self.act_dtype)
+        self._packs = torch.zeros((n64, 2, self.ops.PACK_ELEMS), device=self.device, dtype=self.act_dtype)
         i64 = 0
         for name, k, ci, co, ub in self.specs:
             L = _Layer()
@@ -241,12 +240,8 @@ class FlowNetModel:
     def weights_changed(self):
         """Re-derive the MFMA operand streams after any parameter update (Adam step, load_weights)."""
         self.weights_version += 1
-        if self.dtype == "float32":
-            if self._w64_offsets.numel():                  # all 64->64 layers, the streams in use, one launch
-                ops.pack_conv64_weights_batch(self.flat_w, self._w64_offsets, self._packs, streams=self._pack_streams)
-            return
-        if self._w64_offsets.numel():
-            ops_bf16.pack_conv64_weights_batch(self.flat_w, self._w64_offsets, self._packs)   # one launch (37 per-layer launches before)
+        if self._w64_offsets.numel():                      # all 64->64 layers, the streams in use (fp32), one launch
+            self.ops.pack_conv64_weights_batch(self.flat_w, self._w64_offsets, self._packs, streams=self._pack_streams)
 
     @property
     def trainable_variables(self):
@@ -322,47 +317,41 @@ class FlowNetModel:
             warnings.warn(msg, RuntimeWarning, stacklevel=4)
 
     def _require_pack_streams(self, N, D, H, W, training):
-        """Make sure the pack streams the 64->64 layers read on this grid are current (see __init__)."""
-        if self.dtype != "float32":
-            return
+        """Make sure the pack streams the 64->64 layers read on this grid are current (see __init__; a bf16 pack has none to select)."""
         algos = tuple(sorted(set(self.conv_algo[L.name] for L in self.layers if L.wp_f is not None)))
         key = (N, D, H, W, training, algos)
         need = self._pack_need_cache.get(key)
         if need is None:
             f = d = 0
             for a in algos:
-                f |= ops.conv64_pack_streams(N, D, H, W, a, ops.ROLE_FWD)
+                f |= self.ops.conv64_pack_streams(N, D, H, W, a, ops.ROLE_FWD)
                 if training:
-                    d |= ops.conv64_pack_streams(N, D, H, W, a, ops.ROLE_DGRAD_FUSED)
+                    d |= self.ops.conv64_pack_streams(N, D, H, W, a, ops.ROLE_DGRAD_FUSED)
             need = self._pack_need_cache[key] = (f, d)
         new = [need[0] & ~self._pack_streams[0], need[1] & ~self._pack_streams[1]]
         if new[0] or new[1]:
             self._pack_streams = [self._pack_streams[0] | new[0], self._pack_streams[1] | new[1]]
             if self._w64_offsets.numel():
-                ops.pack_conv64_weights_batch(self.flat_w, self._w64_offsets, self._packs, streams=new)
+                self.ops.pack_conv64_weights_batch(self.flat_w, self._w64_offsets, self._packs, streams=new)
 
     def _conv(self, x, L, act, residual=None, x2=None, out=None, ldy=None, y_coff=0, mask=None):
-        if mask is not None:                               # bf16 training, 64->64: the output and its sign mask (ops_bf16.conv3d_fwd)
-            return self.ops.conv3d_fwd(x, L.w, L.b, act, ops.LEAKY_ALPHA, residual, None, L.wp_f, out, ldy, y_coff, mask=mask)
-        return self.ops.conv3d_fwd(x, L.w, L.b, act, ops.LEAKY_ALPHA, residual, x2, L.wp_f, out, ldy, y_coff, algo=self.conv_algo[L.name])
+        """mask (training, a dense 64->64 layer): also receives the sign mask of the output."""
+        return self.ops.conv3d_fwd(x, L.w, L.b, act, ops.LEAKY_ALPHA, residual, x2, L.wp_f, out, ldy, y_coff, algo=self.conv_algo[L.name],
+                                   mask=mask)
 
     def _mask_ok(self, x, L):
-        """fp32: do the forward and the fused dgrad of this grid write / read sign masks (the plain F(4,3) x F(4,3) kernels)?"""
+        """Do the forward and the fused dgrad of this grid write / read sign masks (fp32: the plain F(4,3) x F(4,3) kernels; bf16: all)?"""
         key = (tuple(x.shape[:4]), self.conv_algo[L.name])
         ok = self._mask_ok_cache.get(key)
         if ok is None:
-            ok = self._mask_ok_cache[key] = ops.conv64_mask_ok(*key[0], key[1])
+            ok = self._mask_ok_cache[key] = self.ops.conv64_mask_ok(*key[0], key[1])
         return ok
 
     def _conv_m(self, x, L, act, residual=None, want_mask=False):
         """A 64->64 layer and, in training, the sign mask of its output (None where the kernels of the grid do not write one)."""
-        if want_mask and self.sign_masks and act != ACT_NONE:
-            if self.dtype == "bfloat16":
-                mask = ops_bf16.new_sign_mask(x)
-                return self._conv(x, L, act, residual=residual, mask=mask), mask
-            if self._mask_ok(x, L):
-                mask = ops.new_sign_mask(x)
-                return ops.conv3d_fwd(x, L.w, L.b, act, ops.LEAKY_ALPHA, residual, None, L.wp_f, algo=self.conv_algo[L.name], mask=mask), mask
+        if want_mask and self.sign_masks and act != ACT_NONE and self._mask_ok(x, L):
+            mask = self.ops.new_sign_mask(x)
+            return self._conv(x, L, act, residual=residual, mask=mask), mask
         return self._conv(x, L, act, residual=residual), None
 
     def forward(self, inputs, training=False):
@@ -469,31 +458,31 @@ class FlowNetModel:
             self._ws = torch.empty((nbytes + 3) // 4, device=self.device, dtype=torch.float32)
         return self._ws
 
+    @contextlib.contextmanager
+    def _on_side(self):
+        """Run the body on the second HIP stream, behind everything the current stream has been given; _join_side() brings it back."""
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        self._side.wait_stream(torch.cuda.current_stream())
+        self._side_busy = True
+        with torch.cuda.stream(self._side):
+            yield
+
     def _wgrad(self, x, dz, L, x2=None, lddz=None, dz_coff=0, bias=True):
         """Weight (+bias) gradient of layer L into the flat gradient buffer.  Weight gradients are leaves of the backward
         graph (nothing downstream reads them before the optimizer), so they run on a second HIP stream and fill the tails
         of the dgrad chain's kernels; backward() joins the streams before returning."""
         N, D, H, W = x.shape[:4]
         if (self.batch_wgrad and (L.k, L.cin, L.cout) == (3, 64, 64) and x2 is None and lddz is None and
-                N * D * H * W <= self.batch_wgrad_max_voxels and
-                (self.dtype != "float32" or self.conv_algo[L.name] in (ops.ALGO_AUTO, ops.ALGO_WINO_H2, ops.ALGO_WINO_BF16X3))):
+                N * D * H * W <= self.batch_wgrad_max_voxels and self.ops.conv64_wgrad_batch_ok(self.conv_algo[L.name])):
             self._wg_pending.append((x, dz, L, bias))        # issued by _flush_wgrads() at the end of the gradient bucket
             return
         nws = self.ops.wgrad_workspace_bytes(N, D, H, W, L.cin, L.cout, L.k)
-        if not self.overlap_wgrad:
-            self.ops.conv3d_wgrad(x, dz, L.k, L.cin, L.cout, x2=x2, dw=L.gw, dbias=L.gb if bias else None, workspace=self._workspace(nws),
-                             lddz=lddz, dz_coff=dz_coff, algo=self.conv_algo[L.name])
-            return
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        main = torch.cuda.current_stream()
-        self._side.wait_stream(main)                      # dz is ready
-        self._side_busy = True
-        ws = self._workspace(nws, side=True)
-        with torch.cuda.stream(self._side):
-            self.ops.conv3d_wgrad(x, dz, L.k, L.cin, L.cout, x2=x2, dw=L.gw, dbias=L.gb if bias else None, workspace=ws, lddz=lddz,
-                             dz_coff=dz_coff, algo=self.conv_algo[L.name])
-        self._side_keep.extend(t for t in (x, dz, x2) if t is not None)     # alive until the streams are joined (see _join_side)
+        with self._on_side() if self.overlap_wgrad else contextlib.nullcontext():      # (side stream: behind the main one, so dz is ready)
+            self.ops.conv3d_wgrad(x, dz, L.k, L.cin, L.cout, x2=x2, dw=L.gw, dbias=L.gb if bias else None,
+                                  workspace=self._workspace(nws, side=self.overlap_wgrad), lddz=lddz, dz_coff=dz_coff, algo=self.conv_algo[L.name])
+        if self.overlap_wgrad:
+            self._side_keep.extend(t for t in (x, dz, x2) if t is not None)     # alive until the streams are joined (see _join_side)
 
     def _flush_wgrads(self):
         """Issue the collected weight gradients: layers of one grid and algorithm as one batched launch, a lone layer as before."""
@@ -504,12 +493,7 @@ class FlowNetModel:
         for (shape, algo), items in groups.items():
             N, D, H, W = shape
             side = self.overlap_wgrad
-            if side:
-                if self._side is None:
-                    self._side = torch.cuda.Stream(device=self.device)
-                self._side.wait_stream(torch.cuda.current_stream())
-                self._side_busy = True
-            with torch.cuda.stream(self._side) if side else contextlib.nullcontext():
+            with self._on_side() if side else contextlib.nullcontext():
                 if len(items) == 1:
                     x, dz, L, bias = items[0]
                     ws = self._workspace(self.ops.wgrad_workspace_bytes(N, D, H, W, 64, 64, 3), side=side)
@@ -536,16 +520,20 @@ class FlowNetModel:
         N, D, H, W, C = t.shape
         return torch.empty((N, D + 2, H + 2, W + 2, C), device=t.device, dtype=torch.float32)
 
+    def _dgrad_fused(self, dz, L, pad, out, skip, y_prev, act, mask):
+        """One fused dgrad launch of the 64->64 layer L into out / pad: act'(y_prev) from `mask`, the sign mask of y_prev, where there is one
+        and the kernels of this grid and algorithm read masks, else from y_prev (None: the producer was linear)."""
+        if mask is not None and (y_prev is None or not self._mask_ok(dz, L)):
+            mask = None
+        self.ops.conv3d_dgrad_fused(dz, L.wp_d, pad, out, skip=skip, y_prev=y_prev, act=act, algo=self.conv_algo[L.name], mask=mask)
+
     def _dgrad_fold(self, dz, L, skip, y_prev, act, mask=None):
         """dz_prev = (MirrorPadGrad(Conv3DBackpropInput(dz)) + skip) * act'(y_prev) for a 64->64 layer: interior voxels
         are finished by the conv epilogue, the surface by one small border kernel.  mask: the sign mask of y_prev, read by the conv
         epilogue instead of y_prev itself (bf16 mode; fp32 on the grids of the F(4,3) x F(4,3) kernels)."""
         out = torch.empty_like(dz)
         pad = self._pad_like(dz)
-        kw = {} if self.dtype == "bfloat16" else {"algo": self.conv_algo[L.name]}
-        if mask is not None and y_prev is not None and (self.dtype == "bfloat16" or self._mask_ok(dz, L)):
-            kw["mask"] = mask
-        self.ops.conv3d_dgrad_fused(dz, L.wp_d, pad, out, skip=skip, y_prev=y_prev, act=act, **kw)
+        self._dgrad_fused(dz, L, pad, out, skip, y_prev, act, mask)
         self.ops.fold_halo_border([pad], out, skip, y_prev, act)
         return out
 
@@ -568,9 +556,7 @@ class FlowNetModel:
                     # the bucket is complete once BOTH streams have run what they hold: the callback (the trainer starts the bucket's
                     # all-reduce in it) is issued from the side stream after that stream has been made to wait for the main one, so the
                     # collective is ordered behind both and the dgrad chain on the main stream does not stop for it
-                    self._side.wait_stream(torch.cuda.current_stream())
-                    self._side_busy = True
-                    with torch.cuda.stream(self._side):
+                    with self._on_side():
                         grad_ready(*self.grad_buckets[k])
                 else:
                     grad_ready(*self.grad_buckets[k])
@@ -592,8 +578,8 @@ class FlowNetModel:
         pads = []
         # ONE multi-source launch forms the sum of the three input gradients in its registers (ops.conv3d_dgrad_fused_multi; fp32: on the
         # grids of the F(4,3) x F(4,3) kernels) instead of three chained launches that re-read and re-write the running sum
-        multi = self.multi_dgrad and (self.dtype == "bfloat16" or (len({self.conv_algo[Ls[li + 2 * h].name] for h in range(3)}) == 1
-                                                                   and self._mask_ok(rb.t, Ls[li])))
+        multi = (self.multi_dgrad and self.ops.conv64_dgrad_multi_ok([self.conv_algo[Ls[li + 2 * h].name] for h in range(3)])
+                 and self._mask_ok(rb.t, Ls[li]))
         dz_gs = []
         for hidx in range(3):
             L1, L2 = Ls[li], Ls[li + 1]
@@ -618,12 +604,7 @@ class FlowNetModel:
                 continue
             pad = self._pad_like(rb.t)
             y_m, a_m = act_of(rb) if hidx == 2 else (None, ACT_NONE)
-            if y_m is not None and rb.mask is not None and (self.dtype == "bfloat16" or self._mask_ok(dz_g, L1)):
-                self.ops.conv3d_dgrad_fused(dz_g, L1.wp_d, pad, dz, skip=dz if hidx > 0 else None, y_prev=y_m, act=a_m, mask=rb.mask,
-                                            **({} if self.dtype == "bfloat16" else {"algo": self.conv_algo[L1.name]}))
-            else:
-                self.ops.conv3d_dgrad_fused(dz_g, L1.wp_d, pad, dz, skip=dz if hidx > 0 else None, y_prev=y_m, act=a_m,
-                                            algo=self.conv_algo[L1.name])
+            self._dgrad_fused(dz_g, L1, pad, dz, dz if hidx > 0 else None, y_m, a_m, rb.mask)
             pads.append(pad)
             del dz_g
             li += 2

@@ -3,6 +3,7 @@
 Every function launches asynchronously on torch's current HIP stream and returns its output tensor(s).
 Tensors must be fp32, contiguous and on a ROCm device; anything else raises (no CPU path)."""
 import ctypes
+import functools
 
 import torch
 
@@ -17,20 +18,38 @@ LEAKY_ALPHA = 0.2
 # FDN_CONV64_PACK_FLOATS (mirrored; _lib.load() checks fdn_version() against FDN_VERSION below): direct stream (27 taps) + Winograd F(4,3)
 # stream (54) + 2-D F(2,3)xF(4,3) stream (72) + 2-D F(4,3)xF(4,3) stream (108) + the same as three bf16 pieces per value (162 float-sized slots)
 CONV64_PACK_FLOATS = 423 * 64 * 64
+# what network.py reads from either operator module: storage type of the activations, elements of one 64->64 pack of that type
+ACT_DTYPE = torch.float32
+PACK_ELEMS = CONV64_PACK_FLOATS
 
 
-def _p(t, name="tensor", allow_none=False):
+def _ptr(dtype, t, name="tensor", allow_none=False):
+    """The device address of a contiguous GPU tensor of exactly `dtype` (None -> NULL where allowed): the one pointer check of both operator
+    modules."""
     if t is None:
         if allow_none:
             return None
         raise FdnError("%s is None" % name)
     if not t.is_cuda:
         raise FdnError("%s must live on the GPU; the HIP path has no CPU fallback" % name)
-    if t.dtype != torch.float32 and t.dtype != torch.uint8:
-        raise FdnError("%s must be float32 (got %s)" % (name, t.dtype))
+    if t.dtype != dtype:
+        raise FdnError("%s must be %s (got %s)" % (name, str(dtype).replace("torch.", ""), t.dtype))
     if not t.is_contiguous():
         raise FdnError("%s must be contiguous" % name)
     return t.data_ptr()
+
+
+_p = functools.partial(_ptr, torch.float32)
+_p64 = functools.partial(_ptr, torch.float64)
+_pu8 = functools.partial(_ptr, torch.uint8)              # the is_kernel flags of the flat parameter buffer
+_pm = functools.partial(_ptr, torch.int16, name="mask")
+
+
+def _mask_ptr(mask, nvox, who):
+    """A sign mask of nvox voxels (four int16 words each, in the shape the storage type's new_sign_mask gives it), or None -> NULL."""
+    if mask is not None and mask.numel() != 4 * nvox:
+        raise FdnError("%s: a sign mask of 4 x %d int16 words expected" % (who, nvox))
+    return _pm(mask, allow_none=True)
 
 
 def _stream():
@@ -58,37 +77,31 @@ def _volume_geometry(frames, patch_size, counts, g0, count, who):
     return (F, X, Y, Z, int(patch_size), nx, ny, nz, int(g0), count)
 
 
+def _input_features_volume(entry, act_dtype, frames, patch_size, counts, g0, count, phase, pc):
+    """input_features_volume of either storage type: `entry` names the library's entry point, act_dtype is the type of phase / pc."""
+    geo = _volume_geometry(frames, patch_size, counts, g0, count, "input_features_volume")
+    P, count = geo[4], geo[9]
+    if phase is None:
+        phase = torch.empty((max(count, 0), P, P, P, 3), device=frames.device, dtype=act_dtype)
+    if pc is None:
+        pc = torch.empty((max(count, 0), P, P, P, 3), device=frames.device, dtype=act_dtype)
+    if min(phase.numel(), pc.numel()) < max(count, 0) * P ** 3 * 3:
+        raise FdnError("input_features_volume: phase / pc hold fewer than (%d,%d,%d,%d,3) elements" % (count, P, P, P))
+    check(getattr(_lib.load(), entry)(_p(frames, "frames"), *geo, _ptr(act_dtype, phase, "phase"), _ptr(act_dtype, pc, "pc"), _stream()), entry)
+    return phase, pc
+
+
 def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None):
     """input_features of patches [g0, g0 + count) of the sliding window over resident frames (F,6,X,Y,Z) (u,v,w,mag_u,mag_v,mag_w,
     normalised): the patches are never materialised.  counts = (nx,ny,nz) of tiler.PatchGenerator.plan; patch g = frame g // (nx*ny*nz),
     then (i,j,k) with k fastest.  Returns (phase, pc), each (count,P,P,P,3)."""
-    geo = _volume_geometry(frames, patch_size, counts, g0, count, "input_features_volume")
-    P, count = geo[4], geo[9]
-    if phase is None:
-        phase = torch.empty((max(count, 0), P, P, P, 3), device=frames.device, dtype=torch.float32)
-    if pc is None:
-        pc = torch.empty((max(count, 0), P, P, P, 3), device=frames.device, dtype=torch.float32)
-    if min(phase.numel(), pc.numel()) < max(count, 0) * P ** 3 * 3:
-        raise FdnError("input_features_volume: phase / pc hold fewer than (%d,%d,%d,%d,3) elements" % (count, P, P, P))
-    check(_lib.load().fdn_input_features_volume(_p(frames, "frames"), *geo, _p(phase, "phase"), _p(pc, "pc"), _stream()),
-          "fdn_input_features_volume")
-    return phase, pc
+    return _input_features_volume("fdn_input_features_volume", ACT_DTYPE, frames, patch_size, counts, g0, count, phase, pc)
 
 
 def _pred_edge(pred, who):
     if pred.dim() != 5 or pred.shape[4] != 3 or not (pred.shape[1] == pred.shape[2] == pred.shape[3]):
         raise FdnError("%s: pred must be (count,S,S,S,3), got %s" % (who, tuple(pred.shape)))
     return pred.shape[1]
-
-
-def _p64(t, name):
-    if not t.is_cuda:
-        raise FdnError("%s must live on the GPU; the HIP path has no CPU fallback" % name)
-    if t.dtype != torch.float64:
-        raise FdnError("%s must be float64 (got %s)" % (name, t.dtype))
-    if not t.is_contiguous():
-        raise FdnError("%s must be contiguous" % name)
-    return t.data_ptr()
 
 
 def stitch_patches(pred, vol, side, counts, g0=0, frame_scale=None):
@@ -157,12 +170,6 @@ def new_sign_mask(y):
     return torch.empty((4, y.shape[0] * y.shape[1] * y.shape[2] * y.shape[3]), device=y.device, dtype=torch.int16)
 
 
-def _pm(t, name="mask"):
-    if not t.is_cuda or t.dtype != torch.int16 or not t.is_contiguous():
-        raise FdnError("%s must be a contiguous int16 tensor on the GPU" % name)
-    return t.data_ptr()
-
-
 def conv3d_fwd(x, w, bias=None, act=ACT_NONE, alpha=LEAKY_ALPHA, residual=None, x2=None, wpack=None, out=None,
                ldy=None, y_coff=0, algo=ALGO_AUTO, mask=None):
     """x (N,D,H,W,Cin[/2 if x2]); w Keras layout (K,K,K,Cin,Cout).
@@ -170,15 +177,15 @@ def conv3d_fwd(x, w, bias=None, act=ACT_NONE, alpha=LEAKY_ALPHA, residual=None, 
     N, D, H, W = x.shape[:4]
     K, Cin, Cout = w.shape[0], w.shape[3], w.shape[4]
     if mask is not None:
-        if (K, Cin, Cout) != (3, 64, 64) or x2 is not None or (ldy not in (None, 64)) or y_coff != 0 or mask.numel() != 4 * N * D * H * W:
-            raise FdnError("conv3d_fwd: a sign mask (4 x %d int16 words) belongs to a dense 64->64 3x3x3 layer" % (N * D * H * W))
+        if (K, Cin, Cout) != (3, 64, 64) or x2 is not None or (ldy not in (None, 64)) or y_coff != 0:
+            raise FdnError("conv3d_fwd: a sign mask belongs to a dense 64->64 3x3x3 layer")
         if out is None:
             out = torch.empty((N, D, H, W, 64), device=x.device, dtype=torch.float32)
         if wpack is None:
             wpack, _ = pack_conv64_weights(w, want_dgrad=False)
         check(_lib.load().fdn_conv64_fwd_mask(_p(x, "x"), _p(wpack, "wpack"), _p(bias, allow_none=True), _p(residual, allow_none=True),
-                                              _p(out, "out"), _pm(mask), N, D, H, W, act, float(alpha), int(algo), _stream()),
-              "fdn_conv64_fwd_mask")
+                                              _p(out, "out"), _mask_ptr(mask, N * D * H * W, "conv3d_fwd"), N, D, H, W, act, float(alpha), int(algo),
+                                              _stream()), "fdn_conv64_fwd_mask")
         return out
     if out is None:
         out = torch.empty((N, D, H, W, Cout), device=x.device, dtype=torch.float32)
@@ -221,11 +228,10 @@ def conv_cout1_dgrad_folded(dz, w, spatial, y_prev=None, act=ACT_NONE, alpha=LEA
         workspace = torch.empty(2048 * 64, device=dz.device, dtype=torch.float32)
     wsb = 0 if workspace is None else workspace.numel() * workspace.element_size()
     if mask is not None:
-        if mask.numel() != 4 * N * D * H * W:
-            raise FdnError("conv_cout1_dgrad_folded: a sign mask of 4 x %d int16 words expected" % (N * D * H * W))
-        check(_lib.load().fdn_conv_cout1_dgrad_folded_mask(_p(dz, "dz"), _p(w, "w"), _pm(mask), act, float(alpha), _p(out),
-                                                           _p(dbias_prev, allow_none=True), _p(workspace, allow_none=True), wsb,
-                                                           N, D, H, W, lddz, dz_coff, _stream()), "fdn_conv_cout1_dgrad_folded_mask")
+        check(_lib.load().fdn_conv_cout1_dgrad_folded_mask(_p(dz, "dz"), _p(w, "w"), _mask_ptr(mask, N * D * H * W, "conv_cout1_dgrad_folded"),
+                                                           act, float(alpha), _p(out), _p(dbias_prev, allow_none=True),
+                                                           _p(workspace, allow_none=True), wsb, N, D, H, W, lddz, dz_coff, _stream()),
+              "fdn_conv_cout1_dgrad_folded_mask")
         return out
     check(_lib.load().fdn_conv_cout1_dgrad_folded(_p(dz, "dz"), _p(w, "w"), _p(y_prev, allow_none=True), act, float(alpha),
                                                   _p(out), _p(dbias_prev, allow_none=True), _p(workspace, allow_none=True), wsb,
@@ -257,11 +263,11 @@ def conv3d_dgrad_fused(dz, wpack_dgrad, dxpad, out, skip=None, y_prev=None, act=
     instead of y_prev for act' (the one-launch form only)."""
     N, D, H, W = dz.shape[:4]
     if mask is not None:
-        if parts != 3 or mask.numel() != 4 * N * D * H * W:
-            raise FdnError("conv3d_dgrad_fused: a sign mask needs the one-launch form and 4 x %d int16 words" % (N * D * H * W))
+        if parts != 3:
+            raise FdnError("conv3d_dgrad_fused: a sign mask needs the one-launch form")
         check(_lib.load().fdn_conv64_dgrad_fused_mask(_p(dz, "dz"), _p(wpack_dgrad, "wpack"), _p(dxpad, "dxpad"), _p(skip, allow_none=True),
-                                                      _pm(mask), act, float(alpha), _p(out, "out"), N, D, H, W, int(algo), _stream()),
-              "fdn_conv64_dgrad_fused_mask")
+                                                      _mask_ptr(mask, N * D * H * W, "conv3d_dgrad_fused"), act, float(alpha), _p(out, "out"),
+                                                      N, D, H, W, int(algo), _stream()), "fdn_conv64_dgrad_fused_mask")
         return out
     if parts == 3:
         check(_lib.load().fdn_conv3d_dgrad_fused(_p(dz, "dz"), _p(wpack_dgrad, "wpack"), _p(dxpad, "dxpad"),
@@ -275,22 +281,34 @@ def conv3d_dgrad_fused(dz, wpack_dgrad, dxpad, out, skip=None, y_prev=None, act=
     return out
 
 
-def conv3d_dgrad_fused_multi(dzs, wpacks_dgrad, dxpad, out, skip=None, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA, algo=ALGO_AUTO, mask=None):
-    """The fused dgrad of 1..3 64->64 layers that share their input, as ONE launch: out / dxpad receive what chained conv3d_dgrad_fused
-    calls (skip = the running sum) would leave, to fp32 rounding -- the sum over the sources is formed in the kernel's registers.  Only
-    where conv64_mask_ok(N, D, H, W, algo); the packs must be views of one pack buffer.  y_prev or mask (its sign mask) or neither."""
+def _dgrad_fused_multi(entry, pa, dzs, wpacks_dgrad, dxpad, out, skip, y_prev, act, alpha, mask, *algo):
+    """conv3d_dgrad_fused_multi of either storage type: `entry` names the library's entry point, pa checks an activation pointer, algo is
+    (algo,) where the entry point takes one."""
     n = len(dzs)
     N, D, H, W = dzs[0].shape[:4]
     if not 1 <= n <= 3 or len(wpacks_dgrad) != n or any(tuple(t.shape) != tuple(dzs[0].shape) for t in dzs):
         raise FdnError("conv3d_dgrad_fused_multi: 1..3 sources of one shape, one pack each")
-    if mask is not None and (y_prev is not None or mask.numel() != 4 * N * D * H * W):
-        raise FdnError("conv3d_dgrad_fused_multi: y_prev OR its sign mask of 4 x %d int16 words" % (N * D * H * W))
-    tz = (ctypes.c_void_p * n)(*[_p(t, "dz") for t in dzs])
-    tw = (ctypes.c_void_p * n)(*[_p(t, "wpack") for t in wpacks_dgrad])
-    check(_lib.load().fdn_conv64_dgrad_fused_multi(tz, tw, n, _p(dxpad, "dxpad"), _p(skip, allow_none=True), _p(y_prev, allow_none=True),
-                                                   None if mask is None else _pm(mask), act, float(alpha), _p(out, "out"), N, D, H, W, int(algo),
-                                                   _stream()), "fdn_conv64_dgrad_fused_multi")
+    tz = (ctypes.c_void_p * n)(*[pa(t, "dz") for t in dzs])
+    tw = (ctypes.c_void_p * n)(*[pa(t, "wpack") for t in wpacks_dgrad])
+    check(getattr(_lib.load(), entry)(tz, tw, n, _p(dxpad, "dxpad"), pa(skip, allow_none=True), pa(y_prev, allow_none=True),
+                                      _mask_ptr(mask, N * D * H * W, "conv3d_dgrad_fused_multi"), act, float(alpha), pa(out, "out"),
+                                      N, D, H, W, *algo, _stream()), entry)
     return out
+
+
+def conv3d_dgrad_fused_multi(dzs, wpacks_dgrad, dxpad, out, skip=None, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA, algo=ALGO_AUTO, mask=None):
+    """The fused dgrad of 1..3 64->64 layers that share their input, as ONE launch: out / dxpad receive what chained conv3d_dgrad_fused
+    calls (skip = the running sum) would leave, to fp32 rounding -- the sum over the sources is formed in the kernel's registers.  Only
+    where conv64_mask_ok(N, D, H, W, algo); the packs must be views of one pack buffer.  y_prev or mask (its sign mask) or neither."""
+    if mask is not None and y_prev is not None:
+        raise FdnError("conv3d_dgrad_fused_multi: y_prev OR its sign mask")
+    return _dgrad_fused_multi("fdn_conv64_dgrad_fused_multi", _p, dzs, wpacks_dgrad, dxpad, out, skip, y_prev, act, alpha, mask, int(algo))
+
+
+def conv64_dgrad_multi_ok(algos):
+    """May 64->64 layers with these algorithms go out as one conv3d_dgrad_fused_multi launch (on a grid where conv64_mask_ok)?  fp32: the
+    launch has one algorithm."""
+    return len(set(algos)) == 1
 
 
 def fold_halo_border(dxpads, out, skip=None, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA):
@@ -340,10 +358,9 @@ def wgrad_batch_workspace_bytes(n_layers, N, D, H, W):
     return int(_lib.load().fdn_conv3d_wgrad_batch_workspace_bytes(n_layers, N, D, H, W))
 
 
-def conv3d_wgrad_batch(xs, dzs, dws, dbiases=None, workspace=None, algo=ALGO_AUTO):
-    """Weight gradients of several 64->64 3x3x3 layers that share one grid in ONE launch (fdn_conv3d_wgrad_batch): xs / dzs / dws are
-    lists of tensors (N,D,H,W,64) / (N,D,H,W,64) / (3,3,3,64,64); dbiases: None or a list with None / (64,) entries."""
-    import ctypes
+def _wgrad_batch(entry, pa, need, xs, dzs, dws, dbiases, workspace, *algo):
+    """conv3d_wgrad_batch of either storage type: `entry` names the library's entry point, pa checks an activation pointer, need is
+    wgrad_batch_workspace_bytes of the module, algo is (algo,) where the entry point takes one."""
     n = len(xs)
     if not (n and len(dzs) == n and len(dws) == n and (dbiases is None or len(dbiases) == n)):
         raise ValueError("conv3d_wgrad_batch: xs, dzs, dws (and dbiases) must be lists of one length")
@@ -351,15 +368,26 @@ def conv3d_wgrad_batch(xs, dzs, dws, dbiases=None, workspace=None, algo=ALGO_AUT
     for x, dz in zip(xs, dzs):
         if tuple(x.shape) != (N, D, H, W, 64) or tuple(dz.shape) != (N, D, H, W, 64):
             raise ValueError("conv3d_wgrad_batch: every layer must have the grid %s with 64 channels" % ((N, D, H, W),))
-    need = wgrad_batch_workspace_bytes(n, N, D, H, W)
+    nbytes = need(n, N, D, H, W)
     if workspace is None:
-        workspace = torch.empty((need + 3) // 4, device=xs[0].device, dtype=torch.float32)
-    table = lambda ts, name: (ctypes.c_void_p * n)(*[None if t is None else _p(t, name) for t in ts])
-    tx, tz, tw = table(xs, "x"), table(dzs, "dz"), table(dws, "dw")
-    tb = table(dbiases, "dbias") if dbiases is not None and any(b is not None for b in dbiases) else None
-    check(_lib.load().fdn_conv3d_wgrad_batch(tx, tz, tw, tb, n, _p(workspace, "workspace"), workspace.numel() * workspace.element_size(),
-                                            N, D, H, W, int(algo), _stream()), "fdn_conv3d_wgrad_batch")
+        workspace = torch.empty((nbytes + 3) // 4, device=xs[0].device, dtype=torch.float32)
+    table = lambda ptr, ts, name, **kw: (ctypes.c_void_p * n)(*[ptr(t, name, **kw) for t in ts])
+    tx, tz, tw = table(pa, xs, "x"), table(pa, dzs, "dz"), table(_p, dws, "dw")
+    tb = table(_p, dbiases, "dbias", allow_none=True) if dbiases is not None and any(b is not None for b in dbiases) else None
+    check(getattr(_lib.load(), entry)(tx, tz, tw, tb, n, _p(workspace, "workspace"), workspace.numel() * workspace.element_size(),
+                                      N, D, H, W, *algo, _stream()), entry)
     return dws
+
+
+def conv3d_wgrad_batch(xs, dzs, dws, dbiases=None, workspace=None, algo=ALGO_AUTO):
+    """Weight gradients of several 64->64 3x3x3 layers that share one grid in ONE launch (fdn_conv3d_wgrad_batch): xs / dzs / dws are
+    lists of tensors (N,D,H,W,64) / (N,D,H,W,64) / (3,3,3,64,64); dbiases: None or a list with None / (64,) entries."""
+    return _wgrad_batch("fdn_conv3d_wgrad_batch", _p, wgrad_batch_workspace_bytes, xs, dzs, dws, dbiases, workspace, int(algo))
+
+
+def conv64_wgrad_batch_ok(algo=ALGO_AUTO):
+    """May the weight gradient of a 64->64 layer with this algorithm join a conv3d_wgrad_batch launch?  fp32: the Winograd kernels' batch."""
+    return algo in (ALGO_AUTO, ALGO_WINO_H2, ALGO_WINO_BF16X3)
 
 
 def upsample_trilinear_fwd(x, R, out=None):
@@ -448,8 +476,6 @@ def volume_metrics(pred, truth, mask, out=None, scratch=None):
         raise FdnError("volume_metrics: mask must be (1,%d,%d,%d) or (%d,%d,%d,%d), got %s" % (X, Y, Z, F, X, Y, Z, tuple(mask.shape)))
     p_pred = _p64(pred, "pred") if pred.dtype == torch.float64 else _p(pred, "pred")
     p_truth, p_mask = _p(truth, "truth"), _p(mask, "mask")
-    if truth.dtype != torch.float32 or mask.dtype != torch.float32:
-        raise FdnError("volume_metrics: truth and mask must be float32 (got %s, %s)" % (truth.dtype, mask.dtype))
     if truth.device != pred.device or mask.device != pred.device:
         raise FdnError("volume_metrics: pred, truth and mask must live on one device")
     if out is None:
@@ -472,7 +498,7 @@ def volume_metrics(pred, truth, mask, out=None, scratch=None):
 def l2_sumsq(w_flat, is_kernel, out=None):
     if out is None:
         out = torch.empty((1,), device=w_flat.device, dtype=torch.float32)
-    check(_lib.load().fdn_l2_sumsq(_p(w_flat), _p(is_kernel), w_flat.numel(), _p(out), _stream()), "fdn_l2_sumsq")
+    check(_lib.load().fdn_l2_sumsq(_p(w_flat), _pu8(is_kernel, "is_kernel"), w_flat.numel(), _p(out), _stream()), "fdn_l2_sumsq")
     return out
 
 
@@ -488,12 +514,12 @@ def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_
     if lr_t_dev is not None:
         if not lr_t_dev.is_cuda or lr_t_dev.dtype != torch.float32 or lr_t_dev.numel() < 1:
             raise FdnError("adam_step: lr_t_dev must hold one float32 on the GPU")
-        check(_lib.load().fdn_adam_step_dev(_p(w), _p(g), _p(m), _p(v), _p(is_kernel), w.numel(), _p(lr_t_dev), float(b1), float(b2),
+        check(_lib.load().fdn_adam_step_dev(_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel"), w.numel(), _p(lr_t_dev), float(b1), float(b2),
                                             float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
                                             _p(sumsq_partials, allow_none=True), _stream()),
               "fdn_adam_step_dev")
         return
-    check(_lib.load().fdn_adam_step(_p(w), _p(g), _p(m), _p(v), _p(is_kernel), w.numel(), float(lr_t), float(b1), float(b2),
+    check(_lib.load().fdn_adam_step(_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel"), w.numel(), float(lr_t), float(b1), float(b2),
                                     float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
                                     _p(sumsq_partials, allow_none=True), _stream()),
           "fdn_adam_step")
@@ -516,7 +542,7 @@ def l2_sumsq_partials(w_flat, is_kernel, partials):
     """ADAM_PARTIALS per-block sums of the kernel parameters' squares (what adam_step leaves behind), for parameters no Adam step has touched."""
     if partials.numel() < ADAM_PARTIALS:
         raise FdnError("l2_sumsq_partials: partials needs %d floats" % ADAM_PARTIALS)
-    check(_lib.load().fdn_l2_sumsq_partials(_p(w_flat), _p(is_kernel), w_flat.numel(), _p(partials), _stream()), "fdn_l2_sumsq_partials")
+    check(_lib.load().fdn_l2_sumsq_partials(_p(w_flat), _pu8(is_kernel, "is_kernel"), w_flat.numel(), _p(partials), _stream()), "fdn_l2_sumsq_partials")
     return partials
 
 

@@ -202,3 +202,40 @@ def test_mask_query_and_multi_source_argument_checks_need_no_gpu(fdn):
     assert multi(fake(0x10000, 0x20000), fake(0x30000, 0x40000), 4, *args) != 0 and "1..3" in err()
     assert multi(fake(0x10000, 0x20000), fake(0x30000, 0x30000 + (1 << 31)), 2, *args) != 0 and "1 GiB" in err()
     assert multi(fake(0x10000, None), fake(0x30000, 0x40000), 2, *args) != 0 and "source 1" in err()
+
+
+def _flownet_model_ast():
+    import ast
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    tree = ast.parse(open(os.path.join(root, "4dflownet_amd", "network.py")).read())
+    cls, = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "FlowNetModel"]
+    return ast, cls
+
+
+def test_both_operator_modules_offer_what_the_model_reaches_through_self_ops(fdn):
+    """FlowNetModel selects ops or ops_bf16 once (self.ops) and asks nothing more about the storage type: every name it reaches through
+    self.ops exists in both modules, and the functions among them have the same parameters, order and defaults."""
+    import inspect
+    from importlib import import_module
+    ast, cls = _flownet_model_ast()
+    names = sorted({n.attr for n in ast.walk(cls) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Attribute) and
+                    n.value.attr == "ops" and isinstance(n.value.value, ast.Name) and n.value.value.id == "self"})
+    assert {"conv3d_fwd", "conv3d_dgrad_fused", "conv3d_wgrad", "conv3d_dgrad_fused_multi", "conv3d_wgrad_batch"} <= set(names), names
+    mods = [fdn.ops, import_module("4dflownet_amd.ops_bf16")]
+    for name in names:
+        a, b = (getattr(m, name, None) for m in mods)
+        assert a is not None and b is not None, "%s is missing in ops%s" % (name, "" if a is None else "_bf16")
+        assert callable(a) == callable(b), name
+        if callable(a):
+            assert inspect.signature(a) == inspect.signature(b), (name, str(inspect.signature(a)), str(inspect.signature(b)))
+
+
+def test_the_model_calls_no_operator_module_by_name():
+    """No method of FlowNetModel calls ops.<f>(...) or ops_bf16.<f>(...): a launch issued past self.ops would take one storage type's
+    kernels in both modes (and bench.py's LaunchTimer, which wraps the attributes of model.ops, would not see it).  Constants such as
+    ops.ACT_RELU are fine."""
+    ast, cls = _flownet_model_ast()
+    direct = [(n.lineno, "%s.%s" % (n.func.value.id, n.func.attr)) for n in ast.walk(cls)
+              if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and isinstance(n.func.value, ast.Name) and
+              n.func.value.id in ("ops", "ops_bf16")]
+    assert not direct, direct

@@ -25,10 +25,10 @@ def l2_rel(got, ref):
     return np.linalg.norm((got - ref).ravel()) / max(np.linalg.norm(ref.ravel()), 1e-30)
 
 
-def make(P, R, LB, HB, seed, dtype, wscale=3.0):
+def make(P, R, LB, HB, seed, dtype, wscale=3.0, conv_algo=None):
     trainer_mod = importlib.import_module("4dflownet_amd.trainer")
     tc = trainer_mod.TrainerController(P, R, initial_learning_rate=1e-3, quicksave_enable=False, low_resblock=LB,
-                                       hi_resblock=HB, seed=seed, dtype=dtype)
+                                       hi_resblock=HB, seed=seed, dtype=dtype, conv_algo=conv_algo)
     params = O.init_params(seed, LB, HB, np.float64)
     rng = np.random.default_rng(seed + 1)
     arrays = []
@@ -182,3 +182,25 @@ def test_bf16_multi_source_head_dgrad_matches_the_chained_launches(fdn):
     assert torch.isfinite(grads[0]).all() and not torch.equal(grads[0], grads[1])      # (the multi-source path really ran)
     rel = ((grads[0] - grads[1]).double().norm() / grads[1].double().norm()).item()
     assert rel <= 1e-2, rel
+
+
+def test_bf16_training_ignores_the_conv_algo_of_a_layer(fdn):
+    """The bf16 kernels have one algorithm: a model built with conv_algo = {first head 64->64 layer: "direct"} trains to the same weights,
+    bit for bit, as one built with conv_algo = None -- its three head dgrads still go out as ONE multi-source launch (a rule "one launch
+    needs one algorithm", which holds in fp32, would chain them and round the running sum to bf16 twice more) and its forward, dgrad and
+    weight-gradient launches are the same.  model.conv_algo keeps what it was given in both modes."""
+    P, R, LB, HB, B = 8, 2, 1, 1, 2
+    batch = O.synthetic_batch(B, P, R, seed=47)
+    network = importlib.import_module("4dflownet_amd.network")
+    first_head = network.layer_specs(LB, HB)[-6][0]
+    ws = []
+    for conv_algo in ({first_head: "direct"}, None):
+        tc, _ = make(P, R, LB, HB, seed=5, dtype="bfloat16", conv_algo=conv_algo)
+        assert (tc.model.layers[-6].name, tc.model.layers[-6].cin, tc.model.layers[-6].cout) == (first_head, 64, 64)
+        assert tc.model.conv_algo[first_head] == (fdn.ops.ALGO_DIRECT if conv_algo else fdn.ops.ALGO_AUTO)
+        assert tc.model.multi_dgrad
+        tc.model.batch_wgrad = False
+        losses = [tc.train_step(batch).clone() for _ in range(3)]
+        ws.append((tc.model.flat_w.clone(), torch.stack([l.float().reshape(-1) for l in losses])))
+    assert torch.isfinite(ws[0][0]).all()
+    assert torch.equal(ws[0][1], ws[1][1]) and torch.equal(ws[0][0], ws[1][0])
