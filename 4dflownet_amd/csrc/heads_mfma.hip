@@ -8,8 +8,13 @@
 //               dx[i][c] = act'(y_prev[i][c]) sum_t A[i][t] w[t][c]      (V x 27) x (27 x 64) GEMM
 //               dW[t][c] = sum_i A[i][t] x[i][c]                         (27 x V) x (V x 64) GEMM
 // so every 64-channel row is touched once (forward: once per tile incl. halo) and the kernels run at the HBM roof.
-// fp32 storage: all three use v_mfma_f32_32x32x2_f32 (K is 64, 27 or the voxel count): fp32 products and accumulation exactly like the
-// VALU kernels they replace.  bf16 storage (T = bf16 bits): v_mfma_f32_32x32x16_bf16 on operands split into bf16 pieces -- forward and
+// fp32 storage: the input and weight gradients use v_mfma_f32_32x32x2_f32 (K is 27 or the voxel count): fp32 products and accumulation
+// like the VALU kernels they replace.  The FORWARD does not multiply in fp32 (round 6): x and w are each split exactly into three bf16
+// pieces (fdn_split3) and six of the nine cross terms go through v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- every product within
+// 2^-22 of the exact one (|mid| <= 2^-8 |v|, |lo| <= 2^-17 |v|: the three dropped terms are below 2^-24 + 2^-34 of it, the last fp32
+// addition rounds by 2^-24), unconditionally, for conv_algo = "direct" as well;
+// tests/test_gpu_thin_operand_range.py pins that with single-product probes, tests/test_gpu_pow2_scaling.py the operand range it holds on.
+// bf16 storage (T = bf16 bits): v_mfma_f32_32x32x16_bf16 on operands split into bf16 pieces -- forward and
 // input gradient on hi + lo pairs (exact to 2^-17; their results are rounded to bf16 anyway), the weight gradient with EXACT products
 // (x is bf16, the fp32 scalars split into three pieces).  The weight gradient took two attempts: with lane = voxel (A transposed through
 // wave-private LDS planes, as in the fp32 path) the bf16 MFMAs made it SLOWER, 479 -> 572 us at (4,128^3) -- the write -> wait -> read

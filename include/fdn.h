@@ -121,7 +121,12 @@ int fdn_pack_conv64_weights_batch_streams(const float* w_base, const int64_t* w_
  * SR4DFlowNet.py:23 is never materialised].  x2, wpack, bias, residual may be NULL where unused.
  * Output rows are written at y[voxel*ldy + y_coff + c] (ldy=Cout,y_coff=0 for a dense tensor;
  * the three 64->1 heads write straight into the (N,V,3) prediction: SR4DFlowNet.py:49).
- * algo: FDN_ALGO_AUTO | FDN_ALGO_DIRECT | FDN_ALGO_WINO_W, consulted by the (64,64,3) path only (see above); here and in the entry points below. */
+ * algo: FDN_ALGO_AUTO | FDN_ALGO_DIRECT | FDN_ALGO_WINO_W, consulted by the (64,64,3) path only (see above); here and in the entry points below.
+ * Arithmetic of the (64,1,3) head, whatever `algo`: x . w is formed on the bf16 matrix pipe with fp32 accumulation -- fp32 storage: x and w
+ * each split exactly into three bf16 pieces, six of the nine cross terms, every product within 2^-22 of the fp32 operands' exact product;
+ * bf16 storage (fdn_conv3d_fwd_bf16): w as two pieces, within 2^-16 -- and, like every conv, fold and upsample entry point of this header,
+ * the result commutes bit for bit with power-of-two scalings of its operands; both hold, and are tested, for non-zero operands with
+ * 2^-46 <= |v| < 2^47 (values of 2^-6 <= |v| < 2^7 scaled by up to 2^+-40) whose two scales multiply to within 2^+-60. */
 int fdn_conv3d_fwd(const float* x, const float* x2, const float* w, const float* wpack, const float* bias,
                    const float* residual, float* y, int N, int D, int H, int W, int Cin, int Cout, int K,
                    int ldy, int y_coff, int act, float alpha, int algo, void* stream);
