@@ -53,6 +53,7 @@ SIGNATURES = {
     "fdn_l2_sumsq": (c_i, [c_fp, c_fp, c_i64, c_fp, c_fp]),
     "fdn_adam_step": (c_i, [c_fp] * 5 + [c_i64] + [c_f] * 5 + [c_fp, c_fp, c_fp]),
     "fdn_adam_step_dev": (c_i, [c_fp] * 5 + [c_i64, c_fp] + [c_f] * 4 + [c_fp, c_fp, c_fp]),
+    "fdn_adam_step_masked": (c_i, [c_fp] * 6 + [c_i64, c_f, c_fp] + [c_f] * 4 + [c_fp, c_fp, c_fp]),
     "fdn_sum_partials": (c_i, [c_fp, c_i, c_fp, c_fp]),
     "fdn_grad_accumulate": (c_i, [c_fp, c_fp, c_i64, c_i, c_fp]),
     "fdn_l2_sumsq_partials": (c_i, [c_fp, c_fp, c_i64, c_fp, c_fp]),

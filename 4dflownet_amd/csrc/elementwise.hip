@@ -698,12 +698,16 @@ __global__ __launch_bounds__(1024) void l2_sumsq_kernel(const float* __restrict_
 // accum != 0 (fdn_grad_accumulate): the sum of micro-batch gradient buffers as a path of this kernel selected by one by-value int --
 // w[i] = g[i] (ACCUM_FIRST) or w[i] + g[i] (ACCUM_ADD); m .. sumsq are not read.  Scalar accesses: w and g are bucket slices at any
 // float offset, and the 13.4 MB of cfg2 are not where the step's time is.
+// frozen != null (fdn_adam_step_masked: fine-tuning, one byte per parameter like isk): an element with frozen[i] != 0 keeps w, m and v --
+// g[i], m[i] and v[i] are neither loaded nor stored -- and still adds w[i]^2 to its block's sum when it is a kernel: the regulariser
+// value covers every kernel (TrainerController.py:129-141).  An element with frozen[i] == 0 takes the statements below unchanged.
 #define ACCUM_FIRST 1
 #define ACCUM_ADD 2
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, const uint8_t* __restrict__ isk, int64_t n, float lr_t_host,
                                                    const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float l2s_host,
-                                                   const float* __restrict__ l2s_dev, float* __restrict__ sumsq, int accum) {
+                                                   const float* __restrict__ l2s_dev, float* __restrict__ sumsq, int accum,
+                                                   const uint8_t* __restrict__ frozen) {
     if (accum) {                                                     // fdn_grad_accumulate: w is the accumulator, g one micro-batch's gradients;
         const bool first = accum == ACCUM_FIRST;                     // nothing else is read.  Uniform, ahead of the Adam path's first load
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -718,15 +722,18 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const 
     float ss = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float wi = w[i];
-        float gi = g[i];
         const bool k = isk[i] != 0;
-        if (k) gi += l2s * wi;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float wn = wi - lr_t * mi / (sqrtf(vi) + eps);
-        w[i] = wn;
+        float wn = wi;
+        if (!(frozen && frozen[i])) {
+            float gi = g[i];
+            if (k) gi += l2s * wi;
+            const float mi = b1 * m[i] + (1.f - b1) * gi;
+            const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+            m[i] = mi;
+            v[i] = vi;
+            wn = wi - lr_t * mi / (sqrtf(vi) + eps);
+            w[i] = wn;
+        }
         if (k) ss += wn * wn;
     }
     if (sumsq) {
@@ -1011,7 +1018,7 @@ extern "C" int fdn_adam_step(float* w, const float* g, float* m, float* v, const
     // fixed grid of FDN_ADAM_PARTIALS blocks when partials are requested (blocks beyond the data write 0)
     const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);
     hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       lr_t, (const float*)nullptr, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0);
+                       lr_t, (const float*)nullptr, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, (const uint8_t*)nullptr);
     FDN_CHECK_LAUNCH("adam_kernel");
     return FDN_OK;
 }
@@ -1024,8 +1031,25 @@ extern "C" int fdn_adam_step_dev(float* w, const float* g, float* m, float* v, c
     FDN_REQUIRE(n > 0, "fdn_adam_step_dev: n=%lld must be positive", (long long)n);
     const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);
     hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       0.f, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0);
+                       0.f, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, (const uint8_t*)nullptr);
     FDN_CHECK_LAUNCH("adam_kernel");
+    return FDN_OK;
+}
+
+extern "C" int fdn_adam_step_masked(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, const uint8_t* frozen, int64_t n,
+                                    float lr_t, const float* lr_t_dev, float b1, float b2, float eps, float l2_grad_scale,
+                                    const float* l2_scale_dev, float* sumsq_partials, void* stream) {
+    FDN_REQUIRE(w, "fdn_adam_step_masked: w is NULL");
+    FDN_REQUIRE(g, "fdn_adam_step_masked: g is NULL");
+    FDN_REQUIRE(m, "fdn_adam_step_masked: m is NULL");
+    FDN_REQUIRE(v, "fdn_adam_step_masked: v is NULL");
+    FDN_REQUIRE(is_kernel, "fdn_adam_step_masked: is_kernel is NULL");
+    FDN_REQUIRE(frozen, "fdn_adam_step_masked: frozen is NULL (fdn_adam_step / fdn_adam_step_dev update every element)");
+    FDN_REQUIRE(n > 0, "fdn_adam_step_masked: n=%lld must be positive", (long long)n);
+    const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);       // the grid rule of fdn_adam_step
+    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
+                       lr_t, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, frozen);
+    FDN_CHECK_LAUNCH("adam_kernel (masked)");
     return FDN_OK;
 }
 
@@ -1041,7 +1065,7 @@ extern "C" int fdn_grad_accumulate(float* acc, const float* g, int64_t n, int fi
                 (long long)(a > b ? a - b : b - a), (long long)n);
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, acc, g, (float*)nullptr, (float*)nullptr,
                        (const uint8_t*)nullptr, n, 0.f, (const float*)nullptr, 0.f, 0.f, 0.f, 0.f, (const float*)nullptr, (float*)nullptr,
-                       first ? ACCUM_FIRST : ACCUM_ADD);
+                       first ? ACCUM_FIRST : ACCUM_ADD, (const uint8_t*)nullptr);
     FDN_CHECK_LAUNCH("adam_kernel (grad accumulate)");
     return FDN_OK;
 }

@@ -7,7 +7,11 @@ callable on 6 arrays (B,P,P,P,1), has .predict(list), .trainable_variables, .sav
 Parameters live in ONE flat fp32 device buffer in layer CREATION order (kernel, bias per layer: conv3d, conv3d_1, ...
 conv3d_35), gradients in a second flat buffer of the same layout, so the data-parallel all-reduce and the Adam step are one
 call each.  Keras' own `trainable_variables` order (depth-sorted layers, keras_layer_order) differs from creation order and
-is what optimizer.pkl uses: keras_variable_order() / trainable_variable_names() translate between the two."""
+is what optimizer.pkl uses: keras_variable_order() / trainable_variable_names() translate between the two.
+
+Fine-tuning: every layer has the Keras `trainable` flag (model.layers[i].trainable = False, or set_trainable).  trainable_variables and
+the two helpers above then cover the trainable layers only, `variables` / get_weights / save all of them; backward_plan says what
+backward() launches and forward(training=True) retains for a given set."""
 import contextlib
 import math
 import os
@@ -66,6 +70,103 @@ def keras_layer_order(low_resblock=8, hi_resblock=4):
     return [2, 0, 3, 1] + list(range(4, n_trunk)) + [h, h + 2, h + 4, h + 1, h + 3, h + 5]
 
 
+def trainable_flags(spec, low_resblock=8, hi_resblock=4):
+    """One bool per layer of layer_specs (creation order) for a FlowNetModel.set_trainable spec: "all", "hires" (the hi-res ResBlocks and the
+    six head layers), "heads" (the six head layers), or an iterable of layer names (ValueError for a name the model does not have)."""
+    names = [s[0] for s in layer_specs(low_resblock, hi_resblock)]
+    n = len(names)
+    if spec is None or (isinstance(spec, str) and spec == "all"):
+        return [True] * n
+    if isinstance(spec, str) and spec == "hires":
+        return [i >= 6 + 2 * low_resblock for i in range(n)]
+    if isinstance(spec, str) and spec == "heads":
+        return [i >= n - 6 for i in range(n)]
+    if isinstance(spec, str):
+        raise ValueError("set_trainable: %r is not 'all', 'hires', 'heads' or an iterable of layer names" % (spec,))
+    want = set(spec)
+    unknown = sorted(str(k) for k in want if k not in names)
+    if unknown:
+        raise ValueError("set_trainable: unknown layer(s) %s" % unknown)
+    return [nm in want for nm in names]
+
+
+def variable_names(low_resblock=8, hi_resblock=4, flags=None):
+    """Keras variable names ('conv3d_7/kernel:0', 'conv3d_7/bias:0') in creation order, of the layers whose flag is set (None: all)."""
+    out = []
+    for i, (name, _, _, _, ub) in enumerate(layer_specs(low_resblock, hi_resblock)):
+        if flags is None or flags[i]:
+            out.append("%s/kernel:0" % name)
+            if ub:
+                out.append("%s/bias:0" % name)
+    return out
+
+
+def keras_variable_positions(low_resblock=8, hi_resblock=4, flags=None):
+    """Positions into variable_names(..., flags) in Keras `trainable_variables` order: keras_layer_order restricted to the flagged layers
+    (Keras lists the variables of the trainable layers in the order of model.layers, so a subset keeps its relative order)."""
+    first = {}
+    k = 0
+    for i, (_, _, _, _, ub) in enumerate(layer_specs(low_resblock, hi_resblock)):
+        if flags is None or flags[i]:
+            first[i] = (k, 2 if ub else 1)
+            k += first[i][1]
+    out = []
+    for i in keras_layer_order(low_resblock, hi_resblock):
+        if i in first:
+            out.extend(range(first[i][0], first[i][0] + first[i][1]))
+    return out
+
+
+def backward_plan(low_resblock, hi_resblock, flags, upsample=True):
+    """What backward() has to launch, and forward(training=True) to retain, when only the layers with flags[i] set are trainable.  Pure:
+    no tensors, no device.  Layer i (creation order) gets
+      wgrad[i]   its weight (+bias) gradient is computed: the layer is trainable;
+      dgrad[i]   the gradient w.r.t. its input is computed: some trainable layer lies upstream of that input.
+    The graph (SR4DFlowNet.py:7-51): pc -> 0 -> 1 and phase -> 2 -> 3 meet in the 1x1 layer 4, then 5, then the ResBlocks (two layers
+    each; the skip adds nothing upstream that the convs do not have), the upsample behind block `low_resblock`, and the three heads
+    (64->64 then 64->1) on the last trunk tensor.  Every layer below layer i of the trunk is upstream of it, so in the trunk
+    dgrad[i] = any(flags[:i]); backward stops at the lowest trainable layer.
+    Derived facts: any_trainable; heads_to_trunk (the heads' input gradient is formed); need_at[k] (the gradient of trunk tensor k is
+    needed: k = 0 the output of layer 5, k = j that of block j); through_upsample; conv1x1_dgrad; branch_phase / branch_pc (descend that
+    branch behind the 1x1); dbias_prev[h] (head h's 64->64 bias gradient, emitted by the folded 64->1 dgrad).
+    keep / masks: for each tensor / sign mask forward(training=True) can retain, whether backward reads it: phase, pc, a0, a1, p0, p1,
+    c0, trunk[k], up_out, h[j] (a block's inner activation), heads[h].  `upsample`: res_increase > 1 (there is an up_out)."""
+    LB, HB = int(low_resblock), int(hi_resblock)
+    nb = LB + HB
+    nt = 6 + 2 * nb
+    n = nt + 6
+    t = [bool(f) for f in flags]
+    if len(t) != n:
+        raise ValueError("backward_plan: %d flags for %d layers" % (len(t), n))
+    below = [any(t[:i]) for i in range(n + 1)]            # below[i]: a layer of index < i is trainable
+    dgrad = [False, t[0], False, t[2]] + [below[i] for i in range(4, nt)]
+    for h in range(3):
+        dgrad += [below[nt], below[nt] or t[nt + 2 * h]]
+    need_at = [below[6 + 2 * k] for k in range(nb + 1)]
+    head1 = any(t[nt + 2 * h] for h in range(3))
+    keep = dict(phase=t[2], pc=t[0], a0=t[1] or dgrad[1], p0=t[3] or dgrad[3], a1=t[4] or dgrad[4], p1=t[4] or dgrad[4], c0=t[5] or dgrad[5],
+                trunk=[], up_out=False, h=[t[7 + 2 * j] or dgrad[7 + 2 * j] for j in range(nb)],
+                heads=[t[nt + 2 * h + 1] or dgrad[nt + 2 * h + 1] for h in range(3)])
+    masks = dict(trunk=[], h=[dgrad[7 + 2 * j] for j in range(nb)], heads=[dgrad[nt + 2 * h + 1] for h in range(3)])
+    for k in range(nb + 1):
+        # readers of trunk tensor k: the upsample's act' (it feeds the upsample), else the next block's first layer (x of its weight
+        # gradient, act' of its dgrad) or, for the last one, the heads (x of the three 64->64 weight gradients, act' of their dgrad)
+        if upsample and k == LB:
+            keep["trunk"].append(need_at[k])
+            masks["trunk"].append(False)
+            # linear producer: read as x of a weight gradient only -- and, where the heads sit on it, as the shape of their input gradient
+            keep["up_out"] = (head1 or below[nt]) if k == nb else t[6 + 2 * k]
+        elif k == nb:
+            keep["trunk"].append(head1 or below[nt])
+            masks["trunk"].append(below[nt])
+        else:
+            keep["trunk"].append(t[6 + 2 * k] or dgrad[6 + 2 * k])
+            masks["trunk"].append(dgrad[6 + 2 * k])
+    return dict(wgrad=t, dgrad=dgrad, any_trainable=below[n], all_trainable=all(t), heads_to_trunk=below[nt], need_at=need_at,
+                through_upsample=need_at[LB], conv1x1_dgrad=below[4], branch_phase=t[2] or t[3], branch_pc=t[0] or t[1],
+                dbias_prev=[t[nt + 2 * h] for h in range(3)], keep=keep, masks=masks)
+
+
 def slow_grid_warning(N, D, H, W):
     """The warning for an fp32 (N, D, H, W) grid whose 64->64 layers FDN_ALGO_AUTO runs off the 2-D Winograd kernels -- all of them on the
     direct kernels, or on the 1-D Winograd kernels -- or None.  The library's own selection decides (fdn_conv64_pack_streams)."""
@@ -80,7 +181,8 @@ def slow_grid_warning(N, D, H, W):
 
 
 class _Layer:
-    __slots__ = ("name", "k", "cin", "cout", "w", "b", "gw", "gb", "wp_f", "wp_d", "w_off", "b_off")
+    """`trainable` (default True) is the Keras flag: `model.layers[i].trainable = False` freezes the layer from the next forward(training=True)."""
+    __slots__ = ("name", "k", "cin", "cout", "w", "b", "gw", "gb", "wp_f", "wp_d", "w_off", "b_off", "trainable")
 
 
 class _T:
@@ -137,6 +239,7 @@ class FlowNetModel:
         for name, k, ci, co, ub in self.specs:
             L = _Layer()
             L.name, L.k, L.cin, L.cout = name, k, ci, co
+            L.trainable = True
             sz = k ** 3 * ci * co
             L.w_off = off
             L.w = self.flat_w[off:off + sz].view(k, k, k, ci, co)
@@ -160,6 +263,13 @@ class FlowNetModel:
         assert off == n
         self.is_kernel = torch.tensor(is_kernel, device=self.device)
         self._w64_offsets = torch.tensor([L.w_off for L in self.layers if L.wp_f is not None], device=self.device, dtype=torch.int64)
+        # fine-tuning: the flags the current plan was made for (layer.trainable is compared against them, _sync_trainable), what backward()
+        # launches and forward(training=True) retains under them (backward_plan), the device byte map of frozen parameters (None: none
+        # frozen) and the contiguous runs of trainable 64->64 layers in _packs
+        self._flags = (True,) * len(self.layers)
+        self._plan = backward_plan(self.low_resblock, self.hi_resblock, self._flags, upsample=self.res_increase > 1)
+        self._frozen_map = None
+        self._pack_runs = [(0, n64)] if n64 else []
         self.weights_version = 0       # bumped by weights_changed(): lets the trainer know whether Adam's sum-of-squares is current
         self._ws = None
         self._ws_bias = None
@@ -237,14 +347,73 @@ class FlowNetModel:
         self.flat_w.copy_(torch.from_numpy(flat))
         self.weights_changed()
 
-    def weights_changed(self):
-        """Re-derive the MFMA operand streams after any parameter update (Adam step, load_weights)."""
+    def weights_changed(self, trainable_only=False):
+        """Re-derive the MFMA operand streams after any parameter update (Adam step, load_weights).  trainable_only (the trainer, after an
+        optimiser step): frozen layers did not move, so only the trainable 64->64 layers are re-packed -- one launch per contiguous run of
+        them in the pack buffer; with every layer trainable that is the one launch over all of them."""
         self.weights_version += 1
-        if self._w64_offsets.numel():                      # all 64->64 layers, the streams in use (fp32), one launch
+        if not self._w64_offsets.numel():
+            return
+        if not trainable_only:                             # all 64->64 layers, the streams in use (fp32), one launch
             self.ops.pack_conv64_weights_batch(self.flat_w, self._w64_offsets, self._packs, streams=self._pack_streams)
+            return
+        self._sync_trainable()
+        for a, b in self._pack_runs:
+            if (a, b) == (0, self._w64_offsets.numel()):
+                self.ops.pack_conv64_weights_batch(self.flat_w, self._w64_offsets, self._packs, streams=self._pack_streams)
+            else:
+                self.ops.pack_conv64_weights_batch(self.flat_w, self._w64_offsets[a:b], self._packs[a:b], streams=self._pack_streams)
+
+    # ------------------------------------------------------------------ fine-tuning: frozen layers
+    def set_trainable(self, spec):
+        """Which layers train: "all", "hires" (the hi-res ResBlocks and the six head layers), "heads" (the six head layers) or an iterable
+        of layer names (ValueError for an unknown one).  The same as setting layer.trainable on every layer; takes effect from the next
+        forward(training=True)."""
+        for L, f in zip(self.layers, trainable_flags(spec, self.low_resblock, self.hi_resblock)):
+            L.trainable = f
+        self._sync_trainable()
+
+    def _sync_trainable(self):
+        """Bring the plan, the frozen byte map and the pack runs in line with the layers' `trainable` flags.  On a change the gradient
+        ranges of frozen layers are zeroed once: backward() never writes them afterwards, so accumulation and the data-parallel
+        all-reduce work on them unchanged."""
+        flags = tuple(bool(L.trainable) for L in self.layers)
+        if flags == self._flags:
+            return
+        self._flags = flags
+        self._plan = backward_plan(self.low_resblock, self.hi_resblock, flags, upsample=self.res_increase > 1)
+        self._cache = None                                 # retained under another plan
+        frozen = np.zeros(self.n_params, dtype=np.uint8)
+        for L, f in zip(self.layers, flags):
+            if not f:
+                hi = L.b_off + L.cout if L.b is not None else L.w_off + L.w.numel()
+                frozen[L.w_off:hi] = 1
+                self.flat_g[L.w_off:hi].zero_()
+        self._frozen_map = None if all(flags) else torch.from_numpy(frozen).to(self.device)
+        runs = []
+        f64 = [f for L, f in zip(self.layers, flags) if L.wp_f is not None]
+        for i, f in enumerate(f64):
+            if f and runs and runs[-1][1] == i:
+                runs[-1] = (runs[-1][0], i + 1)
+            elif f:
+                runs.append((i, i + 1))
+        self._pack_runs = runs
 
     @property
-    def trainable_variables(self):
+    def any_trainable(self):
+        self._sync_trainable()
+        return self._plan["any_trainable"]
+
+    @property
+    def frozen_map(self):
+        """One uint8 per parameter (like is_kernel), 1 in the ranges of frozen layers, on the device -- or None while every layer trains."""
+        self._sync_trainable()
+        return self._frozen_map
+
+    @property
+    def variables(self):
+        """Kernel, bias per layer, ALL layers in creation order (get_weights / set_weights / save / load_weights follow this, whatever is
+        frozen -- unlike Keras, which lists the non-trainable weights last; the weight files go by layer name anyway)."""
         out = []
         for L in self.layers:
             out.append(L.w)
@@ -252,32 +421,34 @@ class FlowNetModel:
                 out.append(L.b)
         return out
 
+    def variable_names(self):
+        """Keras variable names ('conv3d_7/kernel:0', 'conv3d_7/bias:0'), one per entry of self.variables."""
+        return variable_names(self.low_resblock, self.hi_resblock)
+
+    @property
+    def trainable_variables(self):
+        """The variables of the trainable layers, creation order (TrainerController.py:223-225 differentiates and updates these)."""
+        out = []
+        for L in self.layers:
+            if L.trainable:
+                out.append(L.w)
+                if L.b is not None:
+                    out.append(L.b)
+        return out
+
     def keras_variable_order(self):
         """Positions (into self.trainable_variables) in Keras `trainable_variables` order: see keras_layer_order."""
-        first = {}
-        k = 0
-        for i, L in enumerate(self.layers):
-            first[i] = (k, 2 if L.b is not None else 1)
-            k += first[i][1]
-        out = []
-        for i in keras_layer_order(self.low_resblock, self.hi_resblock):
-            out.extend(range(first[i][0], first[i][0] + first[i][1]))
-        return out
+        return keras_variable_positions(self.low_resblock, self.hi_resblock, [bool(L.trainable) for L in self.layers])
 
     def trainable_variable_names(self):
         """Keras variable names ('conv3d_7/kernel:0', 'conv3d_7/bias:0'), one per entry of self.trainable_variables (creation order)."""
-        out = []
-        for L in self.layers:
-            out.append("%s/kernel:0" % L.name)
-            if L.b is not None:
-                out.append("%s/bias:0" % L.name)
-        return out
+        return variable_names(self.low_resblock, self.hi_resblock, [bool(L.trainable) for L in self.layers])
 
     def get_weights(self):
-        return [t.detach().cpu().numpy().copy() for t in self.trainable_variables]
+        return [t.detach().cpu().numpy().copy() for t in self.variables]
 
     def set_weights(self, arrays):
-        tv = self.trainable_variables
+        tv = self.variables
         if len(arrays) != len(tv):
             raise ValueError("set_weights: expected %d arrays, got %d" % (len(tv), len(arrays)))
         for t, a in zip(tv, arrays):
@@ -394,13 +565,33 @@ class FlowNetModel:
     def _forward_body(self, phase, pc, training):
         R = self.res_increase
         Ls = self.layers
+        # training with frozen layers: retain, and request sign masks for, only what the plan says backward() reads.  With every layer
+        # trainable (`full`) the cache and the masks are what they always were.
+        full = True
+        if training:
+            self._sync_trainable()
+            full = self._plan["all_trainable"]
+            keep, masks = self._plan["keep"], self._plan["masks"]
+        kept = lambda t, what, i=None: t if full or (keep[what] if i is None else keep[what][i]) else None
+        linear = _T(None, ACT_NONE)                        # stands for the upsample's output where only its (absent) activation matters
+        want = lambda what, i: training and (full or masks[what][i])
         a0 = self._conv(pc, Ls[0], ACT_RELU)
         a1 = self._conv(a0, Ls[1], ACT_RELU)
         p0 = self._conv(phase, Ls[2], ACT_RELU)
         p1 = self._conv(p0, Ls[3], ACT_RELU)
+        if training:
+            a0, p0, phase, pc = kept(a0, "a0"), kept(p0, "p0"), kept(phase, "phase"), kept(pc, "pc")
         c0 = self._conv(p1, Ls[4], ACT_RELU, x2=a1)          # concat [phase, pc] never materialised (:23)
-        c1, m_c1 = self._conv_m(c0, Ls[5], ACT_RELU, want_mask=training)
+        if training:
+            a1, p1 = kept(a1, "a1"), kept(p1, "p1")
+        c1, m_c1 = self._conv_m(c0, Ls[5], ACT_RELU, want_mask=want("trunk", 0))
+        if training:
+            c0 = kept(c0, "c0")
         rb = _T(c1, ACT_RELU, m_c1)
+        rb_is = ("trunk", 0)                               # what rb is to the plan: trunk tensor k, or the upsample's output
+        if not full:
+            c1 = None                                      # (backward reads it through the trunk tensors below)
+        del m_c1
         blocks = []
         hmasks = []                                        # bf16 training: sign mask of every block's inner activation h (else None)
         up = None
@@ -409,26 +600,33 @@ class FlowNetModel:
         for i in range(nb + 1):
             if i == self.low_resblock and R > 1:
                 up_out = _T(self.ops.upsample_trilinear_fwd(rb.t, R), ACT_NONE)
-                up = (rb, up_out)
-                rb = up_out
+                up = (rb, up_out) if not training else (kept(rb, "trunk", i), kept(up_out, "up_out"))
+                rb, rb_is = up_out, ("up_out", None)
+                del up_out
             if i == nb:
                 break
-            h, m_h = self._conv_m(rb.t, Ls[li], ACT_LEAKY, want_mask=training)
-            out, m_out = self._conv_m(h, Ls[li + 1], ACT_LEAKY, residual=rb.t, want_mask=training)
-            blocks.append((rb, h, out))
+            h, m_h = self._conv_m(rb.t, Ls[li], ACT_LEAKY, want_mask=want("h", i))
+            out, m_out = self._conv_m(h, Ls[li + 1], ACT_LEAKY, residual=rb.t, want_mask=want("trunk", i + 1))
+            if full:
+                blocks.append((rb, h, out))
+            elif training:
+                blocks.append((kept(rb, *rb_is) or (linear if rb.act == ACT_NONE else None), kept(h, "h", i), None))
             hmasks.append(m_h)
-            rb = _T(out, ACT_LEAKY, m_out)
+            rb, rb_is = _T(out, ACT_LEAKY, m_out), ("trunk", i + 1)
+            del h, m_h, out, m_out
             li += 2
         pred = torch.empty(tuple(rb.t.shape[:4]) + (3,), device=self.device)
         heads = []
         gmasks = []                                         # bf16 training: sign masks of the three head activations (else None)
         for hidx in range(3):
-            g, m_g = self._conv_m(rb.t, Ls[li], ACT_RELU, want_mask=training)
+            g, m_g = self._conv_m(rb.t, Ls[li], ACT_RELU, want_mask=want("heads", hidx))
             self._conv(g, Ls[li + 1], ACT_NONE, out=pred, ldy=3, y_coff=hidx)
-            heads.append(g)
+            heads.append(g if not training else kept(g, "heads", hidx))
             gmasks.append(m_g)
+            del g, m_g
             li += 2
         if training:
+            rb = kept(rb, *rb_is)
             self._cache = dict(phase=phase, pc=pc, a0=a0, a1=a1, p0=p0, p1=p1, c0=c0, c1=c1, blocks=blocks, up=up,
                                rb=rb, heads=heads, hmasks=hmasks, gmasks=gmasks)
         return pred
@@ -565,6 +763,10 @@ class FlowNetModel:
         if c is None:
             raise FdnError("backward() without forward(training=True)")
         self._cache = None
+        # what to launch (backward_plan): a frozen layer gets no weight gradient -- its range of flat_g stays the zeros _sync_trainable
+        # left --, and no input gradient is formed below the lowest trainable layer.  forward(training=True) retained under the same plan.
+        plan = self._plan
+        wg, dg = plan["wgrad"], plan["dgrad"]
         Ls = self.layers
         R = self.res_increase
         rb = c["rb"]
@@ -574,29 +776,40 @@ class FlowNetModel:
 
         # three heads fan into rb: chain the interior accumulation through `dz` (skip aliases the output),
         # apply act'(rb) on the last one, then one border fold over the three padded scratches
-        dz = torch.empty_like(rb.t)
+        to_trunk = plan["heads_to_trunk"]
+        dz = torch.empty_like(rb.t) if to_trunk else None
         pads = []
         # ONE multi-source launch forms the sum of the three input gradients in its registers (ops.conv3d_dgrad_fused_multi; fp32: on the
         # grids of the F(4,3) x F(4,3) kernels) instead of three chained launches that re-read and re-write the running sum
-        multi = (self.multi_dgrad and self.ops.conv64_dgrad_multi_ok([self.conv_algo[Ls[li + 2 * h].name] for h in range(3)])
+        multi = (to_trunk and self.multi_dgrad and self.ops.conv64_dgrad_multi_ok([self.conv_algo[Ls[li + 2 * h].name] for h in range(3)])
                  and self._mask_ok(rb.t, Ls[li]))
         dz_gs = []
         for hidx in range(3):
             L1, L2 = Ls[li], Ls[li + 1]
             g = c["heads"][hidx]
             c["heads"][hidx] = None
-            self._wgrad(g, dpred, L2, lddz=3, dz_coff=hidx)
+            if wg[li + 1]:
+                self._wgrad(g, dpred, L2, lddz=3, dz_coff=hidx)
+            m_g = c["gmasks"][hidx]
+            c["gmasks"][hidx] = None
+            if not dg[li + 1]:                 # this head's 64->64 conv and everything below it are frozen
+                del g, m_g
+                li += 2
+                continue
             # the folded head dgrad also emits the bias gradient of the 64->64 head conv (sum of dz_g) while it has it in registers
             if self._ws_bias is None:
                 self._ws_bias = torch.empty(2048 * 64, device=self.device, dtype=torch.float32)
-            m_g = c["gmasks"][hidx]
             mk = {} if m_g is None else {"mask": m_g}          # (bf16 mode: the head activation's sign mask instead of its rows)
             dz_g = self.ops.conv_cout1_dgrad_folded(dpred, L2.w, tuple(g.shape[:4]), g, ACT_RELU, lddz=3, dz_coff=hidx,
-                                               dbias_prev=L1.gb, workspace=self._ws_bias, **mk)
-            c["gmasks"][hidx] = None
+                                               dbias_prev=L1.gb if wg[li] else None, workspace=self._ws_bias, **mk)
             del m_g, mk
             del g
-            self._wgrad(rb.t, dz_g, L1, bias=False)
+            if wg[li]:
+                self._wgrad(rb.t, dz_g, L1, bias=False)
+            if not to_trunk:
+                del dz_g
+                li += 2
+                continue
             if multi:
                 dz_gs.append(dz_g)
                 del dz_g
@@ -608,23 +821,28 @@ class FlowNetModel:
             pads.append(pad)
             del dz_g
             li += 2
-        y_m, a_m = act_of(rb)
-        if multi:
-            pad = self._pad_like(rb.t)
-            use_mask = y_m is not None and rb.mask is not None
-            self.ops.conv3d_dgrad_fused_multi(dz_gs, [Ls[li - 6 + 2 * h].wp_d for h in range(3)], pad, dz, y_prev=None if use_mask else y_m, act=a_m,
-                                              mask=rb.mask if use_mask else None, algo=self.conv_algo[Ls[li - 6].name])
-            pads.append(pad)
-            del dz_gs
-        self.ops.fold_halo_border(pads, dz, None, y_m, a_m)
-        del pads, pad
+        if to_trunk:
+            y_m, a_m = act_of(rb)
+            if multi:
+                pad = self._pad_like(rb.t)
+                use_mask = y_m is not None and rb.mask is not None
+                self.ops.conv3d_dgrad_fused_multi(dz_gs, [Ls[li - 6 + 2 * h].wp_d for h in range(3)], pad, dz, y_prev=None if use_mask else y_m, act=a_m,
+                                                  mask=rb.mask if use_mask else None, algo=self.conv_algo[Ls[li - 6].name])
+                pads.append(pad)
+                del dz_gs
+            self.ops.fold_halo_border(pads, dz, None, y_m, a_m)
+            del pads, pad
         li = len(Ls) - 6
         nb = self.low_resblock + self.hi_resblock
         up = c["up"]
+        need_at = plan["need_at"]
         for i in range(nb, -1, -1):
             if i == self.low_resblock or (done == 1 and i == self.low_resblock // 2 and len(self.grad_buckets) == 3):
                 bucket_done(done)
                 done += 1
+            if not need_at[i]:                 # nothing at or below trunk tensor i trains: the chain ends here
+                dz = None
+                break
             if up is not None and i == self.low_resblock:
                 # dz currently holds d(up_out) (linear producer): pull it through the upsample
                 y_m, a_m = act_of(up[0])
@@ -636,24 +854,42 @@ class FlowNetModel:
             c["blocks"][i - 1] = c["hmasks"][i - 1] = None
             li -= 2
             La, Lb = Ls[li], Ls[li + 1]
-            self._wgrad(h, dz, Lb)
+            if wg[li + 1]:
+                self._wgrad(h, dz, Lb)
+            if not dg[li + 1]:                 # only the block's second conv trains
+                dz = None
+                break
             dz_h = self._dgrad_fold(dz, Lb, None, h, ACT_LEAKY, mask=m_h)
             del m_h
-            self._wgrad(x.t, dz_h, La)
+            if wg[li]:
+                self._wgrad(x.t, dz_h, La)
+            if not dg[li]:
+                dz = None
+                break
             y_m, a_m = act_of(x)
             dz = self._dgrad_fold(dz_h, La, dz, y_m, a_m, mask=x.mask)
             del dz_h
-        assert li == 6
-        # dz == dz_c1
-        self._wgrad(c["c0"], dz, Ls[5])
-        dz_c0 = self._dgrad_fold(dz, Ls[5], None, c["c0"], ACT_RELU)
-        self._wgrad(c["p1"], dz_c0, Ls[4], x2=c["a1"])
-        dz_p1, dz_a1 = self.ops.conv1x1_dgrad(dz_c0, Ls[4].w, c["p1"], c["a1"])
-        for (first, second, src, dzz) in ((Ls[2], Ls[3], "p", dz_p1), (Ls[0], Ls[1], "a", dz_a1)):
-            x0 = c[src + "0"]
-            self._wgrad(x0, dzz, second)
-            dz0 = self._dgrad_fold(dzz, second, None, x0, ACT_RELU)
-            self._wgrad(c["phase"] if src == "p" else c["pc"], dz0, first)
+        if dz is not None:
+            assert li == 6
+            # dz == dz_c1
+            if wg[5]:
+                self._wgrad(c["c0"], dz, Ls[5])
+            if dg[5]:
+                dz_c0 = self._dgrad_fold(dz, Ls[5], None, c["c0"], ACT_RELU)
+                if wg[4]:
+                    self._wgrad(c["p1"], dz_c0, Ls[4], x2=c["a1"])
+                if dg[4]:
+                    dz_p1, dz_a1 = self.ops.conv1x1_dgrad(dz_c0, Ls[4].w, c["p1"], c["a1"])
+                    for (i1, src, dzz, go) in ((2, "p", dz_p1, plan["branch_phase"]), (0, "a", dz_a1, plan["branch_pc"])):
+                        if not go:                  # the whole branch is frozen
+                            continue
+                        first, second = Ls[i1], Ls[i1 + 1]
+                        x0 = c[src + "0"]
+                        if wg[i1 + 1]:
+                            self._wgrad(x0, dzz, second)
+                        if dg[i1 + 1]:
+                            dz0 = self._dgrad_fold(dzz, second, None, x0, ACT_RELU)
+                            self._wgrad(c["phase"] if src == "p" else c["pc"], dz0, first)
         self._flush_wgrads()
         self._join_side()                                            # all weight gradients have landed in flat_g
         while done < len(self.grad_buckets):

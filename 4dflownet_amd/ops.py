@@ -505,15 +505,26 @@ def l2_sumsq(w_flat, is_kernel, out=None):
 ADAM_PARTIALS = 2048                  # FDN_ADAM_PARTIALS
 
 
-def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_dev=None, sumsq_partials=None, lr_t_dev=None):
+def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_dev=None, sumsq_partials=None, lr_t_dev=None, frozen=None):
     """sumsq_partials (ADAM_PARTIALS floats): also receive per-block sums of the updated kernel parameters' squares.
     lr_t_dev (one fp32 device element): the step size is read from it on the device and `lr_t` is ignored (fdn_adam_step_dev) -- the
-    form a captured launch needs, since a by-value lr_t would be frozen into the graph."""
+    form a captured launch needs, since a by-value lr_t would be frozen into the graph.
+    frozen (one uint8 per parameter, fine-tuning): elements with a non-zero byte keep w, m and v, and their g, m and v are not touched
+    (fdn_adam_step_masked); the others are updated exactly as without it.  None: the two entry points above, as always."""
     if sumsq_partials is not None and sumsq_partials.numel() < ADAM_PARTIALS:
         raise FdnError("adam_step: sumsq_partials needs %d floats" % ADAM_PARTIALS)
+    if lr_t_dev is not None and (not lr_t_dev.is_cuda or lr_t_dev.dtype != torch.float32 or lr_t_dev.numel() < 1):
+        raise FdnError("adam_step: lr_t_dev must hold one float32 on the GPU")
+    if frozen is not None:
+        if frozen.numel() != w.numel():
+            raise FdnError("adam_step: frozen holds %d bytes for %d parameters" % (frozen.numel(), w.numel()))
+        check(_lib.load().fdn_adam_step_masked(_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel"), _pu8(frozen, "frozen"), w.numel(),
+                                               0.0 if lr_t_dev is not None else float(lr_t), _p(lr_t_dev, allow_none=True), float(b1), float(b2),
+                                               float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
+                                               _p(sumsq_partials, allow_none=True), _stream()),
+              "fdn_adam_step_masked")
+        return
     if lr_t_dev is not None:
-        if not lr_t_dev.is_cuda or lr_t_dev.dtype != torch.float32 or lr_t_dev.numel() < 1:
-            raise FdnError("adam_step: lr_t_dev must hold one float32 on the GPU")
         check(_lib.load().fdn_adam_step_dev(_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel"), w.numel(), _p(lr_t_dev), float(b1), float(b2),
                                             float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
                                             _p(sumsq_partials, allow_none=True), _stream()),

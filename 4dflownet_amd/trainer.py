@@ -8,7 +8,9 @@ Differences that are deliberate and documented in DESIGN.md:
   * metrics accumulate on the device and are only synchronised when .result() is read, so a training loop that
     does not print every step never stalls the GPU (the reference forces a sync per step, :290);
   * with torch.distributed initialised, train_step sum-all-reduces the flat gradient over RCCL before Adam;
-  * accum_steps = K > 1 (no counterpart in the reference): K train_step calls form ONE optimiser step on the sum of their gradients."""
+  * accum_steps = K > 1 (no counterpart in the reference): K train_step calls form ONE optimiser step on the sum of their gradients;
+  * fine-tuning: `trainable=` / model.set_trainable / `layer.trainable = False` freeze layers as in Keras (:223-225 differentiate and
+    update model.trainable_variables only); backward skips what a frozen layer does not need and Adam leaves its parameters and slots."""
 import datetime
 import os
 import pickle
@@ -75,7 +77,7 @@ class _Optimizer:
 class TrainerController:
     def __init__(self, patch_size, res_increase, initial_learning_rate=1e-4, quicksave_enable=True,
                  network_name='4DFlowNet', low_resblock=8, hi_resblock=4, device=None, seed=0, dtype='float32',
-                 bucketed_allreduce=None, conv_algo=None, div_weight=0, accum_steps=1):
+                 bucketed_allreduce=None, conv_algo=None, div_weight=0, accum_steps=1, trainable=None):
         """Reference arguments: TrainerController.py:18.  Extra (keyword-only in spirit): device, seed (Glorot draw), dtype
         (activation storage, 'float32' | 'bfloat16'), bucketed_allreduce (data parallel only: True = one asynchronous SUM
         all-reduce per gradient bucket started inside backward -- the default --, False = ONE all-reduce of the whole buffer
@@ -87,7 +89,10 @@ class TrainerController:
         reference's step on the concatenated batch: tape.gradient of the (B,) loss vector is the gradient of sum_b loss_b and no layer
         couples samples, TrainerController.py:223,245-249.  1 = every call is an optimiser step, nothing is allocated or launched for
         accumulation.  The attribute of the same name is read when a group starts: a change made mid-group applies from the next
-        group.  See train_step and apply_accumulated)."""
+        group.  See train_step and apply_accumulated), trainable (fine-tuning: None or "all" = every layer, "hires" = the hi-res ResBlocks
+        and the heads, "heads" = the six head layers, or an iterable of layer names -- FlowNetModel.set_trainable; the same as setting
+        `layer.trainable` on self.model.layers as one does in Keras.  Frozen layers get no gradient, no update and no optimiser slots in
+        optimizer.pkl; optimizer.iterations and the bias correction stay global; l2_reg_loss still covers every kernel)."""
         self.div_weight = div_weight   # TrainerController.py:23
         self._checked_div_weight()
         self.accum_steps = accum_steps
@@ -109,6 +114,8 @@ class TrainerController:
         self.model = net.build_network(u, v, w, u_mag, v_mag, w_mag, low_resblock, hi_resblock, device=device, seed=seed,
                                        dtype=dtype, conv_algo=conv_algo)
         self.device = self.model.device
+        if trainable is not None:
+            self.model.set_trainable(trainable)
 
         names = ['train_loss', 'val_loss', 'train_accuracy', 'val_accuracy', 'train_mse', 'val_mse', 'train_div',
                  'val_div', 'l2_reg_loss']
@@ -185,6 +192,8 @@ class TrainerController:
         stop there: no collective, no Adam launch, optimizer.iterations / flat_w / m / v / weights_version / the packs untouched.  Call K
         accumulates, all-reduces the ACCUMULATOR over the ranks if data parallel, and runs Adam on it (its trailing slot = the group's
         global batch size), one iteration.  apply_accumulated() closes a group early."""
+        if not self.model.any_trainable:                            # Keras: "No gradients provided for any variable"
+            raise ValueError("train_step: no layer of the model is trainable (layer.trainable / set_trainable), there is nothing to update")
         if self._accum_count == 0:                                  # a group starts: this is where accum_steps is read
             self._accum_k = self._checked_accum_steps()
         if self._accum_k > 1:
@@ -220,11 +229,24 @@ class TrainerController:
         opt = self.optimizer
         opt.iterations += 1
         # L2 regulariser gradient: the (B,) loss vector carries the scalar L2 term B times (:249) -> B_global * 2*lambda*w
-        ops.adam_step(m.flat_w, m.flat_g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
-                      2.0 * L2_LAMBDA, m.batch_slot, sumsq_partials=self._l2_partials)
-        m.weights_changed()
+        self._adam(m.flat_g, m.batch_slot)
         self._l2_version = m.weights_version
         return loss
+
+    def _adam(self, g, batch_slot):
+        """One Adam launch on the flat buffers and the re-pack of what moved.  With frozen layers: the masked path of the same kernel
+        (their parameters and slots keep their bits, the L2 gradient reaches trainable kernels only, the sum of squares it leaves still
+        covers all kernels) and a re-pack of the trainable 64->64 layers only."""
+        m, opt = self.model, self.optimizer
+        frozen = m.frozen_map
+        if frozen is None:
+            ops.adam_step(m.flat_w, g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
+                          2.0 * L2_LAMBDA, batch_slot, sumsq_partials=self._l2_partials)
+            m.weights_changed()
+        else:
+            ops.adam_step(m.flat_w, g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
+                          2.0 * L2_LAMBDA, batch_slot, sumsq_partials=self._l2_partials, frozen=frozen)
+            m.weights_changed(trainable_only=True)
 
     def _wait_allreduce(self, pending, dp):
         """The current stream waits for the collectives in `pending` (no host synchronisation under nccl)."""
@@ -302,9 +324,7 @@ class TrainerController:
         opt = self.optimizer
         opt.iterations += 1
         n = m.n_params
-        ops.adam_step(m.flat_w, acc[:n], opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
-                      2.0 * L2_LAMBDA, acc[n:n + 1], sumsq_partials=self._l2_partials)
-        m.weights_changed()
+        self._adam(acc[:n], acc[n:n + 1])
         self._l2_version = m.weights_version
         self._accum_count = 0
         self._accum_has = False
@@ -514,11 +534,11 @@ class TrainerController:
         Gradient accumulation: a partial group is never checkpointed -- the accumulator is not part of the files.  train_network applies
         the pending group before it gets here; a caller of its own does the same with apply_accumulated()."""
         self.model.save('%s-best.h5' % self.model_path)
-        tv = self.model.trainable_variables
-        sizes = [t.numel() for t in tv]
-        shapes = [tuple(t.shape) for t in tv]
-        m = [a.reshape(s) for a, s in zip(np.split(self.optimizer.m.cpu().numpy(), np.cumsum(sizes)[:-1]), shapes)]
-        v = [a.reshape(s) for a, s in zip(np.split(self.optimizer.v.cpu().numpy(), np.cumsum(sizes)[:-1]), shapes)]
+        # slots of the TRAINABLE variables only: Keras creates slots for the variables it is given (frozen layers have none)
+        where = self._trainable_slices()
+        m_flat, v_flat = self.optimizer.m.cpu().numpy(), self.optimizer.v.cpu().numpy()
+        m = [m_flat[o:o + k].reshape(s) for o, k, s in where]
+        v = [v_flat[o:o + k].reshape(s) for o, k, s in where]
         order = self.model.keras_variable_order()
         weight_values = [np.int64(self.optimizer.iterations)] + [m[i] for i in order] + [v[i] for i in order]
         with open('%s/optimizer.pkl' % self.model_dir, 'wb') as f:
@@ -531,6 +551,16 @@ class TrainerController:
             f.write("# optimizer.pkl slot order: [iterations] + m slots + v slots, each in this variable order (Keras trainable_variables)\n")
             f.write("\n".join(names[i] for i in order) + "\n")
 
+    def _trainable_slices(self):
+        """(offset, numel, shape) in the flat buffers of every entry of model.trainable_variables (creation order)."""
+        out = []
+        for L in self.model.layers:
+            if L.trainable:
+                out.append((L.w_off, L.w.numel(), tuple(L.w.shape)))
+                if L.b is not None:
+                    out.append((L.b_off, L.b.numel(), tuple(L.b.shape)))
+        return out
+
     def restore_model(self, old_model_dir, old_model_file):
         """TrainerController.py:365-394.  optimizer.pkl slots are in Keras trainable_variables order (see save_best_model).
         A checkpoint never holds a partial accumulation group: a group that is open here is dropped, the next train_step starts one."""
@@ -538,16 +568,20 @@ class TrainerController:
             opt_weights = pickle.load(f)
         tv = self.model.trainable_variables
         n = len(tv)
-        if len(opt_weights) != 1 + 2 * n:
-            raise ValueError("optimizer.pkl holds %d arrays, expected %d" % (len(opt_weights), 1 + 2 * n))
         order = self.model.keras_variable_order()
         names = self.model.trainable_variable_names()
         side = "%s/optimizer_order.txt" % old_model_dir
         legacy = os.environ.get("FDN_OPTIMIZER_PKL_ORDER", "")
+        listed = None
         if os.path.exists(side):                              # written by save_best_model: map the slots by variable name
             listed = [l.strip() for l in open(side) if l.strip() and not l.startswith("#")]
-            if sorted(listed) != sorted(names):
-                raise ValueError("optimizer_order.txt names %d variables that are not this model's" % len(set(listed) ^ set(names)))
+            if sorted(listed) != sorted(names):               # (the slots are those of the variables that were trainable when it was saved)
+                diff = sorted(set(listed) ^ set(names))
+                raise ValueError("optimizer_order.txt names %d variables that are not this model's trainable variables (set the same "
+                                 "layers trainable as when it was saved): %s" % (len(diff), ", ".join(diff)))
+        if len(opt_weights) != 1 + 2 * n:
+            raise ValueError("optimizer.pkl holds %d arrays, expected %d" % (len(opt_weights), 1 + 2 * n))
+        if listed is not None:
             order = [names.index(nm) for nm in listed]
         elif legacy == "creation":                            # a pickle of this repository before round 3 (no sidecar, creation order)
             order = list(range(n))
@@ -566,9 +600,12 @@ class TrainerController:
                                      "see save_best_model)" % (name, slot, tuple(np.shape(src[slot])), tuple(tv[i].shape)))
                 dst[i] = src[slot]
         self.optimizer.iterations = int(opt_weights[0])
-        flat = lambda arrs: torch.from_numpy(np.concatenate([np.asarray(a, np.float32).reshape(-1) for a in arrs]))
-        self.optimizer.m.copy_(flat(m))
-        self.optimizer.v.copy_(flat(v))
+        # (into the trainable variables' ranges of the flat slots; a frozen layer has no slots in the file and keeps what it holds)
+        for dst, arrs in ((self.optimizer.m, m), (self.optimizer.v, v)):
+            host = dst.cpu().numpy()
+            for (o, k, _), a in zip(self._trainable_slices(), arrs):
+                host[o:o + k] = np.asarray(a, np.float32).reshape(-1)
+            dst.copy_(torch.from_numpy(host))
         self.model.load_weights("%s/%s" % (old_model_dir, old_model_file))
         self._accum_count = 0
         self._accum_has = False

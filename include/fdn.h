@@ -345,6 +345,19 @@ int fdn_adam_step(float* w, const float* g, float* m, float* v, const uint8_t* i
 int fdn_adam_step_dev(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, int64_t n,
                       const float* lr_t_dev, float b1, float b2, float eps, float l2_grad_scale,
                       const float* l2_scale_dev, float* sumsq_partials, void* stream);
+/* fdn_adam_step for fine-tuning (`layer.trainable = False`, TrainerController.py:223-225 update model.trainable_variables only):
+ * frozen holds one byte per parameter like is_kernel.  A path of the same kernel, taken when frozen != NULL, on the grid of
+ * fdn_adam_step (FDN_ADAM_PARTIALS blocks when partials are requested).  lr_t_dev != NULL: the step size is lr_t_dev[0], read on the
+ * device as in fdn_adam_step_dev (a captured launch); otherwise the by-value lr_t.
+ *   frozen[i] == 0: the arithmetic of fdn_adam_step -- w, m and v come out bit-identical to fdn_adam_step[_dev] on the same operands.
+ *   frozen[i] != 0: w[i], m[i] and v[i] keep their bits; g[i], m[i] and v[i] are neither read nor written (a NaN or an uninitialised
+ *                   gradient there is harmless).  The element still adds w[i]^2 to its block's partial when is_kernel[i].
+ * The regulariser value covers every kernel, frozen or not (TrainerController.py:129-141 loops over all layers): sumsq_partials equals
+ * fdn_l2_sumsq_partials of the resulting w bit for bit, as after fdn_adam_step.  The L2 gradient reaches unfrozen kernels only.
+ * Refused before the device is touched, the message naming the argument: NULL w, g, m, v, is_kernel or frozen, n <= 0. */
+int fdn_adam_step_masked(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, const uint8_t* frozen, int64_t n,
+                         float lr_t, const float* lr_t_dev, float b1, float b2, float eps, float l2_grad_scale,
+                         const float* l2_scale_dev, float* sumsq_partials, void* stream);
 int fdn_sum_partials(const float* partials, int n, float* out, void* stream);
 /* acc[i] = first ? g[i] : acc[i] + g[i], i in [0, n).  One fp32 add per element (IEEE, round-to-nearest-even):
  * first = 1 is a bit copy (no memset of acc is needed), first = 0 equals numpy's float32 acc + g bit for bit.

@@ -46,6 +46,10 @@ if __name__ == "__main__":
     res_increase = 2
     low_resblock = 8
     hi_resblock = 4
+    # fine-tuning: None = every layer trains; "hires" (hi-res ResBlocks + heads), "heads", or a list of layer names freeze the rest
+    # (TrainerController(trainable=...), the same as `layer.trainable = False` in Keras).  Together with `restore` the run starts from the
+    # restored WEIGHTS with a fresh optimiser: the saved slots belong to the variables that were trainable then.
+    trainable = None
 
     parallel.init_from_env()
     trainset = data.load_indexes(training_file)
@@ -62,9 +66,12 @@ if __name__ == "__main__":
 
     print("4DFlowNet Patch %d, lr %s, batch %d" % (patch_size, initial_learning_rate, batch_size))
     network = trainer.TrainerController(patch_size, res_increase, initial_learning_rate, QUICKSAVE, network_name,
-                                        low_resblock, hi_resblock, accum_steps=accum_steps)
+                                        low_resblock, hi_resblock, accum_steps=accum_steps, trainable=trainable)
     network.init_model_dir()
-    if restore:
+    if restore and trainable is not None:
+        print("Fine-tuning from the weights of %s..." % model_file)
+        network.model.load_weights("%s/%s" % (model_dir, model_file))
+    elif restore:
         print("Restoring model %s..." % model_file)
         network.restore_model(model_dir, model_file)
         print("Learning rate", network.optimizer.lr)
