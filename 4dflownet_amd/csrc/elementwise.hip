@@ -692,22 +692,52 @@ __global__ __launch_bounds__(1024) void l2_sumsq_kernel(const float* __restrict_
     if (threadIdx.x == 0) out[0] = a;
 }
 
+// The per-block sum every pass on the FDN_ADAM_PARTIALS blocking ends with: shuffle tree per wave, then the four waves in a fixed order.
+__device__ __forceinline__ void block_partial(float ss, float* __restrict__ out) {
+    __shared__ float red[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_down(ss, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // sumsq != null: block b also writes sum(w_new^2) over its kernel (non-bias) elements to sumsq[b] (fixed order: the
 // regulariser value of the NEXT step's loss, so fdn_l2_sumsq does not have to stream the parameters again).
 // lr_t_dev != null: the step size is lr_t_dev[0], read on the device (fdn_adam_step_dev: a captured launch must not bake it in).
 // accum != 0 (fdn_grad_accumulate): the sum of micro-batch gradient buffers as a path of this kernel selected by one by-value int --
 // w[i] = g[i] (ACCUM_FIRST) or w[i] + g[i] (ACCUM_ADD); m .. sumsq are not read.  Scalar accesses: w and g are bucket slices at any
 // float offset, and the 13.4 MB of cfg2 are not where the step's time is.
+// accum == GRAD_SUMSQ (fdn_grad_sumsq_partials: gradient clipping, tf.clip_by_global_norm): nothing is written but sumsq[b] = block b's
+// sum of g'^2, g' = g + l2s * w (kernels only) formed as the Adam path below forms it, over the elements with frozen[i] == 0 -- the
+// square of the norm Keras clips, TrainerController.py:73,223-225.  Here rather than in l2_sumsq_partials_kernel: this kernel's
+// parameter list already carries g, w, isk, frozen and the two halves of l2s, and the blocking is the same.
 // frozen != null (fdn_adam_step_masked: fine-tuning, one byte per parameter like isk): an element with frozen[i] != 0 keeps w, m and v --
 // g[i], m[i] and v[i] are neither loaded nor stored -- and still adds w[i]^2 to its block's sum when it is a kernel: the regulariser
 // value covers every kernel (TrainerController.py:129-141).  An element with frozen[i] == 0 takes the statements below unchanged.
+// g_scale_dev != null / clip_value > 0 (fdn_adam_step_clipped): g' *= g_scale_dev[0] (one fp32 multiply behind the L2 term: the scale
+// fdn_clip_scale left on the device) / g' clamped to [-clip_value, clip_value] by comparisons, so that a NaN stays a NaN.
 #define ACCUM_FIRST 1
 #define ACCUM_ADD 2
+#define GRAD_SUMSQ 3
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, const uint8_t* __restrict__ isk, int64_t n, float lr_t_host,
                                                    const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float l2s_host,
                                                    const float* __restrict__ l2s_dev, float* __restrict__ sumsq, int accum,
-                                                   const uint8_t* __restrict__ frozen) {
+                                                   const uint8_t* __restrict__ frozen, const float* __restrict__ g_scale_dev,
+                                                   float clip_value) {
+    if (accum == GRAD_SUMSQ) {                                       // fdn_grad_sumsq_partials: w is only read
+        const float l2s = l2s_dev ? l2s_host * l2s_dev[0] : l2s_host;
+        float ss = 0.f;
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+            if (frozen && frozen[i]) continue;                       // g[i] is not loaded; the element adds +0
+            float gi = g[i];
+            if (isk[i]) gi += l2s * w[i];
+            ss += gi * gi;
+        }
+        block_partial(ss, sumsq);
+        return;
+    }
     if (accum) {                                                     // fdn_grad_accumulate: w is the accumulator, g one micro-batch's gradients;
         const bool first = accum == ACCUM_FIRST;                     // nothing else is read.  Uniform, ahead of the Adam path's first load
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -719,6 +749,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const 
     }
     const float lr_t = lr_t_dev ? lr_t_dev[0] : lr_t_host;
     const float l2s = l2s_dev ? l2s_host * l2s_dev[0] : l2s_host;
+    const float g_scale = g_scale_dev ? g_scale_dev[0] : 1.f;
     float ss = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float wi = w[i];
@@ -727,6 +758,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const 
         if (!(frozen && frozen[i])) {
             float gi = g[i];
             if (k) gi += l2s * wi;
+            if (g_scale_dev) gi *= g_scale;
+            if (clip_value > 0.f) gi = gi > clip_value ? clip_value : (gi < -clip_value ? -clip_value : gi);
             const float mi = b1 * m[i] + (1.f - b1) * gi;
             const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
             m[i] = mi;
@@ -736,14 +769,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const 
         }
         if (k) ss += wn * wn;
     }
-    if (sumsq) {
-        __shared__ float red[4];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_down(ss, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-        __syncthreads();
-        if (threadIdx.x == 0) sumsq[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-    }
+    if (sumsq) block_partial(ss, sumsq);
 }
 
 // The same per-block sums the Adam kernel leaves behind (identical blocking: block b covers the elements b * 256 + t + k * grid * 256),
@@ -754,16 +780,16 @@ __global__ __launch_bounds__(256) void l2_sumsq_partials_kernel(const float* __r
     float ss = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         if (isk[i]) ss += w[i] * w[i];
-    __shared__ float red[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_down(ss, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-    __syncthreads();
-    if (threadIdx.x == 0) sumsq[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    block_partial(ss, sumsq);
 }
 
-// out[0] = sum of n partials, one block, fixed order (deterministic)
-__global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
+// out[0] = sum of n partials, one block, fixed order (deterministic).
+// clip_norm > 0 (fdn_clip_scale): the partials are those of fdn_grad_sumsq_partials and their sum S becomes out[0] = N = sqrtf(S), the
+// global norm, and out[1] = s = clip_norm / max(N, clip_norm), the factor of tf.clip_by_global_norm: exactly 1.0f whenever
+// N <= clip_norm (x / x), so an inactive clip changes no bit downstream.  TF writes clip_norm * min(1 / N, 1 / clip_norm): two roundings
+// instead of one, equal up to rounding.  N not finite (an inf or NaN gradient, or squares that overflow): s = NaN, which makes every
+// parameter the step updates NaN, as in TF.
+__global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restrict__ part, int n, float* __restrict__ out, float clip_norm) {
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += part[i];
@@ -771,7 +797,16 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restri
     for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) {
+        const float total = (red[0] + red[1]) + (red[2] + red[3]);
+        if (clip_norm > 0.f) {
+            const float norm = sqrtf(total);
+            out[0] = norm;
+            out[1] = __builtin_isfinite(norm) ? clip_norm / (norm > clip_norm ? norm : clip_norm) : __builtin_nanf("");
+        } else {
+            out[0] = total;
+        }
+    }
 }
 
 int grid_for(int64_t items, int cap = 4096) {
@@ -1018,7 +1053,7 @@ extern "C" int fdn_adam_step(float* w, const float* g, float* m, float* v, const
     // fixed grid of FDN_ADAM_PARTIALS blocks when partials are requested (blocks beyond the data write 0)
     const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);
     hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       lr_t, (const float*)nullptr, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, (const uint8_t*)nullptr);
+                       lr_t, (const float*)nullptr, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, (const uint8_t*)nullptr, (const float*)nullptr, 0.f);
     FDN_CHECK_LAUNCH("adam_kernel");
     return FDN_OK;
 }
@@ -1031,7 +1066,7 @@ extern "C" int fdn_adam_step_dev(float* w, const float* g, float* m, float* v, c
     FDN_REQUIRE(n > 0, "fdn_adam_step_dev: n=%lld must be positive", (long long)n);
     const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);
     hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       0.f, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, (const uint8_t*)nullptr);
+                       0.f, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, (const uint8_t*)nullptr, (const float*)nullptr, 0.f);
     FDN_CHECK_LAUNCH("adam_kernel");
     return FDN_OK;
 }
@@ -1048,7 +1083,7 @@ extern "C" int fdn_adam_step_masked(float* w, const float* g, float* m, float* v
     FDN_REQUIRE(n > 0, "fdn_adam_step_masked: n=%lld must be positive", (long long)n);
     const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);       // the grid rule of fdn_adam_step
     hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       lr_t, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, frozen);
+                       lr_t, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, frozen, (const float*)nullptr, 0.f);
     FDN_CHECK_LAUNCH("adam_kernel (masked)");
     return FDN_OK;
 }
@@ -1065,14 +1100,59 @@ extern "C" int fdn_grad_accumulate(float* acc, const float* g, int64_t n, int fi
                 (long long)(a > b ? a - b : b - a), (long long)n);
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, acc, g, (float*)nullptr, (float*)nullptr,
                        (const uint8_t*)nullptr, n, 0.f, (const float*)nullptr, 0.f, 0.f, 0.f, 0.f, (const float*)nullptr, (float*)nullptr,
-                       first ? ACCUM_FIRST : ACCUM_ADD, (const uint8_t*)nullptr);
+                       first ? ACCUM_FIRST : ACCUM_ADD, (const uint8_t*)nullptr, (const float*)nullptr, 0.f);
     FDN_CHECK_LAUNCH("adam_kernel (grad accumulate)");
     return FDN_OK;
 }
 
 extern "C" int fdn_sum_partials(const float* partials, int n, float* out, void* stream) {
     FDN_REQUIRE(partials && out && n > 0, "fdn_sum_partials: bad argument");
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, out);
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, out, 0.f);
     FDN_CHECK_LAUNCH("sum_partials_kernel");
+    return FDN_OK;
+}
+
+// Gradient clipping (tf.keras.optimizers.Adam(global_clipnorm= / clipvalue=), TrainerController.py:73): three launches of kernels that
+// exist already -- the sum of squares of the step's gradient and the clipped step as paths of adam_kernel, norm and scale as a path of
+// sum_partials_kernel.  The scale stays on the device between the second and the third.
+extern "C" int fdn_grad_sumsq_partials(const float* g, const float* w, const uint8_t* is_kernel, const uint8_t* frozen, int64_t n,
+                                       float l2_grad_scale, const float* l2_scale_dev, float* partials, void* stream) {
+    FDN_REQUIRE(g, "fdn_grad_sumsq_partials: g is NULL");
+    FDN_REQUIRE(w, "fdn_grad_sumsq_partials: w is NULL");
+    FDN_REQUIRE(is_kernel, "fdn_grad_sumsq_partials: is_kernel is NULL");
+    FDN_REQUIRE(partials, "fdn_grad_sumsq_partials: partials is NULL");
+    FDN_REQUIRE(n > 0, "fdn_grad_sumsq_partials: n=%lld must be positive", (long long)n);
+    hipLaunchKernelGGL(adam_kernel, dim3(FDN_ADAM_PARTIALS), dim3(256), 0, (hipStream_t)stream, const_cast<float*>(w), g, (float*)nullptr,
+                       (float*)nullptr, is_kernel, n, 0.f, (const float*)nullptr, 0.f, 0.f, 0.f, l2_grad_scale, l2_scale_dev, partials,
+                       GRAD_SUMSQ, frozen, (const float*)nullptr, 0.f);
+    FDN_CHECK_LAUNCH("adam_kernel (gradient sum of squares)");
+    return FDN_OK;
+}
+
+extern "C" int fdn_clip_scale(const float* partials, int n_partials, float clip_norm, float* out, void* stream) {
+    FDN_REQUIRE(partials, "fdn_clip_scale: partials is NULL");
+    FDN_REQUIRE(out, "fdn_clip_scale: out is NULL");
+    FDN_REQUIRE(n_partials > 0, "fdn_clip_scale: n_partials=%d must be positive", n_partials);
+    FDN_REQUIRE(__builtin_isfinite(clip_norm) && clip_norm > 0.f, "fdn_clip_scale: clip_norm=%g must be finite and > 0", (double)clip_norm);
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, out, clip_norm);
+    FDN_CHECK_LAUNCH("sum_partials_kernel (clip scale)");
+    return FDN_OK;
+}
+
+extern "C" int fdn_adam_step_clipped(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, const uint8_t* frozen, int64_t n,
+                                     float lr_t, const float* lr_t_dev, float b1, float b2, float eps, float l2_grad_scale,
+                                     const float* l2_scale_dev, const float* g_scale_dev, float clip_value, float* sumsq_partials,
+                                     void* stream) {
+    FDN_REQUIRE(w, "fdn_adam_step_clipped: w is NULL");
+    FDN_REQUIRE(g, "fdn_adam_step_clipped: g is NULL");
+    FDN_REQUIRE(m, "fdn_adam_step_clipped: m is NULL");
+    FDN_REQUIRE(v, "fdn_adam_step_clipped: v is NULL");
+    FDN_REQUIRE(is_kernel, "fdn_adam_step_clipped: is_kernel is NULL");
+    FDN_REQUIRE(n > 0, "fdn_adam_step_clipped: n=%lld must be positive", (long long)n);
+    FDN_REQUIRE(clip_value >= 0.f, "fdn_adam_step_clipped: clip_value=%g must be >= 0 (0 = off)", (double)clip_value);      // (false for NaN)
+    const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);       // the grid rule of fdn_adam_step
+    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
+                       lr_t, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, frozen, g_scale_dev, clip_value);
+    FDN_CHECK_LAUNCH("adam_kernel (clipped)");
     return FDN_OK;
 }

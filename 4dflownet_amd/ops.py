@@ -505,19 +505,39 @@ def l2_sumsq(w_flat, is_kernel, out=None):
 ADAM_PARTIALS = 2048                  # FDN_ADAM_PARTIALS
 
 
-def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_dev=None, sumsq_partials=None, lr_t_dev=None, frozen=None):
+def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_dev=None, sumsq_partials=None, lr_t_dev=None, frozen=None,
+              g_scale_dev=None, clip_value=0.0):
     """sumsq_partials (ADAM_PARTIALS floats): also receive per-block sums of the updated kernel parameters' squares.
     lr_t_dev (one fp32 device element): the step size is read from it on the device and `lr_t` is ignored (fdn_adam_step_dev) -- the
     form a captured launch needs, since a by-value lr_t would be frozen into the graph.
     frozen (one uint8 per parameter, fine-tuning): elements with a non-zero byte keep w, m and v, and their g, m and v are not touched
-    (fdn_adam_step_masked); the others are updated exactly as without it.  None: the two entry points above, as always."""
+    (fdn_adam_step_masked); the others are updated exactly as without it.  None: the two entry points above, as always.
+    Gradient clipping (fdn_adam_step_clipped; at most one of the two): g_scale_dev (one fp32 device element, the second float clip_scale
+    leaves behind) multiplies the gradient, L2 term included, on the device; clip_value > 0 clamps every element of it to
+    [-clip_value, clip_value].  Neither: the entry points above, as always."""
+    clip_value = float(clip_value)
+    if g_scale_dev is not None or clip_value != 0.0:
+        if g_scale_dev is not None and clip_value != 0.0:
+            raise FdnError("adam_step: g_scale_dev and clip_value are both set (global_clipnorm and clipvalue exclude each other)")
+        if g_scale_dev is not None and (not g_scale_dev.is_cuda or g_scale_dev.dtype != torch.float32 or g_scale_dev.numel() != 1):
+            raise FdnError("adam_step: g_scale_dev must hold one float32 on the GPU")
+        if not clip_value >= 0.0:
+            raise FdnError("adam_step: clip_value must be >= 0 (0 = off), got %r" % clip_value)
     if sumsq_partials is not None and sumsq_partials.numel() < ADAM_PARTIALS:
         raise FdnError("adam_step: sumsq_partials needs %d floats" % ADAM_PARTIALS)
     if lr_t_dev is not None and (not lr_t_dev.is_cuda or lr_t_dev.dtype != torch.float32 or lr_t_dev.numel() < 1):
         raise FdnError("adam_step: lr_t_dev must hold one float32 on the GPU")
+    if frozen is not None and frozen.numel() != w.numel():
+        raise FdnError("adam_step: frozen holds %d bytes for %d parameters" % (frozen.numel(), w.numel()))
+    if g_scale_dev is not None or clip_value != 0.0:
+        check(_lib.load().fdn_adam_step_clipped(_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel"), _pu8(frozen, "frozen", allow_none=True),
+                                                w.numel(), 0.0 if lr_t_dev is not None else float(lr_t), _p(lr_t_dev, allow_none=True), float(b1),
+                                                float(b2), float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
+                                                _p(g_scale_dev, "g_scale_dev", allow_none=True), clip_value, _p(sumsq_partials, allow_none=True),
+                                                _stream()),
+              "fdn_adam_step_clipped")
+        return
     if frozen is not None:
-        if frozen.numel() != w.numel():
-            raise FdnError("adam_step: frozen holds %d bytes for %d parameters" % (frozen.numel(), w.numel()))
         check(_lib.load().fdn_adam_step_masked(_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel"), _pu8(frozen, "frozen"), w.numel(),
                                                0.0 if lr_t_dev is not None else float(lr_t), _p(lr_t_dev, allow_none=True), float(b1), float(b2),
                                                float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
@@ -555,6 +575,41 @@ def l2_sumsq_partials(w_flat, is_kernel, partials):
         raise FdnError("l2_sumsq_partials: partials needs %d floats" % ADAM_PARTIALS)
     check(_lib.load().fdn_l2_sumsq_partials(_p(w_flat), _pu8(is_kernel, "is_kernel"), w_flat.numel(), _p(partials), _stream()), "fdn_l2_sumsq_partials")
     return partials
+
+
+def grad_sumsq_partials(g, w, is_kernel, l2_grad_scale, l2_scale_dev=None, partials=None, frozen=None):
+    """ADAM_PARTIALS per-block sums of the squares of the gradient the next adam_step is about to consume: g + l2s * w on kernel
+    elements (l2s = l2_grad_scale * l2_scale_dev[0], as in adam_step), g on biases, elements with a non-zero byte in `frozen` left out
+    (their g is not read).  fdn_grad_sumsq_partials; follow with clip_scale."""
+    if partials is None:
+        partials = torch.empty((ADAM_PARTIALS,), device=g.device, dtype=torch.float32)
+    elif partials.numel() < ADAM_PARTIALS:
+        raise FdnError("grad_sumsq_partials: partials needs %d floats" % ADAM_PARTIALS)
+    n = g.numel()
+    for name, t in (("w", w), ("is_kernel", is_kernel), ("frozen", frozen)):
+        if t is not None and t.numel() != n:
+            raise FdnError("grad_sumsq_partials: %s holds %d elements for %d gradients" % (name, t.numel(), n))
+    if l2_scale_dev is not None and (not l2_scale_dev.is_cuda or l2_scale_dev.dtype != torch.float32 or l2_scale_dev.numel() < 1):
+        raise FdnError("grad_sumsq_partials: l2_scale_dev must hold one float32 on the GPU")
+    check(_lib.load().fdn_grad_sumsq_partials(_p(g, "g"), _p(w, "w"), _pu8(is_kernel, "is_kernel"), _pu8(frozen, "frozen", allow_none=True), n,
+                                              float(l2_grad_scale), _p(l2_scale_dev, "l2_scale_dev", allow_none=True), _p(partials, "partials"),
+                                              _stream()), "fdn_grad_sumsq_partials")
+    return partials
+
+
+def clip_scale(partials, clip_norm, out=None):
+    """out[0] = the global norm sqrt(sum of partials), out[1] = clip_norm / max(norm, clip_norm) (1.0 exactly when the clip is inactive, NaN
+    when the norm is not finite), both left on the device (fdn_clip_scale).  out[1:2] is adam_step's g_scale_dev."""
+    c32 = ctypes.c_float(float(clip_norm)).value              # the fp32 value the library receives
+    if not (c32 > 0.0 and c32 != float("inf")):
+        raise FdnError("clip_scale: clip_norm must be finite and > 0 in float32, got %r" % (clip_norm,))
+    clip_norm = c32
+    if out is None:
+        out = torch.empty((2,), device=partials.device, dtype=torch.float32)
+    elif out.numel() < 2:
+        raise FdnError("clip_scale: out needs 2 floats")
+    check(_lib.load().fdn_clip_scale(_p(partials, "partials"), partials.numel(), clip_norm, _p(out, "out"), _stream()), "fdn_clip_scale")
+    return out
 
 
 def sum_partials(partials, out=None):

@@ -10,7 +10,10 @@ Differences that are deliberate and documented in DESIGN.md:
   * with torch.distributed initialised, train_step sum-all-reduces the flat gradient over RCCL before Adam;
   * accum_steps = K > 1 (no counterpart in the reference): K train_step calls form ONE optimiser step on the sum of their gradients;
   * fine-tuning: `trainable=` / model.set_trainable / `layer.trainable = False` freeze layers as in Keras (:223-225 differentiate and
-    update model.trainable_variables only); backward skips what a frozen layer does not need and Adam leaves its parameters and slots."""
+    update model.trainable_variables only); backward skips what a frozen layer does not need and Adam leaves its parameters and slots;
+  * gradient clipping: `global_clipnorm=` / `clipvalue=` are the arguments of the same name of tf.keras.optimizers.Adam (:73), applied on
+    the device to the gradient Adam is about to consume, the L2 term included."""
+import ctypes
 import datetime
 import os
 import pickle
@@ -25,6 +28,27 @@ from .network import Input, SR4DFlowNet
 
 L2_LAMBDA = 5e-7                      # SR4DFlowNet.py:99
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-7   # tf.keras.optimizers.Adam defaults (TrainerController.py:73)
+
+
+def _clip_arguments(global_clipnorm, clipvalue):
+    """The two clipping arguments of tf.keras.optimizers.Adam as (float or None, float or None): each None or a number that is finite
+    and > 0 as the float32 the device receives, and at most one of them set.  (Keras' per-variable `clipnorm` needs one norm per
+    variable and is not offered.)"""
+    out = []
+    for name, c in (("global_clipnorm", global_clipnorm), ("clipvalue", clipvalue)):
+        if c is None:
+            out.append(None)
+            continue
+        try:
+            cf = ctypes.c_float(float(c)).value
+        except (TypeError, ValueError):
+            raise ValueError("%s must be None or a finite number > 0, got %r" % (name, c)) from None
+        if isinstance(c, (bool, str, bytes)) or not np.isfinite(cf) or cf <= 0:
+            raise ValueError("%s must be None or a finite number > 0, got %r" % (name, c))
+        out.append(cf)
+    if out[0] is not None and out[1] is not None:
+        raise ValueError("global_clipnorm and clipvalue are both set (%r, %r): at most one kind of gradient clipping" % (global_clipnorm, clipvalue))
+    return tuple(out)
 
 
 class Mean:
@@ -77,7 +101,8 @@ class _Optimizer:
 class TrainerController:
     def __init__(self, patch_size, res_increase, initial_learning_rate=1e-4, quicksave_enable=True,
                  network_name='4DFlowNet', low_resblock=8, hi_resblock=4, device=None, seed=0, dtype='float32',
-                 bucketed_allreduce=None, conv_algo=None, div_weight=0, accum_steps=1, trainable=None):
+                 bucketed_allreduce=None, conv_algo=None, div_weight=0, accum_steps=1, trainable=None, global_clipnorm=None,
+                 clipvalue=None):
         """Reference arguments: TrainerController.py:18.  Extra (keyword-only in spirit): device, seed (Glorot draw), dtype
         (activation storage, 'float32' | 'bfloat16'), bucketed_allreduce (data parallel only: True = one asynchronous SUM
         all-reduce per gradient bucket started inside backward -- the default --, False = ONE all-reduce of the whole buffer
@@ -92,7 +117,20 @@ class TrainerController:
         group.  See train_step and apply_accumulated), trainable (fine-tuning: None or "all" = every layer, "hires" = the hi-res ResBlocks
         and the heads, "heads" = the six head layers, or an iterable of layer names -- FlowNetModel.set_trainable; the same as setting
         `layer.trainable` on self.model.layers as one does in Keras.  Frozen layers get no gradient, no update and no optimiser slots in
-        optimizer.pkl; optimizer.iterations and the bias correction stay global; l2_reg_loss still covers every kernel)."""
+        optimizer.pkl; optimizer.iterations and the bias correction stay global; l2_reg_loss still covers every kernel),
+        global_clipnorm / clipvalue (gradient clipping, the arguments of tf.keras.optimizers.Adam at TrainerController.py:73; at most one,
+        finite and > 0, None = off.  The clipped gradient is the one tape.gradient returns at :223, i.e. flat_g + B 2 lambda w on the
+        trainable kernels -- after accumulation and after the all-reduce, once per optimiser step, on the device.  global_clipnorm = c
+        scales it by c / max(N, c), N its L2 norm over all trainable variables (tf.clip_by_global_norm); clipvalue = c clamps every
+        element to [-c, c].  With global_clipnorm set, last_grad_norm is a view of N on the device and grad_norm_metric its running
+        mean, written as '<name>/grad_norm'; a very large finite value logs the norm without ever clipping.  Keras' per-variable
+        `clipnorm` is not offered.  The attributes of the same names are read on every optimiser step)."""
+        self.global_clipnorm = global_clipnorm
+        self.clipvalue = clipvalue
+        self._checked_clip()
+        self._clip_partials = None     # fdn_grad_sumsq_partials' per-block sums and fdn_clip_scale's (norm, scale): allocated by the first
+        self._clip_out = None          # optimiser step that runs with global_clipnorm set
+        self.last_grad_norm = None     # 0-d view of the norm the last clipped step saw (device; reading it synchronises)
         self.div_weight = div_weight   # TrainerController.py:23
         self._checked_div_weight()
         self.accum_steps = accum_steps
@@ -122,6 +160,7 @@ class TrainerController:
         self.loss_metrics = dict((n, Mean(n, self.device)) for n in names)
         self.accuracy_metric = 'val_loss'
         self.learning_rate = initial_learning_rate
+        self.grad_norm_metric = Mean('grad_norm', self.device)     # outside loss_metrics: the columns of loss.csv stay the reference's
         self.optimizer = _Optimizer(self.model, initial_learning_rate)
         self._l2_buf = torch.zeros(1, device=self.device)
         self._l2_partials = torch.zeros(ops.ADAM_PARTIALS, device=self.device)   # sum(w^2) blocks left by the last Adam step
@@ -166,6 +205,10 @@ class TrainerController:
             raise ValueError("accum_steps must be an integer >= 1, got %r" % (k,))
         return int(k)
 
+    def _checked_clip(self):
+        """(global_clipnorm, clipvalue) as floats or None, validated: see _clip_arguments."""
+        return _clip_arguments(self.global_clipnorm, self.clipvalue)
+
     def calculate_and_update_metrics(self, hires, predictions, mask, metric_set, want_grad):
         """TrainerController.py:84-127 (loss_function, the divergence term live when div_weight != 0), :243-256 (metrics)."""
         div_weight = self._checked_div_weight()
@@ -194,6 +237,7 @@ class TrainerController:
         global batch size), one iteration.  apply_accumulated() closes a group early."""
         if not self.model.any_trainable:                            # Keras: "No gradients provided for any variable"
             raise ValueError("train_step: no layer of the model is trainable (layer.trainable / set_trainable), there is nothing to update")
+        self._checked_clip()                                        # (a bad clipping argument stops the step before anything is launched)
         if self._accum_count == 0:                                  # a group starts: this is where accum_steps is read
             self._accum_k = self._checked_accum_steps()
         if self._accum_k > 1:
@@ -239,7 +283,11 @@ class TrainerController:
         covers all kernels) and a re-pack of the trainable 64->64 layers only."""
         m, opt = self.model, self.optimizer
         frozen = m.frozen_map
-        if frozen is None:
+        clipnorm, clipvalue = self._checked_clip()
+        if clipnorm is not None or clipvalue is not None:
+            self._adam_clipped(g, batch_slot, frozen, clipnorm, clipvalue)
+            m.weights_changed(trainable_only=frozen is not None)
+        elif frozen is None:
             ops.adam_step(m.flat_w, g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
                           2.0 * L2_LAMBDA, batch_slot, sumsq_partials=self._l2_partials)
             m.weights_changed()
@@ -247,6 +295,26 @@ class TrainerController:
             ops.adam_step(m.flat_w, g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
                           2.0 * L2_LAMBDA, batch_slot, sumsq_partials=self._l2_partials, frozen=frozen)
             m.weights_changed(trainable_only=True)
+
+    def _adam_clipped(self, g, batch_slot, frozen, clipnorm, clipvalue):
+        """The step with gradient clipping.  global_clipnorm: two launches ahead of Adam's -- per-block sums of squares of g + B 2 lambda w
+        over the trainable elements, then norm and scale by one block -- and Adam reads the scale from the device: no host synchronisation,
+        and every rank of a data-parallel run computes the same bits from the same all-reduced buffer.  clipvalue: Adam's launch alone."""
+        m, opt = self.model, self.optimizer
+        kw = {} if frozen is None else {"frozen": frozen}
+        if clipnorm is not None:
+            if self._clip_out is None:
+                self._clip_partials = torch.zeros(ops.ADAM_PARTIALS, device=self.device)
+                self._clip_out = torch.zeros(2, device=self.device)
+                self.last_grad_norm = self._clip_out[0]
+            ops.grad_sumsq_partials(g, m.flat_w, m.is_kernel, 2.0 * L2_LAMBDA, batch_slot, self._clip_partials, frozen=frozen)
+            ops.clip_scale(self._clip_partials, clipnorm, self._clip_out)
+            self.grad_norm_metric.update_state(self._clip_out[0:1])
+            kw["g_scale_dev"] = self._clip_out[1:2]
+        else:
+            kw["clip_value"] = clipvalue
+        ops.adam_step(m.flat_w, g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
+                      2.0 * L2_LAMBDA, batch_slot, sumsq_partials=self._l2_partials, **kw)
 
     def _wait_allreduce(self, pending, dp):
         """The current stream waits for the collectives in `pending` (no host synchronisation under nccl)."""
@@ -352,6 +420,7 @@ class TrainerController:
     def reset_metrics(self):
         for k in self.loss_metrics:
             self.loss_metrics[k].reset_states()
+        self.grad_norm_metric.reset_states()
 
     # ------------------------------------------------------------------ directories / logging
     def init_model_dir(self, base_dir="../models"):
@@ -376,6 +445,10 @@ class TrainerController:
         self._log('Initial learning rate: %s\n' % self.learning_rate)
         self._log('Accuracy metric: %s\n' % self.accuracy_metric)
         self._log('Divergence weight: %s\n' % self.div_weight)
+        clipnorm, clipvalue = self._checked_clip()
+        if clipnorm is not None or clipvalue is not None:
+            self._log('Gradient clipping: %s\n' % ('global_clipnorm=%s' % self.global_clipnorm if clipnorm is not None else
+                                                   'clipvalue=%s' % self.clipvalue))
         stat_names = ','.join(self.loss_metrics.keys())
         self._log('epoch, %s, learning rate, elapsed (sec), best_model, benchmark_err, benchmark_rel_err, '
                   'benchmark_mse, benchmark_divloss\n' % stat_names)
@@ -387,14 +460,19 @@ class TrainerController:
             if fname.endswith(".py"):
                 shutil.copy2(os.path.join(here, fname), os.path.join(dest, fname))
 
-    def _update_summary_logging(self, epoch, results=None):
+    def _update_summary_logging(self, epoch, results=None, grad_norm=None):
         """TrainerController.py:396-412: epoch-level scalars.  Train writer: '<name>/learning_rate' and every 'train_*' metric
         with the prefix stripped ('<name>/loss', '/accuracy', '/mse', '/div'); validate writer: the 'val_*' metrics likewise;
         step = the 0-based epoch.  ('l2_reg_loss' has neither prefix, so the reference does not log it -- nor do we.)
-        results: metric name -> value (the rank-combined epoch means); defaults to this process's running means."""
+        results: metric name -> value (the rank-combined epoch means); defaults to this process's running means.
+        grad_norm: the epoch mean of the gradient norm, written as '<name>/grad_norm' on the train writer when global_clipnorm is set
+        (no counterpart in the reference, which does not clip); defaults to this process's running mean."""
         if results is None:
             results = dict((k, v.result()) for k, v in self.loss_metrics.items())
         self.train_writer.scalar("%s/learning_rate" % self.network_name, self.optimizer.lr, epoch)
+        if self._checked_clip()[0] is not None:
+            self.train_writer.scalar("%s/grad_norm" % self.network_name,
+                                     self.grad_norm_metric.result() if grad_norm is None else grad_norm, epoch)
         for k in self.loss_metrics:
             if k.startswith('train_'):
                 self.train_writer.scalar("%s/%s" % (self.network_name, k.replace('train_', '')), results[k], epoch)
@@ -485,13 +563,14 @@ class TrainerController:
             # data parallel: every rank saw a shard of each global batch -> combine (total, count) over ranks, so
             # loss.csv and the best-model decision do not depend on the world size
             res = dict((k, v.result_global()) for k, v in self.loss_metrics.items())
+            grad_norm = self.grad_norm_metric.result_global() if self._checked_clip()[0] is not None else None
             message = "\rEpoch %d Train loss: %.5f (%.1f %%), Val loss: %.5f (%.1f %%) - %.1f secs" % (
                 epoch + 1, res['train_loss'], res['train_accuracy'], res['val_loss'], res['val_accuracy'],
                 time.time() - start_loop)
             loss_str = ','.join('%.5f' % res[k] for k in self.loss_metrics)
             log_line = "%d,%s,%.6f,%.1f" % (epoch + 1, loss_str, self.optimizer.lr, time.time() - start_loop)
             if is0:
-                self._update_summary_logging(epoch, res)
+                self._update_summary_logging(epoch, res, grad_norm)
             if res[self.accuracy_metric] < previous_loss:
                 if is0:
                     self.save_best_model()

@@ -371,6 +371,43 @@ int fdn_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* 
  * checkpoint): the multi-block form of fdn_l2_sumsq, which needs no scratch and runs as ONE block.  Follow with fdn_sum_partials. */
 int fdn_l2_sumsq_partials(const float* w, const uint8_t* is_kernel, int64_t n, float* sumsq_partials, void* stream);
 
+/* Gradient clipping: what tf.keras.optimizers.Adam(global_clipnorm=c) / Adam(clipvalue=c) do to the gradient before the update
+ * (the reference builds its optimizer at TrainerController.py:73 and applies tape.gradient's result at :223-225; the L2 regulariser's
+ * gradient is part of that result, so it is part of what is clipped).  The step's gradient is
+ *     g'_i = g_i + l2s * w_i for kernel elements, g_i for biases,   l2s = l2_grad_scale * l2_scale_dev[0] (l2_grad_scale alone if NULL),
+ * formed in fp32 as fdn_adam_step forms it, over the elements with frozen[i] == 0 (every element if frozen == NULL).
+ *
+ * fdn_grad_sumsq_partials: partials[b] (FDN_ADAM_PARTIALS floats) = block b's sum of g'_i^2 on the blocking of fdn_adam_step with
+ * partials (block b takes the elements b * 256 + t + k * FDN_ADAM_PARTIALS * 256); no atomics, a fixed order, blocks beyond the data write 0.
+ * Where frozen[i] != 0, g[i] is not read (a NaN there is harmless) and the element adds +0.  Nothing but partials is written.  A path of
+ * the Adam kernel.  TrainerController.py:73,223-225.
+ * Refused before the device is touched, the message naming the argument: NULL g, w, is_kernel or partials, n <= 0. */
+int fdn_grad_sumsq_partials(const float* g, const float* w, const uint8_t* is_kernel, const uint8_t* frozen /* NULL ok */, int64_t n,
+                            float l2_grad_scale, const float* l2_scale_dev /* NULL ok */, float* partials, void* stream);
+/* tf.clip_by_global_norm's factor from those partials, one block, fixed order (a path of the kernel behind fdn_sum_partials):
+ *     out[0] = N = sqrtf(sum of the n_partials partials) = sqrt(sum g'_i^2),     out[1] = s = clip_norm / max(N, clip_norm).
+ * s is exactly 1.0f whenever N <= clip_norm: an inactive clip changes no bit.  TF writes clip_norm * min(1 / N, 1 / clip_norm), which
+ * rounds twice where this rounds once; the two agree to rounding.  Non-finite rule: if N is not finite (an inf or NaN gradient, or
+ * squares that overflow fp32), s = NaN, and the clipped step makes every unfrozen parameter NaN -- TF: "entries are all set to NaN to
+ * signify that an error occurred".  Both floats stay on the device: out[0] is for telemetry, out + 1 is the g_scale_dev of
+ * fdn_adam_step_clipped.  TrainerController.py:73,223-225.
+ * Refused before the device is touched: NULL partials or out, n_partials <= 0, clip_norm not finite or <= 0. */
+int fdn_clip_scale(const float* partials, int n_partials, float clip_norm, float* out /* 2 floats */, void* stream);
+/* The Adam step on the clipped gradient (TrainerController.py:73,223-225): the operands of fdn_adam_step_masked (frozen and lr_t_dev may
+ * be NULL here) and
+ *     g_scale_dev != NULL: g''_i = g'_i * g_scale_dev[0]  (global_clipnorm: one fp32 multiply behind the L2 term, s of fdn_clip_scale);
+ *     clip_value > 0:      g''_i = g'_i > clip_value ? clip_value : (g'_i < -clip_value ? -clip_value : g'_i)  (clipvalue: comparisons,
+ *                          so a NaN gradient stays NaN);   with both, the multiply comes first.
+ * Everything behind g'' is fdn_adam_step's arithmetic statement for statement: m, v, the update, sumsq_partials of the new parameters.
+ * With g_scale_dev == NULL and clip_value == 0 the results are bit-identical to fdn_adam_step / fdn_adam_step_dev /
+ * fdn_adam_step_masked on the same operands; so they are with g_scale_dev[0] == 1.0f.  Non-finite rule: g_scale_dev[0] = NaN makes
+ * w, m and v of every unfrozen element NaN; frozen elements keep their bits.
+ * Refused before the device is touched, the message naming the argument: NULL w, g, m, v or is_kernel, n <= 0, clip_value negative or NaN. */
+int fdn_adam_step_clipped(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, const uint8_t* frozen /* NULL ok */,
+                          int64_t n, float lr_t, const float* lr_t_dev /* NULL ok */, float b1, float b2, float eps, float l2_grad_scale,
+                          const float* l2_scale_dev /* NULL ok */, const float* g_scale_dev /* NULL ok */, float clip_value,
+                          float* sumsq_partials /* NULL ok */, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * bf16 activation path (BASELINE.json configs[3]: patch 32, res x4, bf16).  The reference has no bf16
  * mode (TF runs fp32); semantics = the fp32 entry points above with every activation / activation-gradient
