@@ -1046,16 +1046,35 @@ extern "C" int fdn_l2_sumsq_partials(const float* w, const uint8_t* is_kernel, i
     return FDN_OK;
 }
 
+// adam_kernel's parameters by name (the kernel keeps its flat list): an entry point sets what its path reads, the rest stays "absent".
+struct AdamOperands {
+    float *w = nullptr, *m = nullptr, *v = nullptr, *sumsq = nullptr;
+    const float *g = nullptr, *lr_t_dev = nullptr, *l2_scale_dev = nullptr, *g_scale_dev = nullptr;
+    const uint8_t *is_kernel = nullptr, *frozen = nullptr;
+    int64_t n = 0;
+    float lr_t = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f, l2_grad_scale = 0.f, clip_value = 0.f;
+    int accum = 0;
+};
+
+// The one place adam_kernel is launched from.
+static int launch_adam(const AdamOperands& a, int grid, hipStream_t stream, const char* what) {
+    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, stream, a.w, a.g, a.m, a.v, a.is_kernel, a.n, a.lr_t, a.lr_t_dev, a.b1, a.b2,
+                       a.eps, a.l2_grad_scale, a.l2_scale_dev, a.sumsq, a.accum, a.frozen, a.g_scale_dev, a.clip_value);
+    FDN_CHECK_LAUNCH(what);
+    return FDN_OK;
+}
+
+// The grid of the four Adam steps: fixed at FDN_ADAM_PARTIALS blocks when partials are requested (blocks beyond the data write 0).
+static int adam_step_grid(int64_t n, const float* sumsq_partials) { return sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048); }
+
 extern "C" int fdn_adam_step(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, int64_t n, float lr_t,
                              float b1, float b2, float eps, float l2_grad_scale, const float* l2_scale_dev,
                              float* sumsq_partials, void* stream) {
     FDN_REQUIRE(w && g && m && v && is_kernel && n > 0, "fdn_adam_step: bad argument");
-    // fixed grid of FDN_ADAM_PARTIALS blocks when partials are requested (blocks beyond the data write 0)
-    const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       lr_t, (const float*)nullptr, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, (const uint8_t*)nullptr, (const float*)nullptr, 0.f);
-    FDN_CHECK_LAUNCH("adam_kernel");
-    return FDN_OK;
+    AdamOperands a;
+    a.w = w, a.g = g, a.m = m, a.v = v, a.is_kernel = is_kernel, a.n = n, a.b1 = b1, a.b2 = b2, a.eps = eps;
+    a.l2_grad_scale = l2_grad_scale, a.l2_scale_dev = l2_scale_dev, a.sumsq = sumsq_partials, a.lr_t = lr_t;
+    return launch_adam(a, adam_step_grid(n, sumsq_partials), (hipStream_t)stream, "adam_kernel");
 }
 
 extern "C" int fdn_adam_step_dev(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, int64_t n,
@@ -1064,11 +1083,10 @@ extern "C" int fdn_adam_step_dev(float* w, const float* g, float* m, float* v, c
     FDN_REQUIRE(w && g && m && v && is_kernel, "fdn_adam_step_dev: NULL operand");
     FDN_REQUIRE(lr_t_dev, "fdn_adam_step_dev: lr_t_dev is NULL (fdn_adam_step takes the step size by value)");
     FDN_REQUIRE(n > 0, "fdn_adam_step_dev: n=%lld must be positive", (long long)n);
-    const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       0.f, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, (const uint8_t*)nullptr, (const float*)nullptr, 0.f);
-    FDN_CHECK_LAUNCH("adam_kernel");
-    return FDN_OK;
+    AdamOperands a;
+    a.w = w, a.g = g, a.m = m, a.v = v, a.is_kernel = is_kernel, a.n = n, a.b1 = b1, a.b2 = b2, a.eps = eps;
+    a.l2_grad_scale = l2_grad_scale, a.l2_scale_dev = l2_scale_dev, a.sumsq = sumsq_partials, a.lr_t_dev = lr_t_dev;
+    return launch_adam(a, adam_step_grid(n, sumsq_partials), (hipStream_t)stream, "adam_kernel");
 }
 
 extern "C" int fdn_adam_step_masked(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, const uint8_t* frozen, int64_t n,
@@ -1081,11 +1099,11 @@ extern "C" int fdn_adam_step_masked(float* w, const float* g, float* m, float* v
     FDN_REQUIRE(is_kernel, "fdn_adam_step_masked: is_kernel is NULL");
     FDN_REQUIRE(frozen, "fdn_adam_step_masked: frozen is NULL (fdn_adam_step / fdn_adam_step_dev update every element)");
     FDN_REQUIRE(n > 0, "fdn_adam_step_masked: n=%lld must be positive", (long long)n);
-    const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);       // the grid rule of fdn_adam_step
-    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       lr_t, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, frozen, (const float*)nullptr, 0.f);
-    FDN_CHECK_LAUNCH("adam_kernel (masked)");
-    return FDN_OK;
+    AdamOperands a;
+    a.w = w, a.g = g, a.m = m, a.v = v, a.is_kernel = is_kernel, a.n = n, a.b1 = b1, a.b2 = b2, a.eps = eps;
+    a.l2_grad_scale = l2_grad_scale, a.l2_scale_dev = l2_scale_dev, a.sumsq = sumsq_partials;
+    a.lr_t = lr_t, a.lr_t_dev = lr_t_dev, a.frozen = frozen;
+    return launch_adam(a, adam_step_grid(n, sumsq_partials), (hipStream_t)stream, "adam_kernel (masked)");
 }
 
 extern "C" int fdn_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream) {
@@ -1098,11 +1116,9 @@ extern "C" int fdn_grad_accumulate(float* acc, const float* g, int64_t n, int fi
     FDN_REQUIRE((uint64_t)n <= (UINTPTR_MAX - (a > b ? a : b)) / sizeof(float), "fdn_grad_accumulate: n=%lld floats run past the address space", (long long)n);
     FDN_REQUIRE((a > b ? a - b : b - a) >= bytes, "fdn_grad_accumulate: acc and g overlap (%lld bytes apart, n=%lld floats): an in-place call would double the buffer",
                 (long long)(a > b ? a - b : b - a), (long long)n);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, acc, g, (float*)nullptr, (float*)nullptr,
-                       (const uint8_t*)nullptr, n, 0.f, (const float*)nullptr, 0.f, 0.f, 0.f, 0.f, (const float*)nullptr, (float*)nullptr,
-                       first ? ACCUM_FIRST : ACCUM_ADD, (const uint8_t*)nullptr, (const float*)nullptr, 0.f);
-    FDN_CHECK_LAUNCH("adam_kernel (grad accumulate)");
-    return FDN_OK;
+    AdamOperands op;
+    op.w = acc, op.g = g, op.n = n, op.accum = first ? ACCUM_FIRST : ACCUM_ADD;
+    return launch_adam(op, grid_for(n), (hipStream_t)stream, "adam_kernel (grad accumulate)");
 }
 
 extern "C" int fdn_sum_partials(const float* partials, int n, float* out, void* stream) {
@@ -1122,11 +1138,10 @@ extern "C" int fdn_grad_sumsq_partials(const float* g, const float* w, const uin
     FDN_REQUIRE(is_kernel, "fdn_grad_sumsq_partials: is_kernel is NULL");
     FDN_REQUIRE(partials, "fdn_grad_sumsq_partials: partials is NULL");
     FDN_REQUIRE(n > 0, "fdn_grad_sumsq_partials: n=%lld must be positive", (long long)n);
-    hipLaunchKernelGGL(adam_kernel, dim3(FDN_ADAM_PARTIALS), dim3(256), 0, (hipStream_t)stream, const_cast<float*>(w), g, (float*)nullptr,
-                       (float*)nullptr, is_kernel, n, 0.f, (const float*)nullptr, 0.f, 0.f, 0.f, l2_grad_scale, l2_scale_dev, partials,
-                       GRAD_SUMSQ, frozen, (const float*)nullptr, 0.f);
-    FDN_CHECK_LAUNCH("adam_kernel (gradient sum of squares)");
-    return FDN_OK;
+    AdamOperands a;
+    a.w = const_cast<float*>(w), a.g = g, a.is_kernel = is_kernel, a.n = n;          // (this path only reads w)
+    a.l2_grad_scale = l2_grad_scale, a.l2_scale_dev = l2_scale_dev, a.sumsq = partials, a.accum = GRAD_SUMSQ, a.frozen = frozen;
+    return launch_adam(a, FDN_ADAM_PARTIALS, (hipStream_t)stream, "adam_kernel (gradient sum of squares)");
 }
 
 extern "C" int fdn_clip_scale(const float* partials, int n_partials, float clip_norm, float* out, void* stream) {
@@ -1150,9 +1165,9 @@ extern "C" int fdn_adam_step_clipped(float* w, const float* g, float* m, float* 
     FDN_REQUIRE(is_kernel, "fdn_adam_step_clipped: is_kernel is NULL");
     FDN_REQUIRE(n > 0, "fdn_adam_step_clipped: n=%lld must be positive", (long long)n);
     FDN_REQUIRE(clip_value >= 0.f, "fdn_adam_step_clipped: clip_value=%g must be >= 0 (0 = off)", (double)clip_value);      // (false for NaN)
-    const int grid = sumsq_partials ? FDN_ADAM_PARTIALS : grid_for(n, 2048);       // the grid rule of fdn_adam_step
-    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, is_kernel, n,
-                       lr_t, lr_t_dev, b1, b2, eps, l2_grad_scale, l2_scale_dev, sumsq_partials, 0, frozen, g_scale_dev, clip_value);
-    FDN_CHECK_LAUNCH("adam_kernel (clipped)");
-    return FDN_OK;
+    AdamOperands a;
+    a.w = w, a.g = g, a.m = m, a.v = v, a.is_kernel = is_kernel, a.n = n, a.b1 = b1, a.b2 = b2, a.eps = eps;
+    a.l2_grad_scale = l2_grad_scale, a.l2_scale_dev = l2_scale_dev, a.sumsq = sumsq_partials;
+    a.lr_t = lr_t, a.lr_t_dev = lr_t_dev, a.frozen = frozen, a.g_scale_dev = g_scale_dev, a.clip_value = clip_value;
+    return launch_adam(a, adam_step_grid(n, sumsq_partials), (hipStream_t)stream, "adam_kernel (clipped)");
 }

@@ -516,7 +516,8 @@ def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_
     leaves behind) multiplies the gradient, L2 term included, on the device; clip_value > 0 clamps every element of it to
     [-clip_value, clip_value].  Neither: the entry points above, as always."""
     clip_value = float(clip_value)
-    if g_scale_dev is not None or clip_value != 0.0:
+    clipped = g_scale_dev is not None or clip_value != 0.0
+    if clipped:
         if g_scale_dev is not None and clip_value != 0.0:
             raise FdnError("adam_step: g_scale_dev and clip_value are both set (global_clipnorm and clipvalue exclude each other)")
         if g_scale_dev is not None and (not g_scale_dev.is_cuda or g_scale_dev.dtype != torch.float32 or g_scale_dev.numel() != 1):
@@ -529,31 +530,23 @@ def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_
         raise FdnError("adam_step: lr_t_dev must hold one float32 on the GPU")
     if frozen is not None and frozen.numel() != w.numel():
         raise FdnError("adam_step: frozen holds %d bytes for %d parameters" % (frozen.numel(), w.numel()))
-    if g_scale_dev is not None or clip_value != 0.0:
-        check(_lib.load().fdn_adam_step_clipped(_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel"), _pu8(frozen, "frozen", allow_none=True),
-                                                w.numel(), 0.0 if lr_t_dev is not None else float(lr_t), _p(lr_t_dev, allow_none=True), float(b1),
-                                                float(b2), float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
-                                                _p(g_scale_dev, "g_scale_dev", allow_none=True), clip_value, _p(sumsq_partials, allow_none=True),
-                                                _stream()),
-              "fdn_adam_step_clipped")
-        return
-    if frozen is not None:
-        check(_lib.load().fdn_adam_step_masked(_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel"), _pu8(frozen, "frozen"), w.numel(),
-                                               0.0 if lr_t_dev is not None else float(lr_t), _p(lr_t_dev, allow_none=True), float(b1), float(b2),
-                                               float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
-                                               _p(sumsq_partials, allow_none=True), _stream()),
-              "fdn_adam_step_masked")
-        return
-    if lr_t_dev is not None:
-        check(_lib.load().fdn_adam_step_dev(_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel"), w.numel(), _p(lr_t_dev), float(b1), float(b2),
-                                            float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
-                                            _p(sumsq_partials, allow_none=True), _stream()),
-              "fdn_adam_step_dev")
-        return
-    check(_lib.load().fdn_adam_step(_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel"), w.numel(), float(lr_t), float(b1), float(b2),
-                                    float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True),
-                                    _p(sumsq_partials, allow_none=True), _stream()),
-          "fdn_adam_step")
+    lib = _lib.load()
+    # every operand once, in the order the widest entry point takes them; the four argument lists below differ in what they leave out
+    bufs = [_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel")]
+    frozen_p, n = _pu8(frozen, "frozen", allow_none=True), w.numel()
+    lr = [0.0 if lr_t_dev is not None else float(lr_t), _p(lr_t_dev, allow_none=True)]
+    hyper = [float(b1), float(b2), float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True)]
+    clip = [_p(g_scale_dev, "g_scale_dev", allow_none=True), clip_value]
+    tail = [_p(sumsq_partials, allow_none=True), _stream()]
+    if clipped:
+        entry, args = "fdn_adam_step_clipped", bufs + [frozen_p, n] + lr + hyper + clip + tail
+    elif frozen is not None:
+        entry, args = "fdn_adam_step_masked", bufs + [frozen_p, n] + lr + hyper + tail
+    elif lr_t_dev is not None:
+        entry, args = "fdn_adam_step_dev", bufs + [n] + lr[1:] + hyper + tail
+    else:
+        entry, args = "fdn_adam_step", bufs + [n] + lr[:1] + hyper + tail
+    check(getattr(lib, entry)(*args), entry)
 
 
 def grad_accumulate(acc, g, first):

@@ -233,74 +233,114 @@ class TrainerController:
         move inside a group, so the L2 term and the per-sample losses are those of the big batch), and model.flat_g_ext is left holding
         this micro-batch's own local gradient and batch size.  Calls 1 .. K-1 add it into self.accum_g_ext (fdn_grad_accumulate) and
         stop there: no collective, no Adam launch, optimizer.iterations / flat_w / m / v / weights_version / the packs untouched.  Call K
-        accumulates, all-reduces the ACCUMULATOR over the ranks if data parallel, and runs Adam on it (its trailing slot = the group's
-        global batch size), one iteration.  apply_accumulated() closes a group early."""
+        accumulates and closes the step (_close_step) on the ACCUMULATOR, whose trailing slot is then the group's global batch size.
+        apply_accumulated() closes a group early.  K = 1 is the same body with model.flat_g_ext as the step buffer (_step_buffer) and
+        nothing to accumulate: every call closes.
+
+        The trailing slot of the gradient buffer carries this rank's batch size; after the SUM all-reduce the step buffer's slot holds
+        the global batch size, which the Adam kernel reads on the device -- no host synchronisation per step.
+
+        Data parallel with bucketed_allreduce, on the closing call: one SUM all-reduce per bucket of the step buffer, started inside
+        backward()'s grad_ready callback as soon as the bucket's last launch has been enqueued (RCCL works on its own stream: the hi-res
+        bucket travels while the low-res layers are still computing).  Every rank issues the same buckets in the same order, also a rank
+        whose shard of a ragged batch is empty.  Otherwise ONE all-reduce of the whole step buffer after backward (_close_step).
+
+        Stream order of the accumulate (K > 1): where no per-bucket collective runs -- calls 1 .. K-1, and a closing call that is not
+        both data parallel and bucketed -- ONE launch over the whole buffer on the main stream after backward() has returned, i.e. behind
+        its join of the weight-gradient stream.  Else the accumulate of bucket [lo, hi) is issued inside the grad_ready callback, on the
+        stream that callback runs on (the weight-gradient stream once it has been made to wait for the main one, see
+        FlowNetModel.backward): behind every writer of the bucket and behind the earlier micro-steps' accumulates, ahead of the bucket's
+        all-reduce, which is started from the same stream right after it; _close_step then joins that stream before Adam."""
         if not self.model.any_trainable:                            # Keras: "No gradients provided for any variable"
             raise ValueError("train_step: no layer of the model is trainable (layer.trainable / set_trainable), there is nothing to update")
         self._checked_clip()                                        # (a bad clipping argument stops the step before anything is launched)
         if self._accum_count == 0:                                  # a group starts: this is where accum_steps is read
             self._accum_k = self._checked_accum_steps()
-        if self._accum_k > 1:
-            return self._train_micro_step(data_pairs)
         inputs, hires, venc, mask = self._unpack(data_pairs)
         B = inputs[0].shape[0]
         m = self.model
-        # The trailing slot of the gradient buffer carries this rank's batch size; after the SUM all-reduce it holds the
-        # global batch size, which the Adam kernel reads on the device -- no host synchronisation per step.
         m.batch_slot.fill_(float(B))
-        # Data parallel: one SUM all-reduce per gradient bucket, started as soon as backward() has enqueued the bucket's last
-        # launch (RCCL works on its own stream: the hi-res bucket travels while the low-res layers are still computing).  Every
-        # rank issues the same buckets in the same order, also a rank whose shard of a ragged batch is empty.
-        pending = []
-        reduce_bucket = None
-        dp = parallel.world_size() > 1
-        if dp and self.bucketed_allreduce:
-            def reduce_bucket(lo, hi):
-                pending.append(parallel.allreduce_sum_start(m.flat_g_ext[lo:hi]))
+        buf = self._step_buffer()
+        closing = self._accum_count + 1 >= self._accum_k            # (K = 1: always)
+        first = not self._accum_has
+        contribute = None                                           # (K = 1: the gradient already is where the step reads it)
+        if self._accum_k > 1:
+            def contribute(lo, hi):
+                ops.grad_accumulate(buf[lo:hi], m.flat_g_ext[lo:hi], first)
+        pending = on_bucket = None
+        if closing and self.bucketed_allreduce and parallel.world_size() > 1:
+            pending = []
+
+            def on_bucket(lo, hi):
+                if contribute is not None and B > 0:
+                    contribute(lo, hi)
+                pending.append(parallel.allreduce_sum_start(buf[lo:hi]))
         if B > 0:
             pred = m.forward(inputs, training=True)
             loss, dpred = self.calculate_and_update_metrics(hires, pred, mask, 'train', True)
-            m.backward(dpred, grad_ready=reduce_bucket)
-        else:                                   # ragged tail on this rank: contribute a zero gradient
-            m.flat_g.zero_()
+            m.backward(dpred, grad_ready=on_bucket)
+            if contribute is not None:
+                if on_bucket is None:
+                    contribute(0, buf.numel())
+                self._accum_has = True
+        else:                                   # ragged tail on this rank: a zero gradient, which contributes nothing to an accumulator;
+            m.flat_g.zero_()                    # the rank still joins the step's collectives
             loss = None
-            if reduce_bucket is not None:
+            if on_bucket is not None:
+                if contribute is not None and first:        # every micro-batch of this rank's group was empty: it reduces zeros
+                    buf.zero_()
+                    self._accum_has = True
                 for lo, hi in m.grad_buckets:
-                    reduce_bucket(lo, hi)
-        if dp and not self.bucketed_allreduce:             # the plain form: one collective over the whole buffer after backward
-            pending.append(parallel.allreduce_sum_start(m.flat_g_ext))
-        self._wait_allreduce(pending, dp)
-        opt = self.optimizer
-        opt.iterations += 1
-        # L2 regulariser gradient: the (B,) loss vector carries the scalar L2 term B times (:249) -> B_global * 2*lambda*w
-        self._adam(m.flat_g, m.batch_slot)
-        self._l2_version = m.weights_version
+                    on_bucket(lo, hi)
+        if contribute is not None:
+            self._accum_count += 1
+        if closing:
+            self._close_step(pending)
         return loss
 
+    def _step_buffer(self):
+        """What the running step's collectives reduce and its Adam launch reads, (n_params + 1,): model.flat_g_ext when every call is a
+        step, else the accumulator (allocated by the first micro-step of the first group; never memset: the first contribution of a
+        group is a copy)."""
+        if self._accum_k == 1:
+            return self.model.flat_g_ext
+        if self.accum_g_ext is None:
+            self.accum_g_ext = torch.empty_like(self.model.flat_g_ext)
+        return self.accum_g_ext
+
+    def _close_step(self, pending=None):
+        """The end of an optimiser step: reduce the step buffer over the ranks (pending: the per-bucket collectives the closing call
+        has already started; None: one all-reduce of the whole buffer here), wait, and run ONE Adam step on it, one iteration."""
+        m, buf = self.model, self._step_buffer()
+        grouped = self._accum_k > 1
+        dp = parallel.world_size() > 1
+        if pending is None:
+            pending = []
+            if grouped and not self._accum_has:
+                buf.zero_()
+            if dp:
+                pending.append(parallel.allreduce_sum_start(buf))
+        self._wait_allreduce(pending, dp)
+        if grouped:                             # the accumulates the grad_ready callbacks put on the weight-gradient stream: ahead of Adam
+            m._join_side()                      # whatever the transport (K = 1 puts only collectives there, and those were just waited for)
+        self.optimizer.iterations += 1
+        n = m.n_params
+        self._adam(buf[:n], buf[n:n + 1])
+        self._l2_version = m.weights_version
+        self._accum_count = 0
+        self._accum_has = False
+
     def _adam(self, g, batch_slot):
-        """One Adam launch on the flat buffers and the re-pack of what moved.  With frozen layers: the masked path of the same kernel
-        (their parameters and slots keep their bits, the L2 gradient reaches trainable kernels only, the sum of squares it leaves still
-        covers all kernels) and a re-pack of the trainable 64->64 layers only."""
+        """One Adam launch on the flat buffers and the re-pack of what moved; the L2 regulariser's gradient is formed inside it: the (B,)
+        loss vector carries the scalar L2 term B times (:249) -> B_global * 2 lambda w, B_global read from batch_slot.
+        With frozen layers: the masked path of the same kernel (their parameters and slots keep their bits, the L2 gradient reaches
+        trainable kernels only, the sum of squares it leaves still covers all kernels) and a re-pack of the trainable 64->64 layers only.
+        global_clipnorm: two launches ahead of Adam's -- per-block sums of squares of g + B 2 lambda w over the trainable elements, then
+        norm and scale by one block -- and Adam reads the scale from the device: no host synchronisation, and every rank of a
+        data-parallel run computes the same bits from the same all-reduced buffer.  clipvalue: Adam's launch alone."""
         m, opt = self.model, self.optimizer
         frozen = m.frozen_map
         clipnorm, clipvalue = self._checked_clip()
-        if clipnorm is not None or clipvalue is not None:
-            self._adam_clipped(g, batch_slot, frozen, clipnorm, clipvalue)
-            m.weights_changed(trainable_only=frozen is not None)
-        elif frozen is None:
-            ops.adam_step(m.flat_w, g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
-                          2.0 * L2_LAMBDA, batch_slot, sumsq_partials=self._l2_partials)
-            m.weights_changed()
-        else:
-            ops.adam_step(m.flat_w, g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
-                          2.0 * L2_LAMBDA, batch_slot, sumsq_partials=self._l2_partials, frozen=frozen)
-            m.weights_changed(trainable_only=True)
-
-    def _adam_clipped(self, g, batch_slot, frozen, clipnorm, clipvalue):
-        """The step with gradient clipping.  global_clipnorm: two launches ahead of Adam's -- per-block sums of squares of g + B 2 lambda w
-        over the trainable elements, then norm and scale by one block -- and Adam reads the scale from the device: no host synchronisation,
-        and every rank of a data-parallel run computes the same bits from the same all-reduced buffer.  clipvalue: Adam's launch alone."""
-        m, opt = self.model, self.optimizer
         kw = {} if frozen is None else {"frozen": frozen}
         if clipnorm is not None:
             if self._clip_out is None:
@@ -311,10 +351,11 @@ class TrainerController:
             ops.clip_scale(self._clip_partials, clipnorm, self._clip_out)
             self.grad_norm_metric.update_state(self._clip_out[0:1])
             kw["g_scale_dev"] = self._clip_out[1:2]
-        else:
+        elif clipvalue is not None:
             kw["clip_value"] = clipvalue
         ops.adam_step(m.flat_w, g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
                       2.0 * L2_LAMBDA, batch_slot, sumsq_partials=self._l2_partials, **kw)
+        m.weights_changed(trainable_only=frozen is not None)
 
     def _wait_allreduce(self, pending, dp):
         """The current stream waits for the collectives in `pending` (no host synchronisation under nccl)."""
@@ -328,75 +369,6 @@ class TrainerController:
             self.allreduce_wait_events.append((e0, e1))
             del self.allreduce_wait_events[:-4096]          # a diagnostic left on outside the bench must not grow without bound
 
-    # ------------------------------------------------------------------ gradient accumulation (accum_steps > 1)
-    def _train_micro_step(self, data_pairs):
-        """One micro-batch of a group of self._accum_k (see train_step).  Stream order: on calls 1 .. K-1, and on the closing call
-        without per-bucket collectives, ONE accumulate launch of the whole buffer is issued on the main stream after backward() has
-        returned, i.e. behind its join of the weight-gradient stream.  On the closing call of a data-parallel run with
-        bucketed_allreduce the accumulate of bucket [lo, hi) is issued inside backward()'s grad_ready callback, on the stream that
-        callback runs on (the weight-gradient stream once it has been made to wait for the main one, see FlowNetModel.backward): behind
-        every writer of the bucket and behind the earlier micro-steps' accumulates, ahead of the bucket's all-reduce, which is started
-        from the same stream right after it; the main stream then waits for the collectives and joins that stream before Adam."""
-        inputs, hires, venc, mask = self._unpack(data_pairs)
-        B = inputs[0].shape[0]
-        m = self.model
-        m.batch_slot.fill_(float(B))
-        if self.accum_g_ext is None:
-            self.accum_g_ext = torch.empty_like(m.flat_g_ext)       # (never memset: the first contribution of a group is a copy)
-        acc = self.accum_g_ext
-        closing = self._accum_count + 1 >= self._accum_k
-        first = not self._accum_has
-        pending = None
-        on_bucket = None
-        if closing and self.bucketed_allreduce and parallel.world_size() > 1:
-            pending = []
-
-            def on_bucket(lo, hi):
-                if B > 0:
-                    ops.grad_accumulate(acc[lo:hi], m.flat_g_ext[lo:hi], first)
-                pending.append(parallel.allreduce_sum_start(acc[lo:hi]))
-        if B > 0:
-            pred = m.forward(inputs, training=True)
-            loss, dpred = self.calculate_and_update_metrics(hires, pred, mask, 'train', True)
-            m.backward(dpred, grad_ready=on_bucket)
-            if on_bucket is None:
-                ops.grad_accumulate(acc, m.flat_g_ext, first)
-            self._accum_has = True
-        else:                                   # an empty shard contributes nothing; the rank still joins the group's collectives
-            m.flat_g.zero_()
-            loss = None
-            if on_bucket is not None:
-                if first:                       # every micro-batch of this rank's group was empty: it reduces zeros
-                    acc.zero_()
-                    self._accum_has = True
-                for lo, hi in m.grad_buckets:
-                    on_bucket(lo, hi)
-        self._accum_count += 1
-        if closing:
-            self._apply_group(pending)
-        return loss
-
-    def _apply_group(self, pending=None):
-        """Reduce the accumulator over the ranks (pending: the per-bucket collectives the closing micro-step has already started; None:
-        one all-reduce of the whole buffer here) and run ONE Adam step on it."""
-        m, acc = self.model, self.accum_g_ext
-        dp = parallel.world_size() > 1
-        if pending is None:
-            pending = []
-            if not self._accum_has:
-                acc.zero_()
-            if dp:
-                pending.append(parallel.allreduce_sum_start(acc))
-        self._wait_allreduce(pending, dp)
-        m._join_side()                          # what the grad_ready callbacks put on the weight-gradient stream: ahead of Adam whatever the transport
-        opt = self.optimizer
-        opt.iterations += 1
-        n = m.n_params
-        self._adam(acc[:n], acc[n:n + 1])
-        self._l2_version = m.weights_version
-        self._accum_count = 0
-        self._accum_has = False
-
     def apply_accumulated(self):
         """Apply whatever the running group has accumulated as a shorter group: one accumulator all-reduce if data parallel (every
         rank must call it: the ranks see the same number of micro-steps), one Adam step, one iteration.  A strict no-op when nothing
@@ -405,7 +377,7 @@ class TrainerController:
         epoch boundary."""
         if self._accum_count == 0:
             return False
-        self._apply_group()
+        self._close_step()
         return True
 
     def test_step(self, data_pairs):
