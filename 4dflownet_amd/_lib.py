@@ -60,6 +60,7 @@ SIGNATURES = {
     "fdn_grad_sumsq_partials": (c_i, [c_fp] * 4 + [c_i64, c_f, c_fp, c_fp, c_fp]),
     "fdn_clip_scale": (c_i, [c_fp, c_i, c_f, c_fp, c_fp]),
     "fdn_adam_step_clipped": (c_i, [c_fp] * 6 + [c_i64, c_f, c_fp] + [c_f] * 4 + [c_fp, c_fp, c_f, c_fp, c_fp]),
+    "fdn_adam_step_ema": (c_i, [c_fp] * 6 + [c_i64, c_f, c_fp] + [c_f] * 4 + [c_fp, c_fp, c_f, c_fp, c_f, c_i, c_fp, c_fp]),
     "fdn_pack_conv64_weights_batch": (c_i, [c_fp, c_fp, c_i, c_fp, c_fp]),
     "fdn_conv64_pack_streams": (c_i, [c_i] * 6),
     "fdn_pack_conv64_weights_batch_streams": (c_i, [c_fp, c_fp, c_i, c_fp, c_i, c_i, c_fp]),

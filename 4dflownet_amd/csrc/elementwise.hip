@@ -717,6 +717,10 @@ __device__ __forceinline__ void block_partial(float ss, float* __restrict__ out)
 // value covers every kernel (TrainerController.py:129-141).  An element with frozen[i] == 0 takes the statements below unchanged.
 // g_scale_dev != null / clip_value > 0 (fdn_adam_step_clipped): g' *= g_scale_dev[0] (one fp32 multiply behind the L2 term: the scale
 // fdn_clip_scale left on the device) / g' clamped to [-clip_value, clip_value] by comparisons, so that a NaN stays a NaN.
+// ema != null (fdn_adam_step_ema: tf.keras.optimizers.Adam(use_ema=, ema_momentum=)): the exponential moving average of the weights,
+// ema[i] = mom * ema[i] + (1.f - mom) * wn in fp32, formed from the wn in the register right behind the store of w[i]; ema_init != 0
+// (the first step with an average): ema[i] is not loaded, the average starts at wi, the weight before the step.  A frozen element
+// stores the wi it loaded: the average of a frozen parameter is its weight.  w, m, v and sumsq get the bits of the call without ema.
 #define ACCUM_FIRST 1
 #define ACCUM_ADD 2
 #define GRAD_SUMSQ 3
@@ -725,7 +729,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const 
                                                    const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float l2s_host,
                                                    const float* __restrict__ l2s_dev, float* __restrict__ sumsq, int accum,
                                                    const uint8_t* __restrict__ frozen, const float* __restrict__ g_scale_dev,
-                                                   float clip_value) {
+                                                   float clip_value, float* __restrict__ ema, float ema_momentum, int ema_init) {
     if (accum == GRAD_SUMSQ) {                                       // fdn_grad_sumsq_partials: w is only read
         const float l2s = l2s_dev ? l2s_host * l2s_dev[0] : l2s_host;
         float ss = 0.f;
@@ -766,6 +770,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const 
             v[i] = vi;
             wn = wi - lr_t * mi / (sqrtf(vi) + eps);
             w[i] = wn;
+            if (ema) ema[i] = ema_momentum * (ema_init ? wi : ema[i]) + (1.f - ema_momentum) * wn;
+        } else if (ema) {
+            ema[i] = wi;
         }
         if (k) ss += wn * wn;
     }
@@ -1048,18 +1055,19 @@ extern "C" int fdn_l2_sumsq_partials(const float* w, const uint8_t* is_kernel, i
 
 // adam_kernel's parameters by name (the kernel keeps its flat list): an entry point sets what its path reads, the rest stays "absent".
 struct AdamOperands {
-    float *w = nullptr, *m = nullptr, *v = nullptr, *sumsq = nullptr;
+    float *w = nullptr, *m = nullptr, *v = nullptr, *sumsq = nullptr, *ema = nullptr;
     const float *g = nullptr, *lr_t_dev = nullptr, *l2_scale_dev = nullptr, *g_scale_dev = nullptr;
     const uint8_t *is_kernel = nullptr, *frozen = nullptr;
     int64_t n = 0;
-    float lr_t = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f, l2_grad_scale = 0.f, clip_value = 0.f;
-    int accum = 0;
+    float lr_t = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f, l2_grad_scale = 0.f, clip_value = 0.f, ema_momentum = 0.f;
+    int accum = 0, ema_init = 0;
 };
 
 // The one place adam_kernel is launched from.
 static int launch_adam(const AdamOperands& a, int grid, hipStream_t stream, const char* what) {
     hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, stream, a.w, a.g, a.m, a.v, a.is_kernel, a.n, a.lr_t, a.lr_t_dev, a.b1, a.b2,
-                       a.eps, a.l2_grad_scale, a.l2_scale_dev, a.sumsq, a.accum, a.frozen, a.g_scale_dev, a.clip_value);
+                       a.eps, a.l2_grad_scale, a.l2_scale_dev, a.sumsq, a.accum, a.frozen, a.g_scale_dev, a.clip_value,
+                       a.ema, a.ema_momentum, a.ema_init);
     FDN_CHECK_LAUNCH(what);
     return FDN_OK;
 }
@@ -1170,4 +1178,27 @@ extern "C" int fdn_adam_step_clipped(float* w, const float* g, float* m, float* 
     a.l2_grad_scale = l2_grad_scale, a.l2_scale_dev = l2_scale_dev, a.sumsq = sumsq_partials;
     a.lr_t = lr_t, a.lr_t_dev = lr_t_dev, a.frozen = frozen, a.g_scale_dev = g_scale_dev, a.clip_value = clip_value;
     return launch_adam(a, adam_step_grid(n, sumsq_partials), (hipStream_t)stream, "adam_kernel (clipped)");
+}
+
+// Weight EMA (tf.keras.optimizers.Adam(use_ema=True, ema_momentum=)): the clipped step with the average as one more path of adam_kernel.
+// The widest form: frozen, lr_t_dev, g_scale_dev and l2_scale_dev may be NULL, clip_value may be 0.
+extern "C" int fdn_adam_step_ema(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, const uint8_t* frozen, int64_t n,
+                                 float lr_t, const float* lr_t_dev, float b1, float b2, float eps, float l2_grad_scale,
+                                 const float* l2_scale_dev, const float* g_scale_dev, float clip_value, float* ema, float ema_momentum,
+                                 int ema_init, float* sumsq_partials, void* stream) {
+    FDN_REQUIRE(w, "fdn_adam_step_ema: w is NULL");
+    FDN_REQUIRE(g, "fdn_adam_step_ema: g is NULL");
+    FDN_REQUIRE(m, "fdn_adam_step_ema: m is NULL");
+    FDN_REQUIRE(v, "fdn_adam_step_ema: v is NULL");
+    FDN_REQUIRE(is_kernel, "fdn_adam_step_ema: is_kernel is NULL");
+    FDN_REQUIRE(ema, "fdn_adam_step_ema: ema is NULL (fdn_adam_step_clipped is the step without an average)");
+    FDN_REQUIRE(n > 0, "fdn_adam_step_ema: n=%lld must be positive", (long long)n);
+    FDN_REQUIRE(ema_momentum >= 0.f && ema_momentum < 1.f, "fdn_adam_step_ema: ema_momentum=%g must lie in [0, 1)", (double)ema_momentum);  // (false for NaN)
+    FDN_REQUIRE(clip_value >= 0.f, "fdn_adam_step_ema: clip_value=%g must be >= 0 (0 = off)", (double)clip_value);          // (false for NaN)
+    AdamOperands a;
+    a.w = w, a.g = g, a.m = m, a.v = v, a.is_kernel = is_kernel, a.n = n, a.b1 = b1, a.b2 = b2, a.eps = eps;
+    a.l2_grad_scale = l2_grad_scale, a.l2_scale_dev = l2_scale_dev, a.sumsq = sumsq_partials;
+    a.lr_t = lr_t, a.lr_t_dev = lr_t_dev, a.frozen = frozen, a.g_scale_dev = g_scale_dev, a.clip_value = clip_value;
+    a.ema = ema, a.ema_momentum = ema_momentum, a.ema_init = ema_init != 0;
+    return launch_adam(a, adam_step_grid(n, sumsq_partials), (hipStream_t)stream, "adam_kernel (ema)");
 }

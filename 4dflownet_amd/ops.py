@@ -506,7 +506,7 @@ ADAM_PARTIALS = 2048                  # FDN_ADAM_PARTIALS
 
 
 def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_dev=None, sumsq_partials=None, lr_t_dev=None, frozen=None,
-              g_scale_dev=None, clip_value=0.0):
+              g_scale_dev=None, clip_value=0.0, ema=None, ema_momentum=0.0, ema_init=False):
     """sumsq_partials (ADAM_PARTIALS floats): also receive per-block sums of the updated kernel parameters' squares.
     lr_t_dev (one fp32 device element): the step size is read from it on the device and `lr_t` is ignored (fdn_adam_step_dev) -- the
     form a captured launch needs, since a by-value lr_t would be frozen into the graph.
@@ -514,7 +514,11 @@ def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_
     (fdn_adam_step_masked); the others are updated exactly as without it.  None: the two entry points above, as always.
     Gradient clipping (fdn_adam_step_clipped; at most one of the two): g_scale_dev (one fp32 device element, the second float clip_scale
     leaves behind) multiplies the gradient, L2 term included, on the device; clip_value > 0 clamps every element of it to
-    [-clip_value, clip_value].  Neither: the entry points above, as always."""
+    [-clip_value, clip_value].  Neither: the entry points above, as always.
+    Weight EMA (fdn_adam_step_ema, the widest entry point): ema (one fp32 per parameter on the GPU) becomes
+    ema_momentum * ema + (1 - ema_momentum) * w_new in fp32, formed in the same launch; ema_init: the old contents of ema are not read and
+    the weights before the step take their place; frozen elements store their weight.  w, m, v and sumsq_partials get the bits of the
+    call without ema.  None: the four routes above, as always."""
     clip_value = float(clip_value)
     clipped = g_scale_dev is not None or clip_value != 0.0
     if clipped:
@@ -530,6 +534,12 @@ def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_
         raise FdnError("adam_step: lr_t_dev must hold one float32 on the GPU")
     if frozen is not None and frozen.numel() != w.numel():
         raise FdnError("adam_step: frozen holds %d bytes for %d parameters" % (frozen.numel(), w.numel()))
+    if ema is not None:
+        if not ema.is_cuda or ema.dtype != torch.float32 or ema.numel() != w.numel():
+            raise FdnError("adam_step: ema must hold %d float32 on the GPU (one per parameter)" % w.numel())
+        mom32 = ctypes.c_float(float(ema_momentum)).value              # what the device receives
+        if not 0.0 <= mom32 < 1.0:
+            raise FdnError("adam_step: ema_momentum must lie in [0, 1) as float32, got %r" % (ema_momentum,))
     lib = _lib.load()
     # every operand once, in the order the widest entry point takes them; the four argument lists below differ in what they leave out
     bufs = [_p(w), _p(g), _p(m), _p(v), _pu8(is_kernel, "is_kernel")]
@@ -538,7 +548,10 @@ def adam_step(w, g, m, v, is_kernel, lr_t, b1, b2, eps, l2_grad_scale, l2_scale_
     hyper = [float(b1), float(b2), float(eps), float(l2_grad_scale), _p(l2_scale_dev, allow_none=True)]
     clip = [_p(g_scale_dev, "g_scale_dev", allow_none=True), clip_value]
     tail = [_p(sumsq_partials, allow_none=True), _stream()]
-    if clipped:
+    if ema is not None:
+        entry = "fdn_adam_step_ema"
+        args = bufs + [frozen_p, n] + lr + hyper + clip + [_p(ema, "ema"), mom32, 1 if ema_init else 0] + tail
+    elif clipped:
         entry, args = "fdn_adam_step_clipped", bufs + [frozen_p, n] + lr + hyper + clip + tail
     elif frozen is not None:
         entry, args = "fdn_adam_step_masked", bufs + [frozen_p, n] + lr + hyper + tail

@@ -12,7 +12,10 @@ Differences that are deliberate and documented in DESIGN.md:
   * fine-tuning: `trainable=` / model.set_trainable / `layer.trainable = False` freeze layers as in Keras (:223-225 differentiate and
     update model.trainable_variables only); backward skips what a frozen layer does not need and Adam leaves its parameters and slots;
   * gradient clipping: `global_clipnorm=` / `clipvalue=` are the arguments of the same name of tf.keras.optimizers.Adam (:73), applied on
-    the device to the gradient Adam is about to consume, the L2 term included."""
+    the device to the gradient Adam is about to consume, the L2 term included;
+  * weight EMA: `use_ema=` / `ema_momentum=` / `ema_overwrite_frequency=` are the arguments of the same name of
+    tf.keras.optimizers.Adam (:73); the average is formed inside the Adam launch, `ema_weights()` evaluates under it."""
+import contextlib
 import ctypes
 import datetime
 import os
@@ -49,6 +52,28 @@ def _clip_arguments(global_clipnorm, clipvalue):
     if out[0] is not None and out[1] is not None:
         raise ValueError("global_clipnorm and clipvalue are both set (%r, %r): at most one kind of gradient clipping" % (global_clipnorm, clipvalue))
     return tuple(out)
+
+
+def _ema_arguments(use_ema, ema_momentum, ema_overwrite_frequency, ema_validation=False):
+    """The weight-EMA arguments as (bool, float, int or None, bool): use_ema and ema_validation are bools, ema_momentum is a finite real
+    in [0, 1) as the float32 the device receives (0.999999999 rounds to 1.0f and is refused), ema_overwrite_frequency is None or an
+    integer >= 1 (tf.keras.optimizers.Adam(use_ema=, ema_momentum=, ema_overwrite_frequency=)); ema_validation needs use_ema."""
+    for name, b in (("use_ema", use_ema), ("ema_validation", ema_validation)):
+        if not isinstance(b, (bool, np.bool_)):
+            raise ValueError("%s must be True or False, got %r" % (name, b))
+    mom = ema_momentum
+    try:
+        mom32 = ctypes.c_float(float(mom)).value
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("ema_momentum must be a real number in [0, 1) as float32, got %r" % (mom,)) from None
+    if isinstance(mom, (bool, np.bool_, str, bytes)) or not 0.0 <= mom32 < 1.0:                      # (false for NaN)
+        raise ValueError("ema_momentum must be a real number in [0, 1) as float32, got %r" % (mom,))
+    k = ema_overwrite_frequency
+    if k is not None and (isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1):
+        raise ValueError("ema_overwrite_frequency must be None or an integer >= 1, got %r" % (k,))
+    if ema_validation and not use_ema:
+        raise ValueError("ema_validation=True validates under the averaged weights and needs use_ema=True")
+    return bool(use_ema), mom32, None if k is None else int(k), bool(ema_validation)
 
 
 class Mean:
@@ -102,7 +127,7 @@ class TrainerController:
     def __init__(self, patch_size, res_increase, initial_learning_rate=1e-4, quicksave_enable=True,
                  network_name='4DFlowNet', low_resblock=8, hi_resblock=4, device=None, seed=0, dtype='float32',
                  bucketed_allreduce=None, conv_algo=None, div_weight=0, accum_steps=1, trainable=None, global_clipnorm=None,
-                 clipvalue=None):
+                 clipvalue=None, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, ema_validation=False):
         """Reference arguments: TrainerController.py:18.  Extra (keyword-only in spirit): device, seed (Glorot draw), dtype
         (activation storage, 'float32' | 'bfloat16'), bucketed_allreduce (data parallel only: True = one asynchronous SUM
         all-reduce per gradient bucket started inside backward -- the default --, False = ONE all-reduce of the whole buffer
@@ -124,7 +149,25 @@ class TrainerController:
         scales it by c / max(N, c), N its L2 norm over all trainable variables (tf.clip_by_global_norm); clipvalue = c clamps every
         element to [-c, c].  With global_clipnorm set, last_grad_norm is a view of N on the device and grad_norm_metric its running
         mean, written as '<name>/grad_norm'; a very large finite value logs the norm without ever clipping.  Keras' per-variable
-        `clipnorm` is not offered.  The attributes of the same names are read on every optimiser step)."""
+        `clipnorm` is not offered.  The attributes of the same names are read on every optimiser step),
+        use_ema / ema_momentum / ema_overwrite_frequency (weight EMA, the arguments of tf.keras.optimizers.Adam at
+        TrainerController.py:73 [TF]: with use_ema every optimiser step also moves self.ema, a flat fp32 buffer like optimizer.m,
+        a_t = ema_momentum * a_{t-1} + (1 - ema_momentum) * w_t in fp32 inside the Adam launch, a_0 = the weights before the first such
+        step; the average of a frozen parameter is its weight.  The buffer is allocated by the first optimiser step that runs with
+        use_ema; the average restarts from the weights whenever they were changed outside the optimiser (load_weights, set_weights).
+        ema_overwrite_frequency = k: after every optimiser step with iterations % k == 0 the weights are overwritten with the average.
+        finalize_ema() does so on demand, `with ema_weights():` evaluates under the average and restores the weights.  The
+        attributes of the same names are read on every optimiser step), ema_validation (True: train_network runs the validation
+        loop, the best-model decision and quicksave under the averaged weights)."""
+        self.use_ema = use_ema
+        self.ema_momentum = ema_momentum
+        self.ema_overwrite_frequency = ema_overwrite_frequency
+        self.ema_validation = ema_validation
+        self._checked_ema()
+        self.ema = None                # the average, (n_params,) like optimizer.m: allocated by the first optimiser step that runs with use_ema
+        self._ema_version = -1         # model.weights_version the average belongs to (another one: the next step starts it afresh)
+        self._ema_spare = None         # ema_weights(): where the weights wait
+        self._ema_active = False       # inside ema_weights()
         self.global_clipnorm = global_clipnorm
         self.clipvalue = clipvalue
         self._checked_clip()
@@ -209,6 +252,10 @@ class TrainerController:
         """(global_clipnorm, clipvalue) as floats or None, validated: see _clip_arguments."""
         return _clip_arguments(self.global_clipnorm, self.clipvalue)
 
+    def _checked_ema(self):
+        """(use_ema, ema_momentum as float32, ema_overwrite_frequency, ema_validation), validated: see _ema_arguments."""
+        return _ema_arguments(self.use_ema, self.ema_momentum, self.ema_overwrite_frequency, self.ema_validation)
+
     def calculate_and_update_metrics(self, hires, predictions, mask, metric_set, want_grad):
         """TrainerController.py:84-127 (loss_function, the divergence term live when div_weight != 0), :243-256 (metrics)."""
         div_weight = self._checked_div_weight()
@@ -254,6 +301,9 @@ class TrainerController:
         if not self.model.any_trainable:                            # Keras: "No gradients provided for any variable"
             raise ValueError("train_step: no layer of the model is trainable (layer.trainable / set_trainable), there is nothing to update")
         self._checked_clip()                                        # (a bad clipping argument stops the step before anything is launched)
+        self._checked_ema()
+        if self._ema_active:
+            raise RuntimeError("train_step inside `with ema_weights():` -- the model holds the averaged weights, leave the context first")
         if self._accum_count == 0:                                  # a group starts: this is where accum_steps is read
             self._accum_k = self._checked_accum_steps()
         inputs, hires, venc, mask = self._unpack(data_pairs)
@@ -325,8 +375,8 @@ class TrainerController:
             m._join_side()                      # whatever the transport (K = 1 puts only collectives there, and those were just waited for)
         self.optimizer.iterations += 1
         n = m.n_params
-        self._adam(buf[:n], buf[n:n + 1])
-        self._l2_version = m.weights_version
+        overwritten = self._adam(buf[:n], buf[n:n + 1])
+        self._l2_version = -1 if overwritten else m.weights_version      # (the partials Adam left are those of the weights it wrote)
         self._accum_count = 0
         self._accum_has = False
 
@@ -337,8 +387,13 @@ class TrainerController:
         trainable kernels only, the sum of squares it leaves still covers all kernels) and a re-pack of the trainable 64->64 layers only.
         global_clipnorm: two launches ahead of Adam's -- per-block sums of squares of g + B 2 lambda w over the trainable elements, then
         norm and scale by one block -- and Adam reads the scale from the device: no host synchronisation, and every rank of a
-        data-parallel run computes the same bits from the same all-reduced buffer.  clipvalue: Adam's launch alone."""
+        data-parallel run computes the same bits from the same all-reduced buffer.  clipvalue: Adam's launch alone.
+        use_ema: the same single launch through the entry point that also moves self.ema (w, m, v and the partials keep their bits);
+        ema_init whenever the average does not belong to the weights the step starts from.  With ema_overwrite_frequency = k and
+        iterations % k == 0 the weights then become a bit copy of the average, ahead of the step's one re-pack; returns True in that
+        case: the partials the launch left are no longer those of the weights."""
         m, opt = self.model, self.optimizer
+        use_ema, ema_momentum, ema_every, _ = self._checked_ema()
         frozen = m.frozen_map
         clipnorm, clipvalue = self._checked_clip()
         kw = {} if frozen is None else {"frozen": frozen}
@@ -353,9 +408,66 @@ class TrainerController:
             kw["g_scale_dev"] = self._clip_out[1:2]
         elif clipvalue is not None:
             kw["clip_value"] = clipvalue
+        if use_ema:
+            if self.ema is None:
+                self.ema = torch.empty_like(m.flat_w)
+            kw.update(ema=self.ema, ema_momentum=ema_momentum, ema_init=self._ema_version != m.weights_version)
         ops.adam_step(m.flat_w, g, opt.m, opt.v, m.is_kernel, opt.lr_t(), ADAM_B1, ADAM_B2, ADAM_EPS,
                       2.0 * L2_LAMBDA, batch_slot, sumsq_partials=self._l2_partials, **kw)
+        overwrite = use_ema and ema_every is not None and opt.iterations % ema_every == 0
+        if overwrite:
+            ops.grad_accumulate(m.flat_w, self.ema, first=True)     # (a frozen parameter's average is its weight: only trainable layers move)
         m.weights_changed(trainable_only=frozen is not None)
+        if use_ema:
+            self._ema_version = m.weights_version
+        return overwrite
+
+    # ------------------------------------------------------------------ weight EMA
+    @property
+    def ema_current(self):
+        """An average exists and belongs to the weights the model holds (not before the first optimiser step with use_ema, and not after
+        the weights were changed outside the optimiser)."""
+        return self.ema is not None and self._ema_version == self.model.weights_version
+
+    def _require_ema(self, who):
+        if self._ema_active:
+            raise RuntimeError("%s inside `with ema_weights():` -- the model already holds the averaged weights" % who)
+        if not self.ema_current:
+            raise RuntimeError("%s: there is no weight average yet (use_ema=True and one optimiser step create it; loading weights "
+                               "restarts it)" % who)
+
+    def finalize_ema(self):
+        """Overwrite the weights with their average (Keras: optimizer.finalize_variable_values): a bit copy and one re-pack.  The
+        average stays and now equals the weights.  Not called by train_network."""
+        self._require_ema("finalize_ema")
+        m = self.model
+        ops.grad_accumulate(m.flat_w, self.ema, first=True)
+        m.weights_changed()                                         # (the L2 partials Adam left are stale now: another weights_version)
+        self._ema_version = m.weights_version
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside, the model holds the averaged weights (forward, predict, save, test_step); on exit it holds the exact bits it held
+        before.  Two bit copies and a re-pack each way, no torch arithmetic.  train_step, apply_accumulated and a nested entry raise
+        inside; entering raises when there is no average yet."""
+        self._require_ema("ema_weights")
+        m = self.model
+        if self._ema_spare is None:
+            self._ema_spare = torch.empty_like(m.flat_w)
+        l2_current = self._l2_version == m.weights_version
+        ops.grad_accumulate(self._ema_spare, m.flat_w, first=True)
+        ops.grad_accumulate(m.flat_w, self.ema, first=True)
+        m.weights_changed()
+        self._ema_active = True
+        try:
+            yield self
+        finally:
+            self._ema_active = False
+            ops.grad_accumulate(m.flat_w, self._ema_spare, first=True)
+            m.weights_changed()
+            self._ema_version = m.weights_version                   # the same weights as on entry: the average and the L2 partials
+            if l2_current:                                          # of the last Adam step still belong to them
+                self._l2_version = m.weights_version
 
     def _wait_allreduce(self, pending, dp):
         """The current stream waits for the collectives in `pending` (no host synchronisation under nccl)."""
@@ -377,6 +489,8 @@ class TrainerController:
         epoch boundary."""
         if self._accum_count == 0:
             return False
+        if self._ema_active:
+            raise RuntimeError("apply_accumulated inside `with ema_weights():` -- the model holds the averaged weights, leave the context first")
         self._close_step()
         return True
 
@@ -421,6 +535,9 @@ class TrainerController:
         if clipnorm is not None or clipvalue is not None:
             self._log('Gradient clipping: %s\n' % ('global_clipnorm=%s' % self.global_clipnorm if clipnorm is not None else
                                                    'clipvalue=%s' % self.clipvalue))
+        use_ema, ema_momentum, ema_every, ema_validation = self._checked_ema()
+        if use_ema:
+            self._log('Weight EMA: momentum=%s, overwrite_frequency=%s, validation=%s\n' % (self.ema_momentum, ema_every, ema_validation))
         stat_names = ','.join(self.loss_metrics.keys())
         self._log('epoch, %s, learning rate, elapsed (sec), best_model, benchmark_err, benchmark_rel_err, '
                   'benchmark_mse, benchmark_divloss\n' % stat_names)
@@ -526,12 +643,14 @@ class TrainerController:
                         epoch + 1, i + 1, total_batch_train, self.loss_metrics['train_loss'].result(),
                         self.loss_metrics['train_accuracy'].result(), time.time() - start_loop), end='')
             self.apply_accumulated()                       # accum_steps > 1: a ragged last group is applied before validation
-            for i, data_pairs in enumerate(self.device_batches(valset)):
-                self.test_step(data_pairs)
-                if verbose and is0:
-                    print("\rEpoch %d Validation batch %d/%d | loss: %.5f (%.1f %%) - %.1f secs" % (
-                        epoch + 1, i + 1, total_batch_val, self.loss_metrics['val_loss'].result(),
-                        self.loss_metrics['val_accuracy'].result(), time.time() - start_loop), end='')
+            # ema_validation: the validation loop, and with it the best-model decision, sees the averaged weights
+            with self._validation_weights():
+                for i, data_pairs in enumerate(self.device_batches(valset)):
+                    self.test_step(data_pairs)
+                    if verbose and is0:
+                        print("\rEpoch %d Validation batch %d/%d | loss: %.5f (%.1f %%) - %.1f secs" % (
+                            epoch + 1, i + 1, total_batch_val, self.loss_metrics['val_loss'].result(),
+                            self.loss_metrics['val_accuracy'].result(), time.time() - start_loop), end='')
             # data parallel: every rank saw a shard of each global batch -> combine (total, count) over ranks, so
             # loss.csv and the best-model decision do not depend on the world size
             res = dict((k, v.result_global()) for k, v in self.loss_metrics.items())
@@ -550,7 +669,8 @@ class TrainerController:
                 message += ' **'
                 log_line += ',**'
                 if self.QUICKSAVE_ENABLED and testset is not None and is0:
-                    ql, qa, qm, qd = self.quicksave(testset, epoch + 1)
+                    with self._validation_weights():
+                        ql, qa, qm, qd = self.quicksave(testset, epoch + 1)
                     message += ' Benchmark loss: %.5f (%.1f %%)' % (np.mean(ql), np.mean(qa))
                     log_line += ', %.7f, %.2f%%, %.7f, %.7f' % (np.mean(ql), np.mean(qa), np.mean(qm), np.mean(qd))
             if is0:
@@ -564,6 +684,12 @@ class TrainerController:
             msg += "\nFinished at %s\n==================== END TRAINING =================" % time.ctime()
             self._log(msg)
             print(msg)
+
+    def _validation_weights(self):
+        """ema_weights() when ema_validation is set and an average exists (none before the first optimiser step), else nothing."""
+        if self._checked_ema()[3] and self.ema_current:
+            return self.ema_weights()
+        return contextlib.nullcontext()
 
     # ------------------------------------------------------------------ checkpoints
     def save_latest_model(self, epoch):
@@ -583,8 +709,14 @@ class TrainerController:
         tests/golden/tf_golden.npz exists.  Several layers share a shape, so a wrong order cannot be detected from shapes alone.
 
         Gradient accumulation: a partial group is never checkpointed -- the accumulator is not part of the files.  train_network applies
-        the pending group before it gets here; a caller of its own does the same with apply_accumulated()."""
+        the pending group before it gets here; a caller of its own does the same with apply_accumulated().
+
+        Weight EMA: when an average exists, '<dir>/<name>-best-ema.h5' holds it in the same Keras layout (the predictor loads it like
+        any weights file); '-best.h5' and optimizer.pkl are what they are without it."""
         self.model.save('%s-best.h5' % self.model_path)
+        if self.ema_current:
+            with self.ema_weights():
+                self.model.save('%s-best-ema.h5' % self.model_path)
         # slots of the TRAINABLE variables only: Keras creates slots for the variables it is given (frozen layers have none)
         where = self._trainable_slices()
         m_flat, v_flat = self.optimizer.m.cpu().numpy(), self.optimizer.v.cpu().numpy()
@@ -614,7 +746,11 @@ class TrainerController:
 
     def restore_model(self, old_model_dir, old_model_file):
         """TrainerController.py:365-394.  optimizer.pkl slots are in Keras trainable_variables order (see save_best_model).
-        A checkpoint never holds a partial accumulation group: a group that is open here is dropped, the next train_step starts one."""
+        A checkpoint never holds a partial accumulation group: a group that is open here is dropped, the next train_step starts one.
+        Weight EMA: with use_ema set and '<stem>-ema.h5' beside old_model_file (save_best_model writes it), that file becomes the
+        average; otherwise the average restarts from the loaded weights at the next optimiser step."""
+        if self._ema_active:
+            raise RuntimeError("restore_model inside `with ema_weights():` -- leave the context first")
         with open("%s/optimizer.pkl" % old_model_dir, 'rb') as f:
             opt_weights = pickle.load(f)
         tv = self.model.trainable_variables
@@ -657,7 +793,16 @@ class TrainerController:
             for (o, k, _), a in zip(self._trainable_slices(), arrs):
                 host[o:o + k] = np.asarray(a, np.float32).reshape(-1)
             dst.copy_(torch.from_numpy(host))
+        ema_file = "%s/%s-ema.h5" % (old_model_dir, os.path.splitext(old_model_file)[0])
+        have_ema = self._checked_ema()[0] and os.path.exists(ema_file)
+        if have_ema:                                          # through the model's own reader: the file has the layout of a weights file
+            self.model.load_weights(ema_file)
+            if self.ema is None:
+                self.ema = torch.empty_like(self.model.flat_w)
+            ops.grad_accumulate(self.ema, self.model.flat_w, first=True)
         self.model.load_weights("%s/%s" % (old_model_dir, old_model_file))
+        if have_ema:
+            self._ema_version = self.model.weights_version
         self._accum_count = 0
         self._accum_has = False
 

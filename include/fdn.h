@@ -407,6 +407,24 @@ int fdn_adam_step_clipped(float* w, const float* g, float* m, float* v, const ui
                           int64_t n, float lr_t, const float* lr_t_dev /* NULL ok */, float b1, float b2, float eps, float l2_grad_scale,
                           const float* l2_scale_dev /* NULL ok */, const float* g_scale_dev /* NULL ok */, float clip_value,
                           float* sumsq_partials /* NULL ok */, void* stream);
+/* Weight EMA: what tf.keras.optimizers.Adam(use_ema=True, ema_momentum=mom) keeps beside the weights ([TF]-unpinned: TensorFlow is
+ * absent, the recurrence below is the specification).  fdn_adam_step_clipped's operands -- the widest form: frozen, lr_t_dev,
+ * l2_scale_dev and g_scale_dev may be NULL, clip_value may be 0 -- and the average ema (n floats), a path of the same kernel.  With
+ * wi the weight the element held before the step and wn the weight the step stores, in fp32:
+ *     ema_init == 0:    ema[i] = ema_momentum * ema[i] + (1.f - ema_momentum) * wn   (a_t = mom * a_{t-1} + (1 - mom) * w_t);
+ *     ema_init != 0:    ema[i] = ema_momentum * wi + (1.f - ema_momentum) * wn       (the first step with an average: a_0 = w_0, the
+ *                       weights before the step; ema[i] is not read, so the buffer may be uninitialised);
+ *     frozen[i] != 0:   ema[i] = wi, a store of the value already loaded: the average of a currently frozen parameter is its weight,
+ *                       whatever was trainable earlier.  g[i], m[i] and v[i] stay unread.
+ * The average is formed from wn in the register, right behind the store of w[i]; nothing else depends on it: with ema the call leaves
+ * bit-identical w, m, v, partials to the same call of fdn_adam_step_clipped without it.  Once per optimiser step; no collective
+ * (data-parallel ranks form identical averages from identical weights).
+ * Refused before the device is touched, the message naming the argument: NULL w, g, m, v, is_kernel or ema, n <= 0, ema_momentum outside
+ * [0, 1) or NaN, clip_value negative or NaN. */
+int fdn_adam_step_ema(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, const uint8_t* frozen /* NULL ok */,
+                      int64_t n, float lr_t, const float* lr_t_dev /* NULL ok */, float b1, float b2, float eps, float l2_grad_scale,
+                      const float* l2_scale_dev /* NULL ok */, const float* g_scale_dev /* NULL ok */, float clip_value,
+                      float* ema, float ema_momentum, int ema_init, float* sumsq_partials /* NULL ok */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * bf16 activation path (BASELINE.json configs[3]: patch 32, res x4, bf16).  The reference has no bf16
