@@ -50,6 +50,8 @@ SIGNATURES = {
     "fdn_stitch_patches": (c_i, [c_fp, c_fp] + [c_i] * 9 + [c_i64, c_i, c_fp]),
     "fdn_stitch_patches_finish": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 9 + [c_i64, c_i, c_fp]),
     "fdn_pack_patch_cores": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp]),
+    "fdn_input_features_volume_oriented": (c_i, [c_fp] + [c_i] * 8 + [c_i64, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
+    "fdn_unrotate_accumulate": (c_i, [c_fp, c_fp] + [c_i] * 6 + [c_fp]),
     "fdn_l2_sumsq": (c_i, [c_fp, c_fp, c_i64, c_fp, c_fp]),
     "fdn_adam_step": (c_i, [c_fp] * 5 + [c_i64] + [c_f] * 5 + [c_fp, c_fp, c_fp]),
     "fdn_adam_step_dev": (c_i, [c_fp] * 5 + [c_i64, c_fp] + [c_f] * 4 + [c_fp, c_fp, c_fp]),
@@ -75,6 +77,7 @@ SIGNATURES = {
     "fdn_fold_halo_border_bf16": (c_i, [c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_f, c_fp, c_i, c_i, c_i, c_i, c_fp]),
     "fdn_input_features_bf16": (c_i, [c_fp] * 8 + [c_i64, c_fp]),
     "fdn_input_features_volume_bf16": (c_i, [c_fp] + [c_i] * 8 + [c_i64, c_i, c_fp, c_fp, c_fp]),
+    "fdn_input_features_volume_oriented_bf16": (c_i, [c_fp] + [c_i] * 8 + [c_i64, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
     "fdn_conv3d_fwd_bf16": (c_i, [c_fp] * 7 + [c_i] * 10 + [c_f, c_fp]),
     "fdn_conv3d_wgrad_bf16_workspace_bytes": (c_sz, [c_i] * 7),
     "fdn_conv3d_wgrad_bf16": (c_i, [c_fp] * 6 + [c_sz] + [c_i] * 9 + [c_fp]),

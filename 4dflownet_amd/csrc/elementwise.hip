@@ -18,9 +18,13 @@ __device__ __forceinline__ float norm3(float a, float b, float c) {
 // Sliding-window geometry of fdn_input_features_volume (src/Network/PatchGenerator.py:13-40,53-86): with P > 0 the six inputs of output
 // voxel i are gathered from resident frames (F,6,X,Y,Z) at u -- patch g0 + i / P^3 of the window at stride P - 4, shifted by the 2-voxel
 // side pad, zero outside the volume -- instead of being read at u[i] .. mw[i].  P == 0: no geometry (fdn_input_features).
+// orient != 0 (fdn_input_features_volume_oriented, an fdn_orient_word): the features of the patch as PatchHandler3D.apply_rotation
+// (src/Network/PatchHandler3D.py:97-108,166-274) would turn it -- voxel (a,b,c) reads the window voxel np.rot90 puts there, the zero
+// fill comes first, then the components are permuted and signed by multiplication (a padded zero under a negative sign is -0.0, as on
+// the host), and norm3 takes the permuted components in their new order.  0: the plain window.
 struct InputGeom {
     int32_t P, X, Y, Z;
-    int32_t nx, ny, nz, pad_;
+    int32_t nx, ny, nz, orient;
     int64_t g0;
 };
 
@@ -39,19 +43,30 @@ __global__ void input_features_kernel(const float* __restrict__ u, const float* 
         } else {
             const int64_t n = i / per;                       // patch of this launch
             int r = (int)(i - n * per);                      // voxel of the patch, z fastest
-            const int pa = r / (P * P); r -= pa * P * P;
-            const int pb = r / P, pcz = r - pb * P;
+            int pa = r / (P * P); r -= pa * P * P;
+            int pb = r / P, pcz = r - pb * P;
             int64_t g = geo.g0 + n;                          // global patch: frame, then (i, j, k) with k fastest
             const int pk = (int)(g % geo.nz); g /= geo.nz;
             const int pj = (int)(g % geo.ny); g /= geo.ny;
             const int pi = (int)(g % geo.nx);
             const int64_t f = g / geo.nx;
+            if (geo.orient) fdn_rot_source(geo.orient, P, pa, pb, pcz);
             const int x = pi * E + pa - 2, y = pj * E + pb - 2, z = pk * E + pcz - 2;
             a = b = c = ma = mb = mc = 0.f;
             if (x >= 0 && x < geo.X && y >= 0 && y < geo.Y && z >= 0 && z < geo.Z) {
                 const float* s = u + f * 6 * plane + ((int64_t)x * geo.Y + y) * geo.Z + z;
                 a = s[0]; b = s[plane]; c = s[2 * plane];
                 ma = s[3 * plane]; mb = s[4 * plane]; mc = s[5 * plane];
+            }
+            if (geo.orient) {
+                const int s0 = fdn_orient_src(geo.orient, 0), s1 = fdn_orient_src(geo.orient, 1), s2 = fdn_orient_src(geo.orient, 2);
+                const float a0 = a, b0 = b, c0 = c, ma0 = ma, mb0 = mb, mc0 = mc;
+                a = (s0 == 0 ? a0 : s0 == 1 ? b0 : c0) * fdn_orient_sign(geo.orient, 0);
+                b = (s1 == 0 ? a0 : s1 == 1 ? b0 : c0) * fdn_orient_sign(geo.orient, 1);
+                c = (s2 == 0 ? a0 : s2 == 1 ? b0 : c0) * fdn_orient_sign(geo.orient, 2);
+                ma = s0 == 0 ? ma0 : s0 == 1 ? mb0 : mc0;
+                mb = s1 == 0 ? ma0 : s1 == 1 ? mb0 : mc0;
+                mc = s2 == 0 ? ma0 : s2 == 1 ? mb0 : mc0;
             }
         }
         const float speed = norm3(a, b, c);
@@ -841,7 +856,7 @@ static int input_features_t(const float* u, const float* v, const float* w, cons
 }
 template <typename T>
 static int input_features_volume_t(const char* who, const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz,
-                                   int64_t g0, int count, T* phase, T* pc, void* stream) {
+                                   int64_t g0, int count, T* phase, T* pc, void* stream, int plane = 0, int k = 0) {
     FDN_REQUIRE(frames && phase && pc, "%s: NULL argument", who);
     FDN_REQUIRE(F > 0 && X > 0 && Y > 0 && Z > 0, "%s: bad frames (F=%d, X=%d, Y=%d, Z=%d)", who, F, X, Y, Z);
     FDN_REQUIRE(P > 4 && P <= 1024, "%s: patch size P=%d must be in 5..1024 (the window advances by P - 4)", who, P);
@@ -850,8 +865,11 @@ static int input_features_volume_t(const char* who, const float* frames, int F, 
     FDN_REQUIRE(g0 >= 0, "%s: g0=%lld", who, (long long)g0);
     FDN_REQUIRE(g0 + count <= (int64_t)F * nx * ny * nz, "%s: patches [%lld, %lld) exceed F*nx*ny*nz = %lld", who, (long long)g0,
                 (long long)(g0 + count), (long long)((int64_t)F * nx * ny * nz));
+    const int word = fdn_orient_word(plane, k, 0);
+    FDN_REQUIRE(word >= 0, "%s: orientation (plane=%d, k=%d) is neither (0,0) nor plane in 1..3 with k in 1..3", who, plane, k);
     const int64_t nvox = (int64_t)count * P * P * P;
     InputGeom geo{};
+    geo.orient = plane ? word : 0;
     geo.P = P; geo.X = X; geo.Y = Y; geo.Z = Z; geo.nx = nx; geo.ny = ny; geo.nz = nz; geo.g0 = g0;
     hipLaunchKernelGGL(input_features_kernel<T>, dim3(grid_for(nvox)), dim3(256), 0, (hipStream_t)stream, frames,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
@@ -875,6 +893,18 @@ extern "C" int fdn_input_features_volume_bf16(const float* frames, int F, int X,
                                               int64_t g0, int count, uint16_t* phase, uint16_t* pc, void* stream) {
     return input_features_volume_t<uint16_t>("fdn_input_features_volume_bf16", frames, F, X, Y, Z, P, nx, ny, nz, g0, count, phase, pc,
                                              stream);
+}
+
+extern "C" int fdn_input_features_volume_oriented(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz,
+                                                  int64_t g0, int count, int plane, int k, float* phase, float* pc, void* stream) {
+    return input_features_volume_t<float>("fdn_input_features_volume_oriented", frames, F, X, Y, Z, P, nx, ny, nz, g0, count, phase, pc,
+                                          stream, plane, k);
+}
+extern "C" int fdn_input_features_volume_oriented_bf16(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz,
+                                                       int64_t g0, int count, int plane, int k, uint16_t* phase, uint16_t* pc,
+                                                       void* stream) {
+    return input_features_volume_t<uint16_t>("fdn_input_features_volume_oriented_bf16", frames, F, X, Y, Z, P, nx, ny, nz, g0, count, phase,
+                                             pc, stream, plane, k);
 }
 
 extern "C" int fdn_fold_halo(const float* dxpad0, const float* dxpad1, const float* dxpad2, int nsrc, const float* skip,

@@ -195,6 +195,40 @@ __device__ __forceinline__ float fdn_act_grad(float y, int act, float alpha) {
     return 1.f;
 }
 
+// Orientation word of the self-ensemble paths (fdn_input_features_volume_oriented, fdn_unrotate_accumulate): the patch rotations the
+// loader trains with (PatchHandler3D.apply_rotation, src/Network/PatchHandler3D.py:97-108,166-274; data._ROT), packed for a kernel's
+// by-value arguments.  bits 0-1 plane (0 none, 1:(0,1), 2:(0,2), 3:(1,2), np.rot90 axes), bits 2-3 the rot90 count of the index walk,
+// bits 4-5 / 6-7 / 8-9 the source component of output component 0 / 1 / 2, bits 10-12 set where that component changes sign.
+// inverse = 0: the forward transform, out[i] = sign[i] * rot90(v[perm[i]], k);  inverse = 1: what takes a prediction in the rotated frame
+// back, out[perm[i]] = sign[i] * rot90(p[i], 4 - k).  (0,0) is the identity (components 0,1,2, no sign); -1: not an orientation of the set.
+inline int fdn_orient_word(int plane, int k, int inverse) {
+    static const signed char perm[9][3] = {{0, 2, 1}, {0, 1, 2}, {0, 2, 1}, {2, 1, 0}, {0, 1, 2}, {2, 1, 0}, {1, 0, 2}, {0, 1, 2}, {1, 0, 2}};
+    static const signed char sign[9][3] = {{1, 1, -1}, {1, -1, -1}, {1, -1, 1}, {-1, 1, 1}, {-1, 1, -1}, {1, 1, -1}, {-1, 1, 1}, {-1, -1, 1}, {1, -1, 1}};
+    if (plane == 0 && k == 0) return (1 << 6) | (2 << 8);
+    if (plane < 1 || plane > 3 || k < 1 || k > 3) return -1;
+    const int row = (plane - 1) * 3 + (k - 1);
+    int w = plane | ((inverse ? 4 - k : k) << 2);
+    for (int i = 0; i < 3; ++i) {
+        const int dst = inverse ? perm[row][i] : i, src = inverse ? i : perm[row][i];
+        w |= src << (4 + 2 * dst);
+        if (sign[row][i] < 0) w |= 1 << (10 + dst);
+    }
+    return w;
+}
+// out = np.rot90(m, k, axes=(a,b)) of edge S:  k=1: out[ia,ib] = m[ib, S-1-ia];  k=2: m[S-1-ia, S-1-ib];  k=3: m[S-1-ib, ia].
+// (i0,i1,i2): an index of `out` on entry, the index of `m` it reads on return.  Wave-uniform selects, no indexed array.
+__device__ __forceinline__ void fdn_rot_source(int word, int S, int& i0, int& i1, int& i2) {
+    const int plane = word & 3, k = (word >> 2) & 3;
+    if (!plane) return;
+    const int ia = plane == 3 ? i1 : i0, ib = plane == 1 ? i1 : i2;
+    const int na = k == 1 ? ib : (k == 2 ? S - 1 - ia : S - 1 - ib);
+    const int nb = k == 1 ? S - 1 - ia : (k == 2 ? S - 1 - ib : ia);
+    if (plane == 3) i1 = na; else i0 = na;
+    if (plane == 1) i1 = nb; else i2 = nb;
+}
+__device__ __forceinline__ int fdn_orient_src(int word, int comp) { return (word >> (4 + 2 * comp)) & 3; }
+__device__ __forceinline__ float fdn_orient_sign(int word, int comp) { return (word >> (10 + comp)) & 1 ? -1.f : 1.f; }
+
 // Tile of an MFMA kernel's box: td x th x tw voxels, ntd x nth x ntw tiles
 struct FdnTile { int td, th, tw, ntd, nth, ntw; };
 

@@ -26,16 +26,42 @@ struct PatchDesc {          // one per (sample, output tensor); mirrored by data
 // read from the device table `scale` (F,2).
 // mode 3, fdn_pack_patch_cores: the cores alone, contiguous, out = (B,cs,cs,cs,3) -- what a data-parallel rank sends to the rank that
 // stitches (the same element walk: out[i] is the element mode 1 would place).
+// mode 4, fdn_unrotate_accumulate: the self-ensemble's fan-in.  `pred` holds B predictions (B,S,S,S,3) of patches that were fed in a
+// rotated frame (PatchHandler3D.apply_rotation, src/Network/PatchHandler3D.py:97-108,166-274); every element of out = (B,S,S,S,3) takes
+// t = sign * pred[n][rho(a,b,c)][comp'] -- sg.orient is the INVERSE fdn_orient_word -- then v = first ? t : out + t, and on the last
+// orientation v / (float)divisor.  One IEEE add and one correctly rounded divide; it walks the destination, so writes are contiguous
+// (reads are strided for planes 2 and 3) and no two threads meet.
 struct StitchGeom {
     const float* pred;
     int64_t g0;
     int32_t Xo, Yo, Zo, side;
-    int32_t nx, ny, nz, pad_;
+    int32_t nx, ny, nz, orient;
     const double* scale;    // mode 2 only
+    int32_t first, divisor; // mode 4 only
 };
 
 __global__ __launch_bounds__(256) void gather_patches_kernel(const PatchDesc* __restrict__ desc, float* __restrict__ out, int B,
                                                               int S, int mode, StitchGeom sg) {
+    if (mode == 4) {
+        const int64_t per = (int64_t)S * S * S * 3;
+        const int64_t total = per * B;
+        const float div = (float)sg.divisor;
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t n = i / per;
+            int r = (int)(i - n * per);
+            int a = r / (S * S * 3); r -= a * S * S * 3;
+            int b = r / (S * 3); r -= b * S * 3;
+            int c = r / 3;
+            const int comp = r - c * 3;
+            fdn_rot_source(sg.orient, S, a, b, c);
+            const int sc = comp == 0 ? fdn_orient_src(sg.orient, 0) : comp == 1 ? fdn_orient_src(sg.orient, 1) : fdn_orient_src(sg.orient, 2);
+            const float sgn = comp == 0 ? fdn_orient_sign(sg.orient, 0) : comp == 1 ? fdn_orient_sign(sg.orient, 1) : fdn_orient_sign(sg.orient, 2);
+            const float t = sgn * sg.pred[(((n * S + a) * S + b) * S + c) * 3 + sc];
+            const float v = sg.first ? t : out[i] + t;
+            out[i] = sg.divisor > 1 ? v / div : v;
+        }
+        return;
+    }
     if (mode != 0) {
         const int cs = S - 2 * sg.side;                                  // core edge
         const int64_t per = (int64_t)cs * cs * cs * 3;
@@ -148,6 +174,28 @@ extern "C" int fdn_pack_patch_cores(const float* pred, float* cores, int S, int 
     sg.pred = pred; sg.side = side;
     hipLaunchKernelGGL(gather_patches_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const PatchDesc*)nullptr, cores,
                        count, S, 3, sg);
+    FDN_CHECK_LAUNCH("gather_patches_kernel");
+    return FDN_OK;
+}
+
+extern "C" int fdn_unrotate_accumulate(const float* pred, float* acc, int count, int S, int plane, int k, int first, int divisor,
+                                       void* stream) {
+    FDN_REQUIRE(pred && acc, "fdn_unrotate_accumulate: NULL argument");
+    FDN_REQUIRE(count > 0, "fdn_unrotate_accumulate: count=%d", count);
+    FDN_REQUIRE(S > 0 && S <= 512, "fdn_unrotate_accumulate: S=%d must be in 1..512", S);
+    const int word = fdn_orient_word(plane, k, 1);
+    FDN_REQUIRE(word >= 0, "fdn_unrotate_accumulate: orientation (plane=%d, k=%d) is neither (0,0) nor plane in 1..3 with k in 1..3", plane, k);
+    FDN_REQUIRE(first == 0 || first == 1, "fdn_unrotate_accumulate: first=%d must be 0 or 1", first);
+    FDN_REQUIRE(divisor >= 1, "fdn_unrotate_accumulate: divisor=%d must be at least 1", divisor);
+    const int64_t total = (int64_t)count * S * S * S * 3;
+    const uintptr_t p0 = (uintptr_t)pred, a0 = (uintptr_t)acc, bytes = (uintptr_t)total * sizeof(float);
+    FDN_REQUIRE(p0 + bytes <= a0 || a0 + bytes <= p0, "fdn_unrotate_accumulate: pred and acc overlap (%lld bytes each)", (long long)bytes);
+    int64_t nb = (total + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    StitchGeom sg{};
+    sg.pred = pred; sg.orient = word; sg.first = first; sg.divisor = divisor;
+    hipLaunchKernelGGL(gather_patches_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const PatchDesc*)nullptr, acc,
+                       count, S, 4, sg);
     FDN_CHECK_LAUNCH("gather_patches_kernel");
     return FDN_OK;
 }

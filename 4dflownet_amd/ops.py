@@ -4,6 +4,7 @@ Every function launches asynchronously on torch's current HIP stream and returns
 Tensors must be fp32, contiguous and on a ROCm device; anything else raises (no CPU path)."""
 import ctypes
 import functools
+import operator
 
 import torch
 
@@ -77,8 +78,49 @@ def _volume_geometry(frames, patch_size, counts, g0, count, who):
     return (F, X, Y, Z, int(patch_size), nx, ny, nz, int(g0), count)
 
 
-def _input_features_volume(entry, act_dtype, frames, patch_size, counts, g0, count, phase, pc):
+# the geometric self-ensemble's orientations (plane, k): the identity and the nine rotations the loader trains with, in its order
+# (data._ROT; plane 1:(0,1), 2:(0,2), 3:(1,2) np.rot90 axes, k quarter turns)
+ROT90_ORIENTATIONS = ((0, 0),) + tuple((p, k) for p in (1, 2, 3) for k in (1, 2, 3))
+
+
+def _orientation(orientation, who):
+    """(plane, k) of an `orientation=` argument: None is the identity (0, 0); anything outside ROT90_ORIENTATIONS raises ValueError."""
+    if orientation is None:
+        return 0, 0
+    try:
+        plane, k = (operator.index(v) for v in orientation)
+    except (TypeError, ValueError):
+        plane = k = -1
+    if (plane, k) not in ROT90_ORIENTATIONS or any(isinstance(v, bool) for v in orientation):
+        raise ValueError("%s: orientation must be (0, 0) or (plane, k) with plane in 1..3 and k in 1..3, got %r" % (who, orientation))
+    return plane, k
+
+
+def self_ensemble_orientations(self_ensemble):
+    """The `self_ensemble=` option of the predictor as a tuple of (plane, k) orientations, or None for off (None / False).  "rot90":
+    ROT90_ORIENTATIONS, the ten views the network was trained with; a non-empty sequence of unique valid (plane, k) pairs is used as
+    given, in its order.  Anything else raises ValueError."""
+    if self_ensemble is None or self_ensemble is False:
+        return None
+    if isinstance(self_ensemble, str):
+        if self_ensemble == "rot90":
+            return ROT90_ORIENTATIONS
+        raise ValueError('self_ensemble: %r is not a known ensemble ("rot90")' % (self_ensemble,))
+    try:
+        items = list(self_ensemble)
+    except TypeError:
+        raise ValueError('self_ensemble must be None, False, "rot90" or a sequence of (plane, k) pairs, got %r' % (self_ensemble,)) from None
+    if not items:
+        raise ValueError("self_ensemble: an empty list of orientations")
+    res = tuple(_orientation(() if o is None else o, "self_ensemble") for o in items)
+    if len(set(res)) != len(res):
+        raise ValueError("self_ensemble: the orientations must be unique, got %r" % (self_ensemble,))
+    return res
+
+
+def _input_features_volume(entry, act_dtype, frames, patch_size, counts, g0, count, phase, pc, orientation=None):
     """input_features_volume of either storage type: `entry` names the library's entry point, act_dtype is the type of phase / pc."""
+    plane, k = _orientation(orientation, "input_features_volume")
     geo = _volume_geometry(frames, patch_size, counts, g0, count, "input_features_volume")
     P, count = geo[4], geo[9]
     if phase is None:
@@ -87,15 +129,32 @@ def _input_features_volume(entry, act_dtype, frames, patch_size, counts, g0, cou
         pc = torch.empty((max(count, 0), P, P, P, 3), device=frames.device, dtype=act_dtype)
     if min(phase.numel(), pc.numel()) < max(count, 0) * P ** 3 * 3:
         raise FdnError("input_features_volume: phase / pc hold fewer than (%d,%d,%d,%d,3) elements" % (count, P, P, P))
+    if plane:                                                 # (0, 0) is the plain entry point
+        entry = entry.replace("_volume", "_volume_oriented")
+        geo = geo + (plane, k)
     check(getattr(_lib.load(), entry)(_p(frames, "frames"), *geo, _ptr(act_dtype, phase, "phase"), _ptr(act_dtype, pc, "pc"), _stream()), entry)
     return phase, pc
 
 
-def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None):
+def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None, orientation=None):
     """input_features of patches [g0, g0 + count) of the sliding window over resident frames (F,6,X,Y,Z) (u,v,w,mag_u,mag_v,mag_w,
     normalised): the patches are never materialised.  counts = (nx,ny,nz) of tiler.PatchGenerator.plan; patch g = frame g // (nx*ny*nz),
-    then (i,j,k) with k fastest.  Returns (phase, pc), each (count,P,P,P,3)."""
-    return _input_features_volume("fdn_input_features_volume", ACT_DTYPE, frames, patch_size, counts, g0, count, phase, pc)
+    then (i,j,k) with k fastest.  Returns (phase, pc), each (count,P,P,P,3).
+    orientation=(plane, k): the features of the patches as data.rotate_vector_field turns them (fdn_input_features_volume_oriented)."""
+    return _input_features_volume("fdn_input_features_volume", ACT_DTYPE, frames, patch_size, counts, g0, count, phase, pc, orientation)
+
+
+def unrotate_accumulate(pred, acc, orientation, first, divisor=1):
+    """The self-ensemble's fan-in (fdn_unrotate_accumulate): pred (count,S,S,S,3) fp32, predicted from features of `orientation`, is turned
+    back and added to acc of the same shape -- stored, not added, with `first` -- and the sum divided by `divisor` where it exceeds 1
+    (the count of orientations, on the last one).  Returns acc."""
+    S = _pred_edge(pred, "unrotate_accumulate")
+    if tuple(acc.shape) != tuple(pred.shape):
+        raise FdnError("unrotate_accumulate: acc must be %s like pred, got %s" % (tuple(pred.shape), tuple(acc.shape)))
+    plane, k = _orientation(orientation, "unrotate_accumulate")
+    check(_lib.load().fdn_unrotate_accumulate(_p(pred, "pred"), _p(acc, "acc"), pred.shape[0], S, plane, k, int(bool(first)), int(divisor),
+                                              _stream()), "fdn_unrotate_accumulate")
+    return acc
 
 
 def _pred_edge(pred, who):

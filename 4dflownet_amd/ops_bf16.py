@@ -10,7 +10,7 @@ import torch
 from . import _lib
 from ._lib import FdnError, check
 from .ops import (ACT_NONE, ACT_RELU, ACT_LEAKY, LEAKY_ALPHA, ALGO_AUTO, ROLE_FWD, _stream, loss_metrics, l2_sumsq, adam_step,  # noqa: F401
-                  stitch_patches, pack_patch_cores, volume_metrics, _ptr, _p as _pf, _mask_ptr, _input_features_volume, _dgrad_fused_multi,
+                  stitch_patches, pack_patch_cores, unrotate_accumulate, self_ensemble_orientations, volume_metrics, _ptr, _p as _pf, _mask_ptr, _input_features_volume, _dgrad_fused_multi,
                   _wgrad_batch)
 
 BF16 = torch.bfloat16
@@ -30,9 +30,9 @@ def input_features(u, v, w, mu, mv, mw, phase=None, pc=None):
     return phase, pc
 
 
-def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None):
+def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None, orientation=None):
     """ops.input_features_volume with bf16 phase / pc (the frames stay fp32)."""
-    return _input_features_volume("fdn_input_features_volume_bf16", BF16, frames, patch_size, counts, g0, count, phase, pc)
+    return _input_features_volume("fdn_input_features_volume_bf16", BF16, frames, patch_size, counts, g0, count, phase, pc, orientation)
 
 
 def pack_conv64_weights(w, wp_fwd=None, wp_dgrad=None, want_dgrad=True):

@@ -14,6 +14,7 @@ import torch
 from . import h5io, parallel
 from .data import ImageDataset
 from .network import Input, SR4DFlowNet
+from .ops import self_ensemble_orientations
 from .tiler import PatchGenerator
 
 
@@ -166,7 +167,41 @@ def _frame_scale_tensor(frame_scale, F, device):
     return t
 
 
-def predict_volume(network, frames, patch_size, batch_size, out=None, frame_scale=None, patch_range=None):
+def _orientations(self_ensemble):
+    """self_ensemble= of the predictor as the tuple of orientations to average over, or None for the plain path: off, and a list that is
+    exactly the identity (ops.self_ensemble_orientations)."""
+    orientations = self_ensemble_orientations(self_ensemble)
+    return None if orientations is None or tuple(orientations) == ((0, 0),) else orientations
+
+
+def _ensemble_acc(network, batch_size, S):
+    """The (batch_size,S,S,S,3) fp32 accumulator of the self-ensemble, kept on the network between calls (the pattern of _stage)."""
+    key = (batch_size, S)
+    st = getattr(network, "_predict_ensemble", None)
+    if st is None or st[0] != key:
+        st = (key, torch.empty((batch_size, S, S, S, 3), device=network.device, dtype=torch.float32))
+        network._predict_ensemble = st
+    return st[1]
+
+
+def _predict_batch(network, frames, patch_size, counts, g0, count, batch_size, orientations):
+    """The predictions (count,S,S,S,3) fp32 of global patches [g0, g0 + count) of resident frames.  orientations (a tuple of (plane, k),
+    or None): for each one in order the features are formed in the rotated frame (ops.input_features_volume(orientation=)), the network
+    runs on them and the prediction is turned back into the accumulator (ops.unrotate_accumulate); the last one divides by their
+    number.  The mean lives in the accumulator until the next batch: the caller stitches or packs it before asking for another."""
+    if orientations is None:
+        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, count)
+        return network.forward_features(phase, pc)
+    acc = _ensemble_acc(network, batch_size, patch_size * network.res_increase)[:count]
+    last = len(orientations) - 1
+    for j, o in enumerate(orientations):
+        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, count, orientation=o)
+        network.ops.unrotate_accumulate(network.forward_features(phase, pc), acc, o, first=j == 0,
+                                        divisor=len(orientations) if j == last else 1)
+    return acc
+
+
+def predict_volume(network, frames, patch_size, batch_size, out=None, frame_scale=None, patch_range=None, self_ensemble=None):
     """Sliding-window inference with the tiler on the device (predictor.py:67-115 without its host work).  frames: (F,6,X,Y,Z)
     normalised fp32 (u,v,w,mag_u,mag_v,mag_w as ImageDataset.load_vectorfield leaves them), numpy or a device tensor; they are
     uploaded once.  Runs batches of `batch_size` consecutive global patches -- a batch may span two frames, so only the last one is
@@ -177,7 +212,11 @@ def predict_volume(network, frames, patch_size, batch_size, out=None, frame_scal
     FINISHED instead -- prediction * venc, +0.0 where its magnitude is below the threshold (predictor.py:103-107; a threshold of 0
     zeroes nothing) -- inside the stitch launch.
     patch_range=(lo, hi): only global patches [lo, hi) are computed and stitched (a data-parallel shard); the voxels of the other
-    patches are left as they are.  Everything is queued on the current stream."""
+    patches are left as they are.  Everything is queued on the current stream.
+    self_ensemble ("rot90", or a sequence of (plane, k) orientations; ops.self_ensemble_orientations): every batch is predicted under each
+    orientation -- the rotations the loader trains with, data.rotate_vector_field -- turned back and averaged in fp32 on the device before
+    it is stitched (_predict_batch): len(orientations) forwards per patch.  None, False or [(0, 0)]: the plain path."""
+    orientations = _orientations(self_ensemble)
     frames = network._to_dev(frames)
     if frames.dim() != 5 or frames.shape[1] != 6:
         raise ValueError("predict_volume: frames must be (F,6,X,Y,Z), got %s" % (tuple(frames.shape),))
@@ -195,8 +234,8 @@ def predict_volume(network, frames, patch_size, batch_size, out=None, frame_scal
     if not 0 <= lo <= hi <= total:
         raise ValueError("predict_volume: patch_range (%d, %d) outside [0, %d]" % (lo, hi, total))
     for g0 in range(lo, hi, batch_size):
-        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, min(batch_size, hi - g0))
-        network.ops.stitch_patches(network.forward_features(phase, pc), out, 2 * R, counts, g0, frame_scale=scale)
+        pred = _predict_batch(network, frames, patch_size, counts, g0, min(batch_size, hi - g0), batch_size, orientations)
+        network.ops.stitch_patches(pred, out, 2 * R, counts, g0, frame_scale=scale)
     return out
 
 
@@ -208,11 +247,13 @@ def shard_frame_span(lo, hi, per_frame):
     return lo // per_frame, (hi - 1) // per_frame + 1
 
 
-def predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=0):
+def predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=0, self_ensemble=None):
     """The shard of a data-parallel rank: global patches [lo, hi) in batches of `batch_size` consecutive patches, the core of every
     prediction packed (ops.pack_patch_cores) into ONE (hi - lo, c, c, c, 3) fp32 device buffer, c = (patch_size - 4) * R -- what the
     rank sends; the receiver stitches it with side 0 at g0 = lo.  frames as in predict_volume; they may hold only the frames the range
-    touches (shard_frame_span), first_frame being the global index of frames[0]."""
+    touches (shard_frame_span), first_frame being the global index of frames[0].  self_ensemble: as in predict_volume; the mean over the
+    orientations is formed before the cores are packed, so what travels and what the receiver does are the same."""
+    orientations = _orientations(self_ensemble)
     frames = network._to_dev(frames)
     if frames.dim() != 5 or frames.shape[1] != 6:
         raise ValueError("predict_cores: frames must be (F,6,X,Y,Z), got %s" % (tuple(frames.shape),))
@@ -227,8 +268,8 @@ def predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=0
     cores = torch.empty((hi - lo, c, c, c, 3), device=frames.device, dtype=torch.float32)
     for s in range(lo, hi, batch_size):
         e = min(s + batch_size, hi)
-        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, s - base, e - s)
-        network.ops.pack_patch_cores(network.forward_features(phase, pc), 2 * R, out=cores[s - lo:e - lo])
+        pred = _predict_batch(network, frames, patch_size, counts, s - base, e - s, batch_size, orientations)
+        network.ops.pack_patch_cores(pred, 2 * R, out=cores[s - lo:e - lo])
     return cores
 
 
@@ -295,7 +336,7 @@ def _recv_cores(network, shapes):
 
 
 def _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size, round_small_values, verbose,
-                         frames_per_group, on_group=None, device_finish=None):
+                         frames_per_group, on_group=None, device_finish=None, self_ensemble=None):
     """predict_file with the tiler on the device: rows in groups whose frames and stitched output fit DEVICE_TILER_GROUP_BYTES (or
     frames_per_group rows), one predict_volume per group, de-normalised and zeroed inside its stitch launches (frame_scale); the
     finished float64 group travels to pinned host memory on the copy stream while the next group computes and is then appended exactly
@@ -306,7 +347,8 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
     on_group(rows, vol): called on rank 0 for every group once it is stitched (the peers' cores included), before the copy-out, with the
     row numbers and the group's (len(rows),3,X*R,Y*R,Z*R) device tensor; what it queues on the current stream runs before the next group
     (evaluate_file).  output_filepath=None: no staging buffers, no copy to the host and no file; nothing is returned per row.
-    device_finish: overrides FDN_DEVICE_FINISH."""
+    device_finish: overrides FDN_DEVICE_FINISH.  self_ensemble: handed to predict_volume and, on the peers, predict_cores."""
+    orientations = _orientations(self_ensemble)
     world, rank = parallel.world_size(), parallel.rank()
     if device_finish is None:
         device_finish = os.environ.get("FDN_DEVICE_FINISH", "1") not in ("", "0")
@@ -343,7 +385,8 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
             if hi > lo:                                                # an empty shard neither sends nor is waited for
                 f0, f1 = shard_frame_span(lo, hi, per_frame_patches)
                 frames, _ = load(list(range(r0 + f0, r0 + f1)))
-                _send_cores(network, predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=f0))
+                _send_cores(network, predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=f0,
+                                                   self_ensemble=orientations))
         return written
 
     write = output_filepath is not None
@@ -357,8 +400,9 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
         ev.synchronize()
         host = stage[slot].numpy()
         if verbose:
-            print("Processed rows %d-%d/%d: %d patches in %.2f secs." % (rows[0] + 1, rows[-1] + 1, nr_rows, len(rows) * per_frame_patches,
-                                                                       time.time() - t0))
+            print("Processed rows %d-%d/%d: %d patches%s in %.2f secs." % (
+                rows[0] + 1, rows[-1] + 1, nr_rows, len(rows) * per_frame_patches,
+                "" if orientations is None else " x %d orientations" % len(orientations), time.time() - t0))
         for f, (venc, vpp, dx) in enumerate(meta):
             vols, cols = [], []
             for i in range(3):
@@ -385,7 +429,8 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
         if device_finish:                                              # the doubles the host finish multiplies and compares with
             scale = _frame_scale_tensor([(venc, vpp if round_small_values else 0.0) for venc, vpp, _ in meta], len(rows), network.device)
         bounds = shard_bounds(len(rows) * per_frame_patches, world)
-        vol = predict_volume(network, frames, patch_size, batch_size, frame_scale=scale, patch_range=(bounds[0], bounds[1]))
+        vol = predict_volume(network, frames, patch_size, batch_size, frame_scale=scale, patch_range=(bounds[0], bounds[1]),
+                             self_ensemble=orientations)
         peers = {r: (bounds[r + 1] - bounds[r], core, core, core, 3) for r in range(1, world) if bounds[r + 1] > bounds[r]}
         if peers:                                                      # posted after the own shard (see predict_patches)
             for r, cores in _recv_cores(network, peers).items():
@@ -410,17 +455,21 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
 
 
 def predict_file(network, input_filepath, output_filepath, patch_size, res_increase, batch_size=8,
-                 round_small_values=True, verbose=True, device_tiler=False, frames_per_group=None):
+                 round_small_values=True, verbose=True, device_tiler=False, frames_per_group=None, self_ensemble=None):
     """predictor.py:67-115 for every row of the input file.  Returns the list of (u,v,w) volumes written (rank 0; the other ranks
     of a data-parallel run compute their shard of every row's patches and return an empty list).
     device_tiler=True (or FDN_DEVICE_TILER=1): patchify and stitch run on the device (predict_volume) over groups of rows --
     frames_per_group rows, default what fits DEVICE_TILER_GROUP_BYTES; same file, same returned volumes (dtype and shape).  The
     de-normalisation and the zeroing of sub-pixel velocities run inside the stitch launch (FDN_DEVICE_FINISH=0: on the host, as before).
     Data-parallel runs shard every group's patches over the ranks; the peers send the cores of their patches, rank 0 stitches, finishes
-    and writes (_predict_file_device)."""
-    if device_tiler or os.environ.get("FDN_DEVICE_TILER", "0") not in ("", "0"):
+    and writes (_predict_file_device).
+    self_ensemble ("rot90" or a sequence of (plane, k) orientations, see predict_volume): every patch is predicted under each orientation
+    and the predictions are averaged.  It exists on the device tiler only: when set, the file goes through _predict_file_device whatever
+    device_tiler says (FDN_DEVICE_FINISH=0 keeps working); the host tiler path below does not have it."""
+    orientations = _orientations(self_ensemble)
+    if orientations is not None or device_tiler or os.environ.get("FDN_DEVICE_TILER", "0") not in ("", "0"):
         return _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size,
-                                    round_small_values, verbose, frames_per_group)
+                                    round_small_values, verbose, frames_per_group, self_ensemble=orientations)
     pgen = PatchGenerator(patch_size, res_increase)
     dataset = ImageDataset()
     nr_rows = dataset.get_dataset_len(input_filepath)
@@ -500,7 +549,7 @@ def write_metrics_csv(csv_path, metrics, first_row=0):
 
 
 def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase, batch_size=8, round_small_values=True,
-                  output_filepath=None, csv_path=None, frames_per_group=None, verbose=True, return_sums=False):
+                  output_filepath=None, csv_path=None, frames_per_group=None, verbose=True, return_sums=False, self_ensemble=None):
     """Predict every row of the low-resolution file with the tiler on the device (_predict_file_device) and score the finished float64
     prediction, in m/s, against u, v, w of the same row of the high-resolution file (m/s as well: nothing is rescaled), where the
     prediction already is: ops.volume_metrics on every stitched group, 26 doubles per row to the host, metrics_from_sums there.  The
@@ -509,8 +558,10 @@ def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase
     output_filepath=None: the prediction never leaves the device (no staging copy, no HDF5 write).  Given: the file
     predict_file(device_tiler=True) writes.  csv_path: write_metrics_csv.  Data-parallel: the peers send their cores as in
     _predict_file_device; rank 0 evaluates (and writes) and returns the list, the other ranks return [].
-    ValueError, before any GPU work: the two files hold different numbers of rows, the HR volume is not res_increase x the LR volume, or
-    the mask has neither one row nor one per row."""
+    self_ensemble: as in predict_file -- the scores are those of the averaged prediction, what the option buys on this checkpoint.
+    ValueError, before any GPU work: an invalid self_ensemble, the two files hold different numbers of rows, the HR volume is not
+    res_increase x the LR volume, or the mask has neither one row nor one per row."""
+    orientations = _orientations(self_ensemble)
     dataset = ImageDataset()
     nr_rows = dataset.get_dataset_len(input_filepath)
     hr_rows = dataset.get_dataset_len(hr_filepath)
@@ -543,7 +594,8 @@ def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase
 
     t0 = time.time()
     _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size, round_small_values,
-                         verbose and output_filepath is not None, frames_per_group, on_group=score, device_finish=True)
+                         verbose and output_filepath is not None, frames_per_group, on_group=score, device_finish=True,
+                         self_ensemble=orientations)
     if parallel.rank() != 0:
         return ([], np.empty((0, len(VOLUME_SUM_NAMES)))) if return_sums else []
     sums = np.empty((nr_rows, len(VOLUME_SUM_NAMES)), dtype=np.float64)
@@ -554,7 +606,8 @@ def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase
         for i, m in enumerate(metrics):
             print("Row %d/%d: rel. error %.3f %%, RMSE %.5f m/s, slope u/v/w %.4f/%.4f/%.4f, R2 %.4f/%.4f/%.4f" % (
                 i + 1, nr_rows, m["rel_error"], m["rmse"], m["k_u"], m["k_v"], m["k_w"], m["r2_u"], m["r2_v"], m["r2_w"]))
-        print("Evaluated %d rows in %.2f secs." % (nr_rows, time.time() - t0))
+        print("Evaluated %d rows%s in %.2f secs." % (nr_rows, "" if orientations is None else " x %d orientations" % len(orientations),
+                                                     time.time() - t0))
     if csv_path is not None:
         write_metrics_csv(csv_path, metrics)
     return (metrics, sums) if return_sums else metrics
@@ -562,15 +615,17 @@ def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase
 
 def main(data_dir='../data', filename='example_data.h5', output_dir="../result", output_filename='example_result.h5',
          model_path="../models/4DFlowNet/4DFlowNet.h5", patch_size=24, res_increase=2, batch_size=8,
-         round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32", device_tiler=False, frames_per_group=None):
-    """Same hard-coded surface as predictor.py:31-47 (+ dtype, + the device tiler switch of predict_file)."""
+         round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32", device_tiler=False, frames_per_group=None,
+         self_ensemble=None):
+    """Same hard-coded surface as predictor.py:31-47 (+ dtype, + the device tiler switch and self_ensemble of predict_file)."""
     parallel.init_from_env()
     network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype)
     network.load_weights(model_path)
     if not os.path.isdir(output_dir) and parallel.rank() == 0:
         os.makedirs(output_dir)
     predict_file(network, '{}/{}'.format(data_dir, filename), '{}/{}'.format(output_dir, output_filename), patch_size,
-                 res_increase, batch_size, round_small_values, device_tiler=device_tiler, frames_per_group=frames_per_group)
+                 res_increase, batch_size, round_small_values, device_tiler=device_tiler, frames_per_group=frames_per_group,
+                 self_ensemble=self_ensemble)
     if parallel.rank() == 0:
         print("Done!")
 
@@ -578,7 +633,7 @@ def main(data_dir='../data', filename='example_data.h5', output_dir="../result",
 def evaluate_main(data_dir='../data', filename='example_data.h5', hr_filename='example_data_HR.h5', output_dir="../result",
                   csv_filename='example_metrics.csv', output_filename=None, model_path="../models/4DFlowNet/4DFlowNet.h5", patch_size=24,
                   res_increase=2, batch_size=8, round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32",
-                  frames_per_group=None):
+                  frames_per_group=None, self_ensemble=None):
     """The surface of main() for scoring a checkpoint: + hr_filename, the ground truth beside `filename`, and csv_filename; the
     prediction itself is written only with output_filename."""
     parallel.init_from_env()
@@ -588,7 +643,8 @@ def evaluate_main(data_dir='../data', filename='example_data.h5', hr_filename='e
         os.makedirs(output_dir)
     evaluate_file(network, '{}/{}'.format(data_dir, filename), '{}/{}'.format(data_dir, hr_filename), patch_size, res_increase, batch_size,
                   round_small_values, output_filepath=None if output_filename is None else '{}/{}'.format(output_dir, output_filename),
-                  csv_path='{}/{}'.format(output_dir, csv_filename) if parallel.rank() == 0 else None, frames_per_group=frames_per_group)
+                  csv_path='{}/{}'.format(output_dir, csv_filename) if parallel.rank() == 0 else None, frames_per_group=frames_per_group,
+                  self_ensemble=self_ensemble)
     if parallel.rank() == 0:
         print("Done!")
 

@@ -322,6 +322,31 @@ int fdn_stitch_patches_finish(const float* pred, double* vol, const double* fram
  * Refused before the device is touched: NULL pointers, side < 0, S <= 2*side, S > 512, count <= 0. */
 int fdn_pack_patch_cores(const float* pred, float* cores, int S, int side, int count, void* stream);
 
+/* Geometric self-ensemble: inference averaged over the patch rotations the loader trains with (PatchHandler3D.apply_rotation,
+ * src/Network/PatchHandler3D.py:97-108,166-274).  An orientation is (plane, k): (0,0) the identity, else plane 1:(0,1), 2:(0,2), 3:(1,2)
+ * (np.rot90 axes) with k = 1..3 quarter turns; (p,0), (0,k) and anything else are refused.  Each orientation has a component permutation
+ * `perm` and a sign rule `sign` (the table of data._ROT); a patch v turns into  v'[i] = sign[i] * rot90(v[perm[i]], k, axes)  -- the
+ * magnitudes with the same permutation and no sign -- and a prediction p' made in that frame turns back as
+ * q[perm[i]] = sign[i] * rot90(p'[..., i], 4 - k, axes).
+ *
+ * fdn_input_features_volume with the window patch turned first: voxel (a,b,c) of patch g reads the window voxel np.rot90 puts there
+ * (zero outside the volume), THEN the six values are permuted and the velocities multiplied by their sign -- a padded zero under a
+ * negative sign is -0.0 -- and the norms are taken of the permuted components in their new order.  phase, pc equal, bit for bit and sign
+ * of zero included, PatchGenerator.patchify -> apply_rotation -> fdn_input_features on those patches.  Orientation (0,0) is
+ * fdn_input_features_volume itself.  A path of the same kernel (the by-value geometry carries the orientation).  Refusals: those of
+ * fdn_input_features_volume, and an orientation outside the set. */
+int fdn_input_features_volume_oriented(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
+                                       int count, int plane, int k, float* phase, float* pc, void* stream);
+/* The fan-in of the ensemble, the inverse of apply_rotation (src/Network/PatchHandler3D.py:97-108,166-274) on a prediction: pred and acc
+ * are (count,S,S,S,3) fp32, pred the predictions made under orientation (plane, k).  For every
+ * element of acc:  t = the element of q above (sign * pred at the rotated index and permuted component);  v = first ? t : acc + t;
+ * acc = divisor > 1 ? v / (float)divisor : v.  Plain IEEE fp32 -- one add, and one correctly rounded divide on the call that carries the
+ * count of orientations -- so numpy float32 reproduces it bit for bit; with first = 1 acc is not read.  (0,0), first = 1, divisor = 1 is a
+ * copy.  The destination is walked (contiguous writes, no atomics); a runtime mode of the gather kernel.  Refused before the device is
+ * touched: NULL pointers, count <= 0, S <= 0 or S > 512, an orientation outside the set, first not 0 or 1, divisor < 1, pred and acc
+ * ranges that overlap. */
+int fdn_unrotate_accumulate(const float* pred, float* acc, int count, int S, int plane, int k, int first, int divisor, void* stream);
+
 /* sum of squares of the kernel (non-bias) parameters: the l2(5e-7) regulariser value is 5e-7 * out[0].
  * src/Network/TrainerController.py:129-141.  is_kernel: one byte per parameter. */
 int fdn_l2_sumsq(const float* w, const uint8_t* is_kernel, int64_t n, float* out, void* stream);
@@ -481,6 +506,9 @@ int fdn_input_features_bf16(const float* u, const float* v, const float* w, cons
 /* The volume form with bf16 phase / pc (src/Network/PatchGenerator.py:13-40,53-86,116-154, src/predictor.py:67-115); frames stay fp32. */
 int fdn_input_features_volume_bf16(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
                                    int count, uint16_t* phase, uint16_t* pc, void* stream);
+/* fdn_input_features_volume_oriented with bf16 phase / pc (src/Network/PatchHandler3D.py:97-108,166-274); frames stay fp32. */
+int fdn_input_features_volume_oriented_bf16(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
+                                            int count, int plane, int k, uint16_t* phase, uint16_t* pc, void* stream);
 int fdn_conv3d_fwd_bf16(const uint16_t* x, const uint16_t* x2, const float* w, const uint16_t* wpack, const float* bias,
                         const uint16_t* residual, void* y, int N, int D, int H, int W, int Cin, int Cout, int K, int ldy,
                         int y_coff, int act, float alpha, void* stream);

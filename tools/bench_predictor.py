@@ -7,7 +7,13 @@ synthetic 100x100x100 volume (125 patches); prints patches/s.  Launch under torc
 median, the spread (min .. max) and patches/s.  Single process: host tiler, device tiler with the host finish (FDN_DEVICE_FINISH=0) and
 device tiler with the finish inside the stitch launch (the default).  Under torch.distributed.run: the data-parallel host tiler (whole
 patches to rank 0, stitched on its host) and the data-parallel device tiler (cores to rank 0, stitched and finished on its device); with
-fewer devices than ranks the lines are marked oversubscribed and are no scaling numbers."""
+fewer devices than ranks the lines are marked oversubscribed and are no scaling numbers.
+
+--self-ensemble [--runs N] [--plain-only]: the geometric self-ensemble (predict_volume(self_ensemble="rot90")) at the cfg5 shapes, single
+process.  Per batch of 8 patches (24^3 -> 48^3), by device events: the forward, and for each of the ten orientations the oriented window
+features and the rotate-back-and-accumulate launch, with the two new paths together as a share of the forward.  Then predict_volume on
+synthetic 100^3 frames, plain (four frames, 500 patches) and with the ten orientations (one frame, 125 patches), alternately, N >= 3 timed
+runs each: every run, median, spread and patches/s.  --plain-only: the plain leg alone (the command of a tools/ab_source.sh comparison)."""
 import importlib
 import os
 import sys
@@ -44,19 +50,90 @@ LEGS_SINGLE = (("host", False, None), ("device, host finish", True, "0"), ("devi
 LEGS_DP = (("dp host", False, None), ("dp device", True, "1"))
 
 
-def device_tiler_leg(net, dtype, runs, rank=0, world=1):
-    """predict_file end to end (load, patchify, forward, stitch, post-processing) with the file append replaced by a no-op."""
-    import statistics
-    import tempfile
-    build = importlib.import_module("4dflownet_amd.build")
+def _stamp_line():
+    """The first line of a profile: the commit (FDN_COMMIT where the tree is a snapshot without its history) and the library source stamp."""
     import subprocess
-    say = print if rank == 0 else (lambda *a, **k: None)
+    build = importlib.import_module("4dflownet_amd.build")
     commit = os.environ.get("FDN_COMMIT")                  # a snapshot of the tree without its history: the caller names the commit
     if not commit:
         r = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True)
         d = subprocess.run(["git", "-C", ROOT, "status", "--porcelain", "--untracked-files=no"], capture_output=True, text=True)
         commit = r.stdout.strip() + ("+dirty" if d.stdout.strip() else "") if r.returncode == 0 else "unknown"
-    say("# commit %s lib_source_stamp %s" % (commit, build.source_stamp()))
+    return "# commit %s lib_source_stamp %s" % (commit, build.source_stamp())
+
+
+def _event_us(fn, reps=50, warm=5):
+    """Mean device time of fn() in microseconds: `reps` calls between two events on the current stream, after `warm` calls."""
+    for _ in range(warm):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1000.0 / reps
+
+
+def self_ensemble_leg(net, dtype, runs, plain_only=False):
+    """The cost of predict_volume(self_ensemble="rot90") at the cfg5 shapes; see the module docstring."""
+    import statistics
+    P, R, B = 24, 2, 8
+    print(_stamp_line())
+    print("# tools/bench_predictor.py --self-ensemble --runs %d%s%s: patch 24, res x2, batch 8, 8+4 ResBlocks, %s, %s"
+          % (runs, " --plain-only" if plain_only else "", " --bf16" if dtype != "float32" else "", dtype, torch.cuda.get_device_name(0)))
+    rng = np.random.default_rng(0)
+    frames = np.concatenate([rng.uniform(-1, 1, (4, 3, 100, 100, 100)), rng.uniform(0, 0.016, (4, 3, 100, 100, 100))], axis=1).astype(np.float32)
+    dframes = torch.from_numpy(frames).cuda()
+    counts, _, extents = tiler.PatchGenerator(P, R).plan((100, 100, 100))
+    per_frame = counts[0] * counts[1] * counts[2]
+    orientations = net.ops.self_ensemble_orientations("rot90")
+    if not plain_only:
+        g0 = per_frame // 2 - B // 2                           # a batch from the middle of the volume
+        phase, pc = net.ops.input_features_volume(dframes, P, counts, g0, B)
+        pred = net.forward_features(phase, pc).clone()
+        acc = torch.empty_like(pred)
+        fwd = _event_us(lambda: net.forward_features(phase, pc), reps=20)
+        print("per batch of %d patches: forward %.1f us" % (B, fwd))
+        feat, unrot = {}, {}
+        for o in orientations:
+            feat[o] = _event_us(lambda: net.ops.input_features_volume(dframes, P, counts, g0, B, phase=phase, pc=pc, orientation=o))
+            unrot[o] = _event_us(lambda: net.ops.unrotate_accumulate(pred, acc, o, False, 10 if o == orientations[-1] else 1))
+            print("  orientation (%d,%d): oriented features %6.1f us, rotate back + accumulate %6.1f us, together %.2f %% of the forward"
+                  % (o[0], o[1], feat[o], unrot[o], 100.0 * (feat[o] + unrot[o]) / fwd))
+        new = sum(feat[o] + unrot[o] for o in orientations)
+        print("ten orientations: the two new paths %.1f us against ten forwards %.1f us = %.2f %%; the plain features alone %.1f us"
+              % (new, 10 * fwd, 100.0 * new / (10 * fwd), feat[(0, 0)]))
+    legs = [("plain", None, 4)] + ([] if plain_only else [("rot90", "rot90", 1)])
+    outs = {nf: torch.empty((nf, 3) + extents, device="cuda") for _, _, nf in legs}
+    times = dict((leg[0], []) for leg in legs)
+    for r in range(runs + 1):                                  # run 0 warms both legs up
+        for leg, option, nf in legs:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            predictor.predict_volume(net, dframes[:nf], P, B, out=outs[nf], self_ensemble=option)
+            torch.cuda.synchronize()
+            if r:
+                times[leg].append(time.perf_counter() - t0)
+    rate = {}
+    for leg, option, nf in legs:
+        t = times[leg]
+        med = statistics.median(t)
+        rate[leg] = nf * per_frame / med
+        print("predict_volume %-5s (%d x 100^3, %d patches%s): runs %s s; median %.3f s (min %.3f .. max %.3f) = %.1f patches/s"
+              % (leg, nf, nf * per_frame, "" if option is None else " x %d orientations" % len(orientations),
+                 " ".join("%.3f" % x for x in t), med, min(t), max(t), rate[leg]))
+    if not plain_only:
+        print("rot90 / plain patches/s: %.4f (1/K = %.4f)" % (rate["rot90"] / rate["plain"], 1.0 / len(orientations)))
+
+
+def device_tiler_leg(net, dtype, runs, rank=0, world=1):
+    """predict_file end to end (load, patchify, forward, stitch, post-processing) with the file append replaced by a no-op."""
+    import statistics
+    import tempfile
+    say = print if rank == 0 else (lambda *a, **k: None)
+    say(_stamp_line())
     say("# tools/bench_predictor.py --device-tiler --runs %d%s: predict_file wall time without the HDF5 write, patch 24, res x2, batch 8, "
         "8+4 ResBlocks, %s, %s" % (runs, " --bf16" if dtype != "float32" else "", dtype, torch.cuda.get_device_name(0)))
     legs = LEGS_SINGLE
@@ -112,6 +189,12 @@ def main():
     torch.cuda.set_device(local % ndev)
     dtype = "bfloat16" if "--bf16" in sys.argv else "float32"
     net = predictor.prepare_network(24, 2, 8, 4, dtype=dtype)
+    if "--self-ensemble" in sys.argv:
+        if world > 1:
+            raise SystemExit("--self-ensemble is a single-process measurement")
+        runs = int(sys.argv[sys.argv.index("--runs") + 1]) if "--runs" in sys.argv else 3
+        self_ensemble_leg(net, dtype, max(runs, 3), plain_only="--plain-only" in sys.argv)
+        return
     if "--device-tiler" in sys.argv:
         runs = int(sys.argv[sys.argv.index("--runs") + 1]) if "--runs" in sys.argv else 3
         device_tiler_leg(net, dtype, max(runs, 3), rank, world)
