@@ -182,7 +182,10 @@ int fdn_conv64_wino_launch_boxes(const FdnConv64Call& c, const FdnWinoBox* boxes
         return FDN_OK;
     }
     const WinoRegion& r0 = a.reg[0];
-    const bool simple = a.nreg == 1 && r0.ta0 == 0 && r0.ta1 == 2 && r0.tb0 == 0 && r0.tb1 == 2;
+    // the single-region instantiation is the forward's: the inner box of a fused dgrad issued on its own (FDN_DGRAD_INNER) is one region
+    // with all taps too, but it left the integer iw in channel 12 of every 16 where a lane stores a surface voxel to the padded scratch
+    // after fused stores (the far w surface, interior d and h); it runs the instantiation the one-launch form runs, bit for bit
+    const bool simple = a.nreg == 1 && !a.fout && r0.ta0 == 0 && r0.ta1 == 2 && r0.tb0 == 0 && r0.tb1 == 2;
     if (simple) hipLaunchKernelGGL((conv64_wino_kernel<CS, false>), dim3((unsigned)blocks), dim3(256), lds, c.s, a);
     else hipLaunchKernelGGL((conv64_wino_kernel<CS, true>), dim3((unsigned)blocks), dim3(256), lds, c.s, a);
     FDN_CHECK_LAUNCH("conv64_wino_kernel");

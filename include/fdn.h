@@ -22,7 +22,14 @@
  *   - tensors are NDHWC, channel innermost; conv kernels are Keras layout (kd,kh,kw,Cin,Cout);
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream);
  *   - return value: FDN_OK or a negative error code; fdn_last_error() gives a message
- *     (thread-local).  No exceptions cross the boundary.
+ *     (thread-local).  No exceptions cross the boundary;
+ *   - memory contract: an entry point reads no byte outside the extents its arguments describe (N, D, H, W, channel counts,
+ *     ld* / *_coff, element counts, descriptor tables) and writes no byte outside its outputs and the first
+ *     fdn_*_workspace_bytes() bytes of its workspace (a fixed size where this header states one, e.g. 2048 * 64 floats);
+ *     it never reads workspace or output memory before writing it, so neither needs initialising and whatever lies beside
+ *     an operand -- NaN, Inf, another tensor -- cannot reach a result.  Tile overhangs are served by offsets that fall
+ *     outside the buffer range ("reads zero") or by clamped indices with predicated stores, never by a load of a
+ *     neighbour times zero (tests/test_gpu_guard_bands.py, DESIGN.md "Memory contract").
  */
 #ifndef FDN_H
 #define FDN_H
