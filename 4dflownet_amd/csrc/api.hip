@@ -2,10 +2,12 @@
 // See include/fdn.h for the contract and the reference call sites each entry point replaces.
 #include <stdarg.h>
 #include <stdio.h>
+#include <algorithm>
 #include <mutex>
 #include <set>
 #include <string>
 #include <string.h>
+#include <type_traits>
 #include <utility>
 #include "fdn_common.h"
 
@@ -97,7 +99,7 @@ template <typename T> int fdn_wgrad_cin3_launch(const T* x, const T* dz, float* 
                                                 int H, int W, hipStream_t s);
 template <typename T> int fdn_wgrad_cout1_launch(const T* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N,
                                                  int D, int H, int W, int lddz, int dz_coff, hipStream_t s);
-template <typename T> int fdn_conv_cout1_dgrad_folded_launch(const float* dz, const float* w, const T* y_prev, int act,
+template <typename T> int fdn_conv_cout1_dgrad_folded_launch(const char* who, const float* dz, const float* w, const T* y_prev, int act,
                                                              float alpha, T* dz_prev, float* dbias_prev, void* workspace,
                                                              size_t workspace_bytes, int N, int D, int H, int W, int lddz,
                                                              int dz_coff, hipStream_t s, const uint16_t* ymask = nullptr);
@@ -107,57 +109,86 @@ template <typename T> int fdn_bias_grad_launch(const T* dz, float* db, void* ws,
                                                int lddz, int dz_coff, hipStream_t s);
 size_t fdn_small_wgrad_workspace_bytes(int Cin, int Cout, int K);
 
-// The fp32 64->64 entry points: the checks they share, and their call descriptor -- a forward over the (N, D, H, W) grid, or a dgrad
-// (op FDN_CONV64_DGRAD[_FUSED]) onto its padded (D+2, H+2, W+2) grid.  mask_act: act must be one a sign mask belongs to.
-static int conv64_check(const char* who, int algo, int N, int D, int H, int W, int act, bool mask_act = false) {
+// An operator that exists once per storage type (fdn_x / fdn_x_bf16) has ONE body below: a static function template on T = float /
+// uint16_t (bf16 bits) that takes the called entry point's name as `who`; the extern "C" twins forward to it.  Where the two modes
+// differ, the difference stands where it occurs: an `if constexpr (kBf16<T>)` or the overload pair wgrad64_launch.  The bf16 entry
+// points take no algo and pass FDN_ALGO_AUTO.
+template <typename T> constexpr bool kBf16 = sizeof(T) == 2;
+
+// The 64->64 entry points: the checks they share, and their call descriptors -- a forward over the (N, D, H, W) grid, or a dgrad
+// (op FDN_CONV64_DGRAD[_FUSED]) onto its padded (D+2, H+2, W+2) grid.  mask_act: act must be one a sign mask belongs to.  limit: the
+// largest extent (1020: what a padded grid and the mask forms address; the plain forwards take 1022)
+static int conv64_check(const char* who, int algo, int N, int D, int H, int W, int act, bool mask_act = false, int limit = 1020) {
     FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "%s: bad algo %d", who, algo);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= 1020 && H <= 1020 && W <= 1020, "%s: bad dims", who);
+    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= limit && H <= limit && W <= limit, "%s: bad dims", who);
     if (mask_act) FDN_REQUIRE(act == FDN_ACT_RELU || act == FDN_ACT_LEAKY, "%s: a mask belongs to an activation (act %d)", who, act);
     else FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "%s: bad act %d", who, act);
     return FDN_OK;
 }
 
-static FdnConv64Call conv64_call(FdnConv64Op op, const float* x, const float* wpack, float* y, int N, int D, int H, int W, int act,
-                                 float alpha, void* stream) {
+// what every call says: FdnConv64Call for float rows, FdnConv64BfCall for bf16 ones; the entry point adds the output and its own operands
+template <typename T>
+static std::conditional_t<kBf16<T>, FdnConv64BfCall, FdnConv64Call> conv64_call(FdnConv64Op op, const T* x, const T* wpack, int N, int D, int H,
+                                                                                int W, int act, float alpha, void* stream) {
     const int pad = op == FDN_CONV64_FWD ? 0 : 2;
-    FdnConv64Call c;
-    c.op = op; c.x = x; c.wpack = wpack; c.y = y;
+    std::conditional_t<kBf16<T>, FdnConv64BfCall, FdnConv64Call> c;
+    c.op = op; c.x = x; c.wpack = wpack;
     c.N = N; c.ID = D; c.IH = H; c.IW = W; c.OD = D + pad; c.OH = H + pad; c.OW = W + pad;
     c.act = act; c.alpha = alpha; c.s = (hipStream_t)stream;
     return c;
 }
 
+// the checked 64->64 forward of either storage type; ymask: also write the sign mask of the output.  fp32 routes by algo, bf16 has one kernel
+template <typename T>
+static int conv64_fwd_launch(const T* x, const T* wpack, const float* bias, const T* residual, T* y, uint16_t* ymask, int N, int D, int H, int W,
+                             int act, float alpha, int algo, void* stream) {
+    auto c = conv64_call(FDN_CONV64_FWD, x, wpack, N, D, H, W, act, alpha, stream);
+    c.y = y; c.bias = bias; c.residual = residual; c.ymask = ymask;
+    if constexpr (kBf16<T>) return fdn_conv64_bf16_launch(c);
+    else return fdn_conv64_launch_ex(c, 3, algo);
+}
+
+// y: T rows, except the heads' (Cout == 1) fp32 prediction in both modes
+template <typename T>
+static int conv3d_fwd(const char* who, const T* x, const T* x2, const float* w, const T* wpack, const float* bias, const T* residual, void* y,
+                      int N, int D, int H, int W, int Cin, int Cout, int K, int ldy, int y_coff, int act, float alpha, int algo, void* stream) {
+    FDN_REQUIRE(x && y, "%s: x/y is NULL", who);
+    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "%s: bad algo %d", who, algo);
+    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "%s: bad dims N=%d D=%d H=%d W=%d", who, N, D, H, W);
+    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "%s: bad act %d", who, act);
+    hipStream_t s = (hipStream_t)stream;
+    if (Cin == 64 && Cout == 64 && K == 3) {
+        FDN_REQUIRE(wpack, "%s: the 64->64 MFMA path needs wpack (fdn_pack_conv64_weights%s)", who, kBf16<T> ? "_bf16" : "");
+        FDN_REQUIRE(ldy == 64 && y_coff == 0, "%s: 64->64 path writes dense rows (ldy=64,y_coff=0)", who);
+        FDN_REQUIRE(D <= 1022 && H <= 1022 && W <= 1022, "%s: dims too large", who);
+        return conv64_fwd_launch(x, wpack, bias, residual, (T*)y, nullptr, N, D, H, W, act, alpha, algo, stream);
+    }
+    FDN_REQUIRE(residual == nullptr, "%s: residual only on the 64->64 path", who);
+    if (Cin == 3 && Cout == 64 && K == 3) {
+        FDN_REQUIRE(w && ldy == 64 && y_coff == 0, "%s(3->64): needs w, dense output", who);
+        return fdn_conv_cin3_fwd_launch<T>(x, w, bias, (T*)y, N, D, H, W, act, alpha, s);
+    }
+    if (Cin == 64 && Cout == 1 && K == 3) {
+        FDN_REQUIRE(w && ldy >= 1 && y_coff >= 0 && y_coff < ldy, "%s(64->1): bad w/ldy/y_coff", who);
+        return fdn_conv_cout1_fwd_launch<T>(x, w, bias, (float*)y, N, D, H, W, ldy, y_coff, act, alpha, s);
+    }
+    if (Cin == 128 && Cout == 64 && K == 1) {
+        FDN_REQUIRE(w && x2 && ldy == 64 && y_coff == 0, "%s(1x1 128->64): needs w, x2, dense output", who);
+        return fdn_conv1x1_fwd_launch<T>(x, x2, w, bias, (T*)y, (int64_t)N * D * H * W, act, alpha, s);
+    }
+    fdn_set_error("%s: unsupported (Cin=%d,Cout=%d,K=%d)", who, Cin, Cout, K);
+    return FDN_ERR_UNSUPPORTED;
+}
 extern "C" int fdn_conv3d_fwd(const float* x, const float* x2, const float* w, const float* wpack, const float* bias,
                               const float* residual, float* y, int N, int D, int H, int W, int Cin, int Cout, int K,
                               int ldy, int y_coff, int act, float alpha, int algo, void* stream) {
-    FDN_REQUIRE(x && y, "fdn_conv3d_fwd: x/y is NULL");
-    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "fdn_conv3d_fwd: bad algo %d", algo);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_conv3d_fwd: bad dims N=%d D=%d H=%d W=%d", N, D, H, W);
-    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "fdn_conv3d_fwd: bad act %d", act);
-    hipStream_t s = (hipStream_t)stream;
-    if (Cin == 64 && Cout == 64 && K == 3) {
-        FDN_REQUIRE(wpack, "fdn_conv3d_fwd: the 64->64 MFMA path needs wpack (fdn_pack_conv64_weights)");
-        FDN_REQUIRE(ldy == 64 && y_coff == 0, "fdn_conv3d_fwd: 64->64 path writes dense rows (ldy=64,y_coff=0)");
-        FDN_REQUIRE(D <= 1022 && H <= 1022 && W <= 1022, "fdn_conv3d_fwd: dims too large");
-        FdnConv64Call c = conv64_call(FDN_CONV64_FWD, x, wpack, y, N, D, H, W, act, alpha, stream);
-        c.bias = bias; c.residual = residual;
-        return fdn_conv64_launch_ex(c, 3, algo);
-    }
-    FDN_REQUIRE(residual == nullptr, "fdn_conv3d_fwd: residual only on the 64->64 path");
-    if (Cin == 3 && Cout == 64 && K == 3) {
-        FDN_REQUIRE(w && ldy == 64 && y_coff == 0, "fdn_conv3d_fwd(3->64): needs w, dense output");
-        return fdn_conv_cin3_fwd_launch(x, w, bias, y, N, D, H, W, act, alpha, s);
-    }
-    if (Cin == 64 && Cout == 1 && K == 3) {
-        FDN_REQUIRE(w && ldy >= 1 && y_coff >= 0 && y_coff < ldy, "fdn_conv3d_fwd(64->1): bad w/ldy/y_coff");
-        return fdn_conv_cout1_fwd_launch(x, w, bias, y, N, D, H, W, ldy, y_coff, act, alpha, s);
-    }
-    if (Cin == 128 && Cout == 64 && K == 1) {
-        FDN_REQUIRE(w && x2 && ldy == 64 && y_coff == 0, "fdn_conv3d_fwd(1x1 128->64): needs w, x2, dense output");
-        return fdn_conv1x1_fwd_launch(x, x2, w, bias, y, (int64_t)N * D * H * W, act, alpha, s);
-    }
-    fdn_set_error("fdn_conv3d_fwd: unsupported (Cin=%d,Cout=%d,K=%d)", Cin, Cout, K);
-    return FDN_ERR_UNSUPPORTED;
+    return conv3d_fwd<float>("fdn_conv3d_fwd", x, x2, w, wpack, bias, residual, y, N, D, H, W, Cin, Cout, K, ldy, y_coff, act, alpha, algo, stream);
+}
+extern "C" int fdn_conv3d_fwd_bf16(const uint16_t* x, const uint16_t* x2, const float* w, const uint16_t* wpack,
+                                   const float* bias, const uint16_t* residual, void* y, int N, int D, int H, int W, int Cin,
+                                   int Cout, int K, int ldy, int y_coff, int act, float alpha, void* stream) {
+    return conv3d_fwd<uint16_t>("fdn_conv3d_fwd_bf16", x, x2, w, wpack, bias, residual, y, N, D, H, W, Cin, Cout, K, ldy, y_coff, act, alpha,
+                                FDN_ALGO_AUTO, stream);
 }
 
 extern "C" int fdn_conv3d_dgrad(const float* dz, const float* w, const float* wpack, float* dxpad, int N, int D,
@@ -170,7 +201,9 @@ extern "C" int fdn_conv3d_dgrad(const float* dz, const float* w, const float* wp
         FDN_REQUIRE(wpack, "fdn_conv3d_dgrad: the 64->64 MFMA path needs wpack = wp_dgrad");
         FDN_REQUIRE(lddz == 64 && dz_coff == 0, "fdn_conv3d_dgrad: 64->64 path reads dense rows");
         FDN_REQUIRE(D <= 1020 && H <= 1020 && W <= 1020, "fdn_conv3d_dgrad: dims too large");
-        return fdn_conv64_launch_ex(conv64_call(FDN_CONV64_DGRAD, dz, wpack, dxpad, N, D, H, W, FDN_ACT_NONE, 0.f, stream), 3, algo);
+        FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD, dz, wpack, N, D, H, W, FDN_ACT_NONE, 0.f, stream);
+        c.y = dxpad;
+        return fdn_conv64_launch_ex(c, 3, algo);
     }
     if (Cin == 64 && Cout == 1 && K == 3) {
         FDN_REQUIRE(w, "fdn_conv3d_dgrad(64->1): needs w");
@@ -185,8 +218,8 @@ extern "C" int fdn_conv3d_dgrad_fused(const float* dz, const float* wpack, float
                                       int W, int algo, void* stream) {
     FDN_REQUIRE(dz && wpack && dxpad && dz_prev, "fdn_conv3d_dgrad_fused: NULL argument");
     if (int rc = conv64_check("fdn_conv3d_dgrad_fused", algo, N, D, H, W, act)) return rc;
-    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz, wpack, dxpad, N, D, H, W, act, alpha, stream);
-    c.fskip = skip; c.fy = y_prev; c.fout = dz_prev;
+    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz, wpack, N, D, H, W, act, alpha, stream);
+    c.y = dxpad; c.fskip = skip; c.fy = y_prev; c.fout = dz_prev;
     return fdn_conv64_launch_ex(c, 3, algo);
 }
 
@@ -195,17 +228,15 @@ extern "C" int fdn_conv64_fwd_mask(const float* x, const float* wpack, const flo
                                    int N, int D, int H, int W, int act, float alpha, int algo, void* stream) {
     FDN_REQUIRE(x && wpack && y && y_mask, "fdn_conv64_fwd_mask: NULL argument");
     if (int rc = conv64_check("fdn_conv64_fwd_mask", algo, N, D, H, W, act)) return rc;
-    FdnConv64Call c = conv64_call(FDN_CONV64_FWD, x, wpack, y, N, D, H, W, act, alpha, stream);
-    c.bias = bias; c.residual = residual; c.ymask = y_mask;
-    return fdn_conv64_launch_ex(c, 3, algo);
+    return conv64_fwd_launch(x, wpack, bias, residual, y, y_mask, N, D, H, W, act, alpha, algo, stream);
 }
 
 extern "C" int fdn_conv64_dgrad_fused_mask(const float* dz, const float* wpack, float* dxpad, const float* skip, const uint16_t* y_mask,
                                            int act, float alpha, float* dz_prev, int N, int D, int H, int W, int algo, void* stream) {
     FDN_REQUIRE(dz && wpack && dxpad && dz_prev && y_mask, "fdn_conv64_dgrad_fused_mask: NULL argument");
     if (int rc = conv64_check("fdn_conv64_dgrad_fused_mask", algo, N, D, H, W, act, true)) return rc;
-    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz, wpack, dxpad, N, D, H, W, act, alpha, stream);
-    c.fskip = skip; c.fmask = y_mask; c.fout = dz_prev;
+    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz, wpack, N, D, H, W, act, alpha, stream);
+    c.y = dxpad; c.fskip = skip; c.fmask = y_mask; c.fout = dz_prev;
     return fdn_conv64_launch_ex(c, 3, algo);
 }
 
@@ -222,8 +253,8 @@ extern "C" int fdn_conv64_dgrad_fused_multi(const float* const* dz, const float*
     for (int i = 0; i < nsrc; ++i) FDN_REQUIRE(dz[i] && wpack[i], "fdn_conv64_dgrad_fused_multi: NULL pointer for source %d", i);
     for (int i = 1; i < nsrc; ++i)
         for (int j = i; j > 0 && wpack[ord[j]] < wpack[ord[j - 1]]; --j) { const int t = ord[j]; ord[j] = ord[j - 1]; ord[j - 1] = t; }
-    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz[ord[0]], wpack[ord[0]], dxpad, N, D, H, W, act, alpha, stream);
-    c.fskip = skip; c.fy = y_prev; c.fmask = y_mask; c.fout = dz_prev; c.nsrc = nsrc;
+    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz[ord[0]], wpack[ord[0]], N, D, H, W, act, alpha, stream);
+    c.y = dxpad; c.fskip = skip; c.fy = y_prev; c.fmask = y_mask; c.fout = dz_prev; c.nsrc = nsrc;
     for (int i = 1; i < nsrc; ++i) {
         const long long d = (long long)(wpack[ord[i]] - wpack[ord[0]]) * (long long)sizeof(float);
         FDN_REQUIRE(d >= 0 && d < (1ll << 30), "fdn_conv64_dgrad_fused_multi: the packs of the sources must lie within 1 GiB of each other (one fdn_pack_conv64_weights_batch buffer)");
@@ -238,95 +269,258 @@ extern "C" int fdn_conv3d_dgrad_fused_part(const float* dz, const float* wpack, 
     FDN_REQUIRE(dz && wpack && dxpad && dz_prev, "fdn_conv3d_dgrad_fused_part: NULL argument");
     if (int rc = conv64_check("fdn_conv3d_dgrad_fused_part", algo, N, D, H, W, act)) return rc;
     FDN_REQUIRE(parts >= 1 && parts <= 3, "fdn_conv3d_dgrad_fused_part: parts must be FDN_DGRAD_INNER | FDN_DGRAD_SHELL");
-    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz, wpack, dxpad, N, D, H, W, act, alpha, stream);
-    c.fskip = skip; c.fy = y_prev; c.fout = dz_prev;
+    FdnConv64Call c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz, wpack, N, D, H, W, act, alpha, stream);
+    c.y = dxpad; c.fskip = skip; c.fy = y_prev; c.fout = dz_prev;
     return fdn_conv64_launch_ex(c, parts, algo);
 }
 
+// ---- the bf16 64->64 entry points.  Unlike the fp32 ones they allow a NULL mask with any act (one entry point takes y_prev and the
+// mask), refuse a mask with FDN_ACT_NONE, and hand the sources of a multi-source dgrad over as given ----
+static int conv64_fwd_bf16(const char* who, const uint16_t* x, const uint16_t* wpack, const float* bias, const uint16_t* residual, uint16_t* y,
+                           uint16_t* y_mask, int N, int D, int H, int W, int act, float alpha, void* stream) {
+    FDN_REQUIRE(x && wpack && y, "%s: NULL argument", who);
+    if (int rc = conv64_check(who, FDN_ALGO_AUTO, N, D, H, W, act, false, 1022)) return rc;
+    return conv64_fwd_launch(x, wpack, bias, residual, y, y_mask, N, D, H, W, act, alpha, FDN_ALGO_AUTO, stream);
+}
+extern "C" int fdn_conv64_fwd_bf16_mask(const uint16_t* x, const uint16_t* wpack, const float* bias, const uint16_t* residual,
+                                        uint16_t* y, uint16_t* y_mask, int N, int D, int H, int W, int act, float alpha, void* stream) {
+    return conv64_fwd_bf16("fdn_conv64_fwd_bf16_mask", x, wpack, bias, residual, y, y_mask, N, D, H, W, act, alpha, stream);
+}
+extern "C" int fdn_conv64_fwd_bf16(const uint16_t* x, const uint16_t* wpack, const float* bias, const uint16_t* residual,
+                                   uint16_t* y, int N, int D, int H, int W, int act, float alpha, void* stream) {
+    return conv64_fwd_bf16("fdn_conv64_fwd_bf16", x, wpack, bias, residual, y, nullptr, N, D, H, W, act, alpha, stream);
+}
+
+// the fused dgrad of nsrc = 1..3 sources: the single-source entry points are tables of one
+static int conv64_dgrad_fused_bf16(const char* who, const uint16_t* const* dz, const uint16_t* const* wpack, int nsrc, float* dxpad,
+                                   const uint16_t* skip, const uint16_t* y_prev, const uint16_t* y_mask, int act, float alpha,
+                                   uint16_t* dz_prev, int N, int D, int H, int W, void* stream) {
+    FDN_REQUIRE(dz && wpack && dxpad && dz_prev && nsrc >= 1 && nsrc <= 3, "%s: NULL argument or nsrc outside 1..3", who);
+    if (int rc = conv64_check(who, FDN_ALGO_AUTO, N, D, H, W, act)) return rc;
+    FDN_REQUIRE(!(y_mask && act == FDN_ACT_NONE), "%s: a sign mask needs act = RELU or LEAKY", who);
+    for (int i = 0; i < nsrc; ++i) FDN_REQUIRE(dz[i] && wpack[i], "%s: NULL pointer for source %d", who, i);
+    FdnConv64BfCall c = conv64_call(FDN_CONV64_DGRAD_FUSED, dz[0], wpack[0], N, D, H, W, act, alpha, stream);
+    c.ypad = dxpad; c.fskip = skip; c.fy = y_prev; c.fmask = y_mask; c.fout = dz_prev; c.nsrc = nsrc;
+    if (nsrc > 1) { c.x1 = dz[1]; c.wp1 = wpack[1]; }
+    if (nsrc > 2) { c.x2 = dz[2]; c.wp2 = wpack[2]; }
+    return fdn_conv64_bf16_launch(c);
+}
+extern "C" int fdn_conv64_dgrad_fused_bf16_mask(const uint16_t* dz, const uint16_t* wpack, float* dxpad, const uint16_t* skip,
+                                                const uint16_t* y_prev, const uint16_t* y_mask, int act, float alpha,
+                                                uint16_t* dz_prev, int N, int D, int H, int W, void* stream) {
+    return conv64_dgrad_fused_bf16("fdn_conv64_dgrad_fused_bf16_mask", &dz, &wpack, 1, dxpad, skip, y_prev, y_mask, act, alpha, dz_prev, N, D, H, W, stream);
+}
+extern "C" int fdn_conv64_dgrad_fused_bf16(const uint16_t* dz, const uint16_t* wpack, float* dxpad, const uint16_t* skip,
+                                           const uint16_t* y_prev, int act, float alpha, uint16_t* dz_prev, int N, int D,
+                                           int H, int W, void* stream) {
+    return conv64_dgrad_fused_bf16("fdn_conv64_dgrad_fused_bf16", &dz, &wpack, 1, dxpad, skip, y_prev, nullptr, act, alpha, dz_prev, N, D, H, W, stream);
+}
+extern "C" int fdn_conv64_dgrad_fused_bf16_multi(const uint16_t* const* dz, const uint16_t* const* wpack, int nsrc, float* dxpad,
+                                                 const uint16_t* skip, const uint16_t* y_prev, const uint16_t* y_mask, int act, float alpha,
+                                                 uint16_t* dz_prev, int N, int D, int H, int W, void* stream) {
+    return conv64_dgrad_fused_bf16("fdn_conv64_dgrad_fused_bf16_multi", dz, wpack, nsrc, dxpad, skip, y_prev, y_mask, act, alpha, dz_prev, N, D, H, W, stream);
+}
+
+// ---- the thin operators ----
+template <typename T>
+static int fold_halo_border(const char* who, const float* dxpad0, const float* dxpad1, const float* dxpad2, int nsrc, const T* skip,
+                            const T* y_prev, int act, float alpha, T* dz_prev, int N, int D, int H, int W, void* stream) {
+    FDN_REQUIRE(dxpad0 && dz_prev, "%s: NULL argument", who);
+    FDN_REQUIRE(nsrc >= 1 && nsrc <= 3 && (nsrc < 2 || dxpad1) && (nsrc < 3 || dxpad2), "%s: bad nsrc %d", who, nsrc);
+    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "%s: bad dims", who);
+    return fdn_fold_halo_border_launch(dxpad0, dxpad1, dxpad2, nsrc, skip, y_prev, act, alpha, dz_prev, N, D, H, W, (hipStream_t)stream);
+}
 extern "C" int fdn_fold_halo_border(const float* dxpad0, const float* dxpad1, const float* dxpad2, int nsrc,
                                     const float* skip, const float* y_prev, int act, float alpha, float* dz_prev, int N,
                                     int D, int H, int W, void* stream) {
-    FDN_REQUIRE(dxpad0 && dz_prev, "fdn_fold_halo_border: NULL argument");
-    FDN_REQUIRE(nsrc >= 1 && nsrc <= 3 && (nsrc < 2 || dxpad1) && (nsrc < 3 || dxpad2), "fdn_fold_halo_border: bad nsrc %d", nsrc);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_fold_halo_border: bad dims");
-    return fdn_fold_halo_border_launch(dxpad0, dxpad1, dxpad2, nsrc, skip, y_prev, act, alpha, dz_prev, N, D, H, W,
-                                       (hipStream_t)stream);
+    return fold_halo_border<float>("fdn_fold_halo_border", dxpad0, dxpad1, dxpad2, nsrc, skip, y_prev, act, alpha, dz_prev, N, D, H, W, stream);
+}
+extern "C" int fdn_fold_halo_border_bf16(const float* dxpad0, const float* dxpad1, const float* dxpad2, int nsrc,
+                                         const uint16_t* skip, const uint16_t* y_prev, int act, float alpha,
+                                         uint16_t* dz_prev, int N, int D, int H, int W, void* stream) {
+    return fold_halo_border<uint16_t>("fdn_fold_halo_border_bf16", dxpad0, dxpad1, dxpad2, nsrc, skip, y_prev, act, alpha, dz_prev, N, D, H, W, stream);
 }
 
+template <typename T>
+static int conv1x1_dgrad(const char* who, const T* dz, const float* w, const T* ya, const T* yb, T* dxa, T* dxb, int64_t nvox, void* stream) {
+    FDN_REQUIRE(dz && w && ya && yb && dxa && dxb && nvox > 0, "%s: NULL argument or nvox<=0", who);
+    return fdn_conv1x1_dgrad_launch<T>(dz, w, ya, yb, dxa, dxb, nvox, (hipStream_t)stream);
+}
+extern "C" int fdn_conv1x1_dgrad(const float* dz, const float* w, const float* ya, const float* yb, float* dxa, float* dxb,
+                                 int64_t nvox, void* stream) {
+    return conv1x1_dgrad<float>("fdn_conv1x1_dgrad", dz, w, ya, yb, dxa, dxb, nvox, stream);
+}
+extern "C" int fdn_conv1x1_dgrad_bf16(const uint16_t* dz, const float* w, const uint16_t* ya, const uint16_t* yb,
+                                      uint16_t* dxa, uint16_t* dxb, int64_t nvox, void* stream) {
+    return conv1x1_dgrad<uint16_t>("fdn_conv1x1_dgrad_bf16", dz, w, ya, yb, dxa, dxb, nvox, stream);
+}
+
+// The head's dgrad with the fold: act' from y_prev or from its sign mask.  fp32 has an entry point for either (mask_form: the mask
+// and its activation are required), bf16 one that takes both pointers.  The launcher checks the operands and the workspace under `who`.
+template <typename T>
+static int conv_cout1_dgrad_folded(const char* who, bool mask_form, const float* dz, const float* w, const T* y_prev, const uint16_t* y_mask,
+                                   int act, float alpha, T* dz_prev, float* dbias_prev, void* workspace, size_t workspace_bytes, int N,
+                                   int D, int H, int W, int lddz, int dz_coff, void* stream) {
+    if (mask_form) FDN_REQUIRE(y_mask && (act == FDN_ACT_RELU || act == FDN_ACT_LEAKY), "%s: a sign mask and act = RELU or LEAKY", who);
+    else FDN_REQUIRE(!(y_mask && act == FDN_ACT_NONE), "%s: a sign mask needs act = RELU or LEAKY", who);
+    return fdn_conv_cout1_dgrad_folded_launch<T>(who, dz, w, y_prev, act, alpha, dz_prev, dbias_prev, workspace, workspace_bytes, N, D, H, W,
+                                                 lddz, dz_coff, (hipStream_t)stream, y_mask);
+}
+extern "C" int fdn_conv_cout1_dgrad_folded(const float* dz, const float* w, const float* y_prev, int act, float alpha,
+                                           float* dz_prev, float* dbias_prev, void* workspace, size_t workspace_bytes, int N,
+                                           int D, int H, int W, int lddz, int dz_coff, void* stream) {
+    return conv_cout1_dgrad_folded<float>("fdn_conv_cout1_dgrad_folded", false, dz, w, y_prev, nullptr, act, alpha, dz_prev, dbias_prev, workspace,
+                                          workspace_bytes, N, D, H, W, lddz, dz_coff, stream);
+}
+extern "C" int fdn_conv_cout1_dgrad_folded_mask(const float* dz, const float* w, const uint16_t* y_mask, int act, float alpha,
+                                                float* dz_prev, float* dbias_prev, void* workspace, size_t workspace_bytes, int N,
+                                                int D, int H, int W, int lddz, int dz_coff, void* stream) {
+    return conv_cout1_dgrad_folded<float>("fdn_conv_cout1_dgrad_folded_mask", true, dz, w, nullptr, y_mask, act, alpha, dz_prev, dbias_prev,
+                                          workspace, workspace_bytes, N, D, H, W, lddz, dz_coff, stream);
+}
+extern "C" int fdn_conv_cout1_dgrad_folded_bf16_mask(const float* dz, const float* w, const uint16_t* y_prev, const uint16_t* y_mask,
+                                                     int act, float alpha, uint16_t* dz_prev, float* dbias_prev, void* workspace,
+                                                     size_t workspace_bytes, int N, int D, int H, int W, int lddz, int dz_coff,
+                                                     void* stream) {
+    return conv_cout1_dgrad_folded<uint16_t>("fdn_conv_cout1_dgrad_folded_bf16_mask", false, dz, w, y_prev, y_mask, act, alpha, dz_prev, dbias_prev,
+                                             workspace, workspace_bytes, N, D, H, W, lddz, dz_coff, stream);
+}
+extern "C" int fdn_conv_cout1_dgrad_folded_bf16(const float* dz, const float* w, const uint16_t* y_prev, int act, float alpha,
+                                                uint16_t* dz_prev, float* dbias_prev, void* workspace, size_t workspace_bytes,
+                                                int N, int D, int H, int W, int lddz, int dz_coff, void* stream) {
+    return conv_cout1_dgrad_folded<uint16_t>("fdn_conv_cout1_dgrad_folded_bf16", false, dz, w, y_prev, nullptr, act, alpha, dz_prev, dbias_prev,
+                                             workspace, workspace_bytes, N, D, H, W, lddz, dz_coff, stream);
+}
+
+// ---- weight gradients ----
+// The 64->64 kernel of a storage type.  fp32: Winograd F(3,4) along W (wgrad64_wino.hip), half the multiplies of the direct kernel,
+// which FDN_ALGO_DIRECT selects -- the workspace serves either; bf16: one kernel
+static int wgrad64_launch(const float* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H, int W, int algo, hipStream_t s) {
+    return (fdn_wgrad64_force_direct || algo == FDN_ALGO_DIRECT) ? fdn_wgrad64_launch(x, dz, dw, ws, ws_bytes, N, D, H, W, s)
+                                                                 : fdn_wgrad64_wino_launch(x, dz, dw, ws, ws_bytes, N, D, H, W, s, algo);
+}
+static int wgrad64_launch(const uint16_t* x, const uint16_t* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H, int W, int, hipStream_t s) {
+    return fdn_wgrad64_bf16_launch(x, dz, dw, ws, ws_bytes, N, D, H, W, s);
+}
+template <typename T>
+static size_t conv3d_wgrad_workspace_bytes(int N, int D, int H, int W, int Cin, int Cout, int K) {
+    if (!(Cin == 64 && Cout == 64 && K == 3)) return fdn_small_wgrad_workspace_bytes(Cin, Cout, K);
+    if constexpr (kBf16<T>) return fdn_wgrad64_bf16_workspace_bytes(N, D, H, W);
+    else return std::max(fdn_wgrad64_workspace_bytes(N, D, H, W), fdn_wgrad64_wino_workspace_bytes(N, D, H, W));
+}
 extern "C" size_t fdn_conv3d_wgrad_workspace_bytes(int N, int D, int H, int W, int Cin, int Cout, int K) {
-    if (Cin == 64 && Cout == 64 && K == 3) {
-        const size_t wd = fdn_wgrad64_workspace_bytes(N, D, H, W), ww = fdn_wgrad64_wino_workspace_bytes(N, D, H, W);
-        return wd > ww ? wd : ww;
-    }
-    return fdn_small_wgrad_workspace_bytes(Cin, Cout, K);
+    return conv3d_wgrad_workspace_bytes<float>(N, D, H, W, Cin, Cout, K);
+}
+extern "C" size_t fdn_conv3d_wgrad_bf16_workspace_bytes(int N, int D, int H, int W, int Cin, int Cout, int K) {
+    return conv3d_wgrad_workspace_bytes<uint16_t>(N, D, H, W, Cin, Cout, K);
 }
 
-extern "C" int fdn_conv3d_wgrad(const float* x, const float* x2, const float* dz, float* dw, float* dbias,
-                                void* workspace, size_t workspace_bytes, int N, int D, int H, int W, int Cin, int Cout,
-                                int K, int lddz, int dz_coff, int algo, void* stream) {
-    FDN_REQUIRE(x && dz && dw, "fdn_conv3d_wgrad: x/dz/dw is NULL");
-    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "fdn_conv3d_wgrad: bad algo %d", algo);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_conv3d_wgrad: bad dims");
-    const size_t need = fdn_conv3d_wgrad_workspace_bytes(N, D, H, W, Cin, Cout, K);
+// dz: T rows, except the heads' (Cout == 1) fp32 prediction gradient in both modes
+template <typename T>
+static int conv3d_wgrad(const char* who, const T* x, const T* x2, const void* dz, float* dw, float* dbias, void* workspace,
+                        size_t workspace_bytes, int N, int D, int H, int W, int Cin, int Cout, int K, int lddz, int dz_coff, int algo,
+                        void* stream) {
+    FDN_REQUIRE(x && dz && dw, "%s: x/dz/dw is NULL", who);
+    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "%s: bad algo %d", who, algo);
+    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "%s: bad dims", who);
+    const size_t need = conv3d_wgrad_workspace_bytes<T>(N, D, H, W, Cin, Cout, K);
     if (workspace_bytes < need || (need && !workspace)) {
-        fdn_set_error("fdn_conv3d_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
+        fdn_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
         return FDN_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
     const int64_t nvox = (int64_t)N * D * H * W;
+    const T* dzt = (const T*)dz;
     int rc;
+    if (Cin == 64 && Cout == 1 && K == 3) {
+        const float* dzf = (const float*)dz;
+        rc = fdn_wgrad_cout1_launch<T>(x, dzf, dw, workspace, workspace_bytes, N, D, H, W, lddz, dz_coff, s);
+        if (rc != FDN_OK || !dbias) return rc;
+        return fdn_bias_grad_launch<float>(dzf, dbias, workspace, workspace_bytes, nvox, 1, lddz, dz_coff, s);
+    }
     if (Cin == 64 && Cout == 64 && K == 3) {
-        FDN_REQUIRE(lddz == 64 && dz_coff == 0, "fdn_conv3d_wgrad: 64->64 path reads dense dz rows");
-        // Winograd F(3,4) along W (wgrad64_wino.hip): half the multiplies of the direct kernel, which FDN_ALGO_DIRECT selects
-        rc = (fdn_wgrad64_force_direct || algo == FDN_ALGO_DIRECT)
-                 ? fdn_wgrad64_launch(x, dz, dw, workspace, workspace_bytes, N, D, H, W, s)
-                 : fdn_wgrad64_wino_launch(x, dz, dw, workspace, workspace_bytes, N, D, H, W, s, algo);
+        FDN_REQUIRE(lddz == 64 && dz_coff == 0, "%s: 64->64 path reads dense dz rows", who);
+        rc = wgrad64_launch(x, dzt, dw, workspace, workspace_bytes, N, D, H, W, algo, s);
     } else if (Cin == 3 && Cout == 64 && K == 3) {
-        FDN_REQUIRE(lddz == 64 && dz_coff == 0, "fdn_conv3d_wgrad(3->64): dense dz rows");
-        rc = fdn_wgrad_cin3_launch(x, dz, dw, workspace, workspace_bytes, N, D, H, W, s);
-    } else if (Cin == 64 && Cout == 1 && K == 3) {
-        rc = fdn_wgrad_cout1_launch(x, dz, dw, workspace, workspace_bytes, N, D, H, W, lddz, dz_coff, s);
+        FDN_REQUIRE(lddz == 64 && dz_coff == 0, "%s(3->64): dense dz rows", who);
+        rc = fdn_wgrad_cin3_launch<T>(x, dzt, dw, workspace, workspace_bytes, N, D, H, W, s);
     } else if (Cin == 128 && Cout == 64 && K == 1) {
-        FDN_REQUIRE(x2 && lddz == 64 && dz_coff == 0, "fdn_conv3d_wgrad(1x1): needs x2, dense dz rows");
-        rc = fdn_wgrad_1x1_launch(x, x2, dz, dw, workspace, workspace_bytes, nvox, s);
+        FDN_REQUIRE(x2 && lddz == 64 && dz_coff == 0, "%s(1x1): needs x2, dense dz rows", who);
+        rc = fdn_wgrad_1x1_launch<T>(x, x2, dzt, dw, workspace, workspace_bytes, nvox, s);
     } else {
-        fdn_set_error("fdn_conv3d_wgrad: unsupported (Cin=%d,Cout=%d,K=%d)", Cin, Cout, K);
+        fdn_set_error("%s: unsupported (Cin=%d,Cout=%d,K=%d)", who, Cin, Cout, K);
         return FDN_ERR_UNSUPPORTED;
     }
-    if (rc != FDN_OK) return rc;
-    if (dbias) return fdn_bias_grad_launch(dz, dbias, workspace, workspace_bytes, nvox, Cout, lddz, dz_coff, s);
-    return FDN_OK;
+    if (rc != FDN_OK || !dbias) return rc;
+    return fdn_bias_grad_launch<T>(dzt, dbias, workspace, workspace_bytes, nvox, Cout, lddz, dz_coff, s);
+}
+extern "C" int fdn_conv3d_wgrad(const float* x, const float* x2, const float* dz, float* dw, float* dbias,
+                                void* workspace, size_t workspace_bytes, int N, int D, int H, int W, int Cin, int Cout,
+                                int K, int lddz, int dz_coff, int algo, void* stream) {
+    return conv3d_wgrad<float>("fdn_conv3d_wgrad", x, x2, dz, dw, dbias, workspace, workspace_bytes, N, D, H, W, Cin, Cout, K, lddz, dz_coff, algo, stream);
+}
+extern "C" int fdn_conv3d_wgrad_bf16(const uint16_t* x, const uint16_t* x2, const void* dz, float* dw, float* dbias,
+                                     void* workspace, size_t workspace_bytes, int N, int D, int H, int W, int Cin, int Cout,
+                                     int K, int lddz, int dz_coff, void* stream) {
+    return conv3d_wgrad<uint16_t>("fdn_conv3d_wgrad_bf16", x, x2, dz, dw, dbias, workspace, workspace_bytes, N, D, H, W, Cin, Cout, K, lddz, dz_coff,
+                                  FDN_ALGO_AUTO, stream);
 }
 
 // Weight gradients of n_layers 64->64 3x3x3 layers that share one grid, in ONE launch (+ one reduction launch) where the kernel allows
-// it (W % 4 == 0, even D, FDN_ALGO_AUTO / _WINO_H2), else layer by layer through fdn_conv3d_wgrad's path.  The batched kernel gives
-// every layer 64 / n_layers splits of the voxel sum where the single-layer launch uses 63: equal to fp32 rounding, not bit for bit.
+// it, else layer by layer through conv3d_wgrad.  fp32: W % 4 == 0, even D, FDN_ALGO_AUTO / _WINO_H2; the batched kernel gives every
+// layer 64 / n_layers splits of the voxel sum where the single-layer launch uses 63: equal to fp32 rounding, not bit for bit.  bf16:
+// fdn_wgrad64_bf16_batch_ok.
 static bool wgrad_batchable(int n_layers, int D, int W, int algo) {
     return !fdn_wgrad64_force_direct && (W & 3) == 0 && fdn_wgrad64_wino_batch_ok(n_layers, D, algo);
 }
-extern "C" size_t fdn_conv3d_wgrad_batch_workspace_bytes(int n_layers, int N, int D, int H, int W) {
+template <typename T>
+static size_t conv3d_wgrad_batch_workspace_bytes(int n_layers, int N, int D, int H, int W) {
     if (n_layers <= 0 || N <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t one = fdn_conv3d_wgrad_workspace_bytes(N, D, H, W, 64, 64, 3);
-    size_t all = 0;                       // (the batch may go out in chunks of fewer layers with more splits each: fdn_conv3d_wgrad_batch)
-    if (wgrad_batchable(n_layers, D, W, FDN_ALGO_AUTO))
-        for (int c = 2; c <= n_layers; ++c) {
+    const size_t one = conv3d_wgrad_workspace_bytes<T>(N, D, H, W, 64, 64, 3);
+    size_t all = 0;
+    if constexpr (kBf16<T>) {
+        if (fdn_wgrad64_bf16_batch_ok(n_layers, N, D, H, W)) all = fdn_wgrad64_bf16_batch_workspace_bytes(n_layers, N, D, H, W);
+    } else if (wgrad_batchable(n_layers, D, W, FDN_ALGO_AUTO)) {
+        for (int c = 2; c <= n_layers; ++c) {          // (the batch may go out in chunks of fewer layers with more splits each: conv3d_wgrad_batch)
             const size_t b = fdn_wgrad64_wino_batch_workspace_bytes(c, N, D, H, W);
             if (b > all) all = b;
         }
+    }
     return all > one ? all : one;
 }
-extern "C" int fdn_conv3d_wgrad_batch(const float* const* x, const float* const* dz, float* const* dw, float* const* dbias, int n_layers,
-                                      void* workspace, size_t workspace_bytes, int N, int D, int H, int W, int algo, void* stream) {
-    FDN_REQUIRE(x && dz && dw && n_layers > 0, "fdn_conv3d_wgrad_batch: NULL table or n_layers <= 0");
-    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "fdn_conv3d_wgrad_batch: bad algo %d", algo);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_conv3d_wgrad_batch: bad dims");
-    const size_t need = fdn_conv3d_wgrad_batch_workspace_bytes(n_layers, N, D, H, W);
+extern "C" size_t fdn_conv3d_wgrad_batch_workspace_bytes(int n_layers, int N, int D, int H, int W) {
+    return conv3d_wgrad_batch_workspace_bytes<float>(n_layers, N, D, H, W);
+}
+extern "C" size_t fdn_conv3d_wgrad_bf16_batch_workspace_bytes(int n_layers, int N, int D, int H, int W) {
+    return conv3d_wgrad_batch_workspace_bytes<uint16_t>(n_layers, N, D, H, W);
+}
+
+template <typename T>
+static int conv3d_wgrad_batch(const char* who, const T* const* x, const T* const* dz, float* const* dw, float* const* dbias, int n_layers,
+                              void* workspace, size_t workspace_bytes, int N, int D, int H, int W, int algo, void* stream) {
+    FDN_REQUIRE(x && dz && dw && n_layers > 0, "%s: NULL table or n_layers <= 0", who);
+    FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "%s: bad algo %d", who, algo);
+    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "%s: bad dims", who);
+    const size_t need = conv3d_wgrad_batch_workspace_bytes<T>(n_layers, N, D, H, W);
     if (workspace_bytes < need || !workspace) {
-        fdn_set_error("fdn_conv3d_wgrad_batch: workspace %zu < %zu bytes", workspace_bytes, need);
+        fdn_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
         return FDN_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (wgrad_batchable(n_layers, D, W, algo)) {
+    auto single = [&](int i) {
+        return conv3d_wgrad<T>(who, x[i], nullptr, dz[i], dw[i], nullptr, workspace, workspace_bytes, N, D, H, W, 64, 64, 3, 64, 0, algo, stream);
+    };
+    bool batched;
+    if constexpr (kBf16<T>) batched = fdn_wgrad64_bf16_batch_ok(n_layers, N, D, H, W);
+    else batched = wgrad_batchable(n_layers, D, W, algo);
+    if (!batched) {
+        for (int i = 0; i < n_layers; ++i) {
+            FDN_REQUIRE(x[i] && dz[i] && dw[i], "%s: NULL pointer for layer %d", who, i);
+            if (int rc = single(i)) return rc;
+        }
+    } else if constexpr (kBf16<T>) {
+        if (int rc = fdn_wgrad64_bf16_batch_launch(x, dz, dw, n_layers, workspace, workspace_bytes, N, D, H, W, s)) return rc;
+    } else {
         // The batched kernel gives every layer 64 / n splits x 4 coordinates: n = 11 fills 220 of the 256 CUs.  Such a batch goes out in
         // chunks that fill the chip (>= 63 of 64 split slots: 1, 2, 3, 4, 7, 8, 9, 16 layers), a batch at >= 15/16 as it is.
         auto fill64 = [](int c) { return (64 / c) * c; };
@@ -335,219 +529,22 @@ extern "C" int fdn_conv3d_wgrad_batch(const float* const* x, const float* const*
             int c = rem;
             if (fill64(rem) < 60) { c = rem - 1; while (c > 1 && fill64(c) < 63) --c; }
             if (c >= 2) { if (int rc = fdn_wgrad64_wino_batch_launch(x + i0, dz + i0, dw + i0, c, workspace, workspace_bytes, N, D, H, W, s)) return rc; }
-            else if (int rc = fdn_conv3d_wgrad(x[i0], nullptr, dz[i0], dw[i0], nullptr, workspace, workspace_bytes, N, D, H, W, 64, 64, 3, 64, 0, algo, stream)) return rc;
+            else if (int rc = single(i0)) return rc;
             i0 += c;
-        }
-    } else {
-        for (int i = 0; i < n_layers; ++i) {
-            FDN_REQUIRE(x[i] && dz[i] && dw[i], "fdn_conv3d_wgrad_batch: NULL pointer for layer %d", i);
-            if (int rc = fdn_conv3d_wgrad(x[i], nullptr, dz[i], dw[i], nullptr, workspace, workspace_bytes, N, D, H, W, 64, 64, 3, 64, 0, algo, stream))
-                return rc;
         }
     }
     if (dbias)                           // (stream-ordered behind the reduction: the workspace is free again)
         for (int i = 0; i < n_layers; ++i)
             if (dbias[i])
-                if (int rc = fdn_bias_grad_launch(dz[i], dbias[i], workspace, workspace_bytes, (int64_t)N * D * H * W, 64, 64, 0, s)) return rc;
+                if (int rc = fdn_bias_grad_launch<T>(dz[i], dbias[i], workspace, workspace_bytes, (int64_t)N * D * H * W, 64, 64, 0, s)) return rc;
     return FDN_OK;
 }
-
-// ---- bf16 activation path ----
-extern "C" int fdn_conv64_fwd_bf16_mask(const uint16_t* x, const uint16_t* wpack, const float* bias, const uint16_t* residual,
-                                        uint16_t* y, uint16_t* y_mask, int N, int D, int H, int W, int act, float alpha, void* stream) {
-    FDN_REQUIRE(x && wpack && y, "fdn_conv64_fwd_bf16: NULL argument");
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= 1022 && H <= 1022 && W <= 1022, "fdn_conv64_fwd_bf16: bad dims");
-    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "fdn_conv64_fwd_bf16: bad act %d", act);
-    return fdn_conv64_bf16_launch(x, wpack, bias, residual, y, nullptr, nullptr, nullptr, nullptr, N, D, H, W, D, H, W, 0, 0,
-                                  act, alpha, (hipStream_t)stream, y_mask, nullptr);
-}
-
-extern "C" int fdn_conv64_fwd_bf16(const uint16_t* x, const uint16_t* wpack, const float* bias, const uint16_t* residual,
-                                   uint16_t* y, int N, int D, int H, int W, int act, float alpha, void* stream) {
-    return fdn_conv64_fwd_bf16_mask(x, wpack, bias, residual, y, nullptr, N, D, H, W, act, alpha, stream);
-}
-
-extern "C" int fdn_conv64_dgrad_fused_bf16_mask(const uint16_t* dz, const uint16_t* wpack, float* dxpad, const uint16_t* skip,
-                                                const uint16_t* y_prev, const uint16_t* y_mask, int act, float alpha,
-                                                uint16_t* dz_prev, int N, int D, int H, int W, void* stream) {
-    FDN_REQUIRE(dz && wpack && dxpad && dz_prev, "fdn_conv64_dgrad_fused_bf16: NULL argument");
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= 1020 && H <= 1020 && W <= 1020, "fdn_conv64_dgrad_fused_bf16: bad dims");
-    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "fdn_conv64_dgrad_fused_bf16: bad act %d", act);
-    FDN_REQUIRE(!(y_mask && act == FDN_ACT_NONE), "fdn_conv64_dgrad_fused_bf16_mask: a sign mask needs act = RELU or LEAKY");
-    return fdn_conv64_bf16_launch(dz, wpack, nullptr, nullptr, nullptr, dxpad, skip, y_prev, dz_prev, N, D, H, W, D + 2, H + 2,
-                                  W + 2, -1, 1, act, alpha, (hipStream_t)stream, nullptr, y_mask);
-}
-
-extern "C" int fdn_conv64_dgrad_fused_bf16_multi(const uint16_t* const* dz, const uint16_t* const* wpack, int nsrc, float* dxpad,
-                                                 const uint16_t* skip, const uint16_t* y_prev, const uint16_t* y_mask, int act, float alpha,
-                                                 uint16_t* dz_prev, int N, int D, int H, int W, void* stream) {
-    FDN_REQUIRE(dz && wpack && dxpad && dz_prev && nsrc >= 1 && nsrc <= 3, "fdn_conv64_dgrad_fused_bf16_multi: NULL argument or nsrc outside 1..3");
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && D <= 1020 && H <= 1020 && W <= 1020, "fdn_conv64_dgrad_fused_bf16_multi: bad dims");
-    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "fdn_conv64_dgrad_fused_bf16_multi: bad act %d", act);
-    FDN_REQUIRE(!(y_mask && act == FDN_ACT_NONE), "fdn_conv64_dgrad_fused_bf16_multi: a sign mask needs act = RELU or LEAKY");
-    for (int i = 0; i < nsrc; ++i) FDN_REQUIRE(dz[i] && wpack[i], "fdn_conv64_dgrad_fused_bf16_multi: NULL pointer for source %d", i);
-    const FdnExtraSrcBf ex{nsrc, nsrc > 1 ? dz[1] : nullptr, nsrc > 2 ? dz[2] : nullptr, nsrc > 1 ? wpack[1] : nullptr, nsrc > 2 ? wpack[2] : nullptr};
-    return fdn_conv64_bf16_launch(dz[0], wpack[0], nullptr, nullptr, nullptr, dxpad, skip, y_prev, dz_prev, N, D, H, W, D + 2, H + 2,
-                                  W + 2, -1, 1, act, alpha, (hipStream_t)stream, nullptr, y_mask, nsrc > 1 ? &ex : nullptr);
-}
-
-extern "C" int fdn_conv64_dgrad_fused_bf16(const uint16_t* dz, const uint16_t* wpack, float* dxpad, const uint16_t* skip,
-                                           const uint16_t* y_prev, int act, float alpha, uint16_t* dz_prev, int N, int D,
-                                           int H, int W, void* stream) {
-    return fdn_conv64_dgrad_fused_bf16_mask(dz, wpack, dxpad, skip, y_prev, nullptr, act, alpha, dz_prev, N, D, H, W, stream);
-}
-
-extern "C" int fdn_fold_halo_border_bf16(const float* dxpad0, const float* dxpad1, const float* dxpad2, int nsrc,
-                                         const uint16_t* skip, const uint16_t* y_prev, int act, float alpha,
-                                         uint16_t* dz_prev, int N, int D, int H, int W, void* stream) {
-    FDN_REQUIRE(dxpad0 && dz_prev, "fdn_fold_halo_border_bf16: NULL argument");
-    FDN_REQUIRE(nsrc >= 1 && nsrc <= 3 && (nsrc < 2 || dxpad1) && (nsrc < 3 || dxpad2), "fdn_fold_halo_border_bf16: bad nsrc %d", nsrc);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_fold_halo_border_bf16: bad dims");
-    return fdn_fold_halo_border_bf16_launch(dxpad0, dxpad1, dxpad2, nsrc, skip, y_prev, act, alpha, dz_prev, N, D, H, W,
-                                            (hipStream_t)stream);
-}
-
-extern "C" int fdn_conv1x1_dgrad(const float* dz, const float* w, const float* ya, const float* yb, float* dxa, float* dxb,
-                                 int64_t nvox, void* stream) {
-    FDN_REQUIRE(dz && w && ya && yb && dxa && dxb && nvox > 0, "fdn_conv1x1_dgrad: NULL argument or nvox<=0");
-    return fdn_conv1x1_dgrad_launch<float>(dz, w, ya, yb, dxa, dxb, nvox, (hipStream_t)stream);
-}
-
-extern "C" int fdn_conv_cout1_dgrad_folded(const float* dz, const float* w, const float* y_prev, int act, float alpha,
-                                           float* dz_prev, float* dbias_prev, void* workspace, size_t workspace_bytes, int N,
-                                           int D, int H, int W, int lddz, int dz_coff, void* stream) {
-    return fdn_conv_cout1_dgrad_folded_launch<float>(dz, w, y_prev, act, alpha, dz_prev, dbias_prev, workspace, workspace_bytes,
-                                                     N, D, H, W, lddz, dz_coff, (hipStream_t)stream);
-}
-
-extern "C" int fdn_conv_cout1_dgrad_folded_mask(const float* dz, const float* w, const uint16_t* y_mask, int act, float alpha,
-                                                float* dz_prev, float* dbias_prev, void* workspace, size_t workspace_bytes, int N,
-                                                int D, int H, int W, int lddz, int dz_coff, void* stream) {
-    FDN_REQUIRE(y_mask && (act == FDN_ACT_RELU || act == FDN_ACT_LEAKY), "fdn_conv_cout1_dgrad_folded_mask: a sign mask and act = RELU or LEAKY");
-    return fdn_conv_cout1_dgrad_folded_launch<float>(dz, w, nullptr, act, alpha, dz_prev, dbias_prev, workspace, workspace_bytes,
-                                                     N, D, H, W, lddz, dz_coff, (hipStream_t)stream, y_mask);
-}
-
-// ---- bf16 activation path: the thin layers and the generic conv entry points ----
-extern "C" int fdn_conv1x1_dgrad_bf16(const uint16_t* dz, const float* w, const uint16_t* ya, const uint16_t* yb,
-                                      uint16_t* dxa, uint16_t* dxb, int64_t nvox, void* stream) {
-    FDN_REQUIRE(dz && w && ya && yb && dxa && dxb && nvox > 0, "fdn_conv1x1_dgrad_bf16: NULL argument or nvox<=0");
-    return fdn_conv1x1_dgrad_launch<uint16_t>(dz, w, ya, yb, dxa, dxb, nvox, (hipStream_t)stream);
-}
-
-extern "C" size_t fdn_conv3d_wgrad_bf16_batch_workspace_bytes(int n_layers, int N, int D, int H, int W) {
-    if (n_layers <= 0 || N <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t one = fdn_conv3d_wgrad_bf16_workspace_bytes(N, D, H, W, 64, 64, 3);
-    const size_t all = fdn_wgrad64_bf16_batch_ok(n_layers, N, D, H, W) ? fdn_wgrad64_bf16_batch_workspace_bytes(n_layers, N, D, H, W) : 0;
-    return all > one ? all : one;
+extern "C" int fdn_conv3d_wgrad_batch(const float* const* x, const float* const* dz, float* const* dw, float* const* dbias, int n_layers,
+                                      void* workspace, size_t workspace_bytes, int N, int D, int H, int W, int algo, void* stream) {
+    return conv3d_wgrad_batch<float>("fdn_conv3d_wgrad_batch", x, dz, dw, dbias, n_layers, workspace, workspace_bytes, N, D, H, W, algo, stream);
 }
 extern "C" int fdn_conv3d_wgrad_bf16_batch(const uint16_t* const* x, const uint16_t* const* dz, float* const* dw, float* const* dbias,
                                            int n_layers, void* workspace, size_t workspace_bytes, int N, int D, int H, int W, void* stream) {
-    FDN_REQUIRE(x && dz && dw && n_layers > 0, "fdn_conv3d_wgrad_bf16_batch: NULL table or n_layers <= 0");
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_conv3d_wgrad_bf16_batch: bad dims");
-    const size_t need = fdn_conv3d_wgrad_bf16_batch_workspace_bytes(n_layers, N, D, H, W);
-    if (workspace_bytes < need || !workspace) {
-        fdn_set_error("fdn_conv3d_wgrad_bf16_batch: workspace %zu < %zu bytes", workspace_bytes, need);
-        return FDN_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (fdn_wgrad64_bf16_batch_ok(n_layers, N, D, H, W)) {
-        if (int rc = fdn_wgrad64_bf16_batch_launch(x, dz, dw, n_layers, workspace, workspace_bytes, N, D, H, W, s)) return rc;
-    } else {
-        for (int i = 0; i < n_layers; ++i) {
-            FDN_REQUIRE(x[i] && dz[i] && dw[i], "fdn_conv3d_wgrad_bf16_batch: NULL pointer for layer %d", i);
-            if (int rc = fdn_wgrad64_bf16_launch(x[i], dz[i], dw[i], workspace, workspace_bytes, N, D, H, W, s)) return rc;
-        }
-    }
-    if (dbias)                           // (stream-ordered behind the reduction: the workspace is free again)
-        for (int i = 0; i < n_layers; ++i)
-            if (dbias[i])
-                if (int rc = fdn_bias_grad_launch<uint16_t>(dz[i], dbias[i], workspace, workspace_bytes, (int64_t)N * D * H * W, 64, 64, 0, s)) return rc;
-    return FDN_OK;
-}
-
-extern "C" int fdn_conv_cout1_dgrad_folded_bf16_mask(const float* dz, const float* w, const uint16_t* y_prev, const uint16_t* y_mask,
-                                                     int act, float alpha, uint16_t* dz_prev, float* dbias_prev, void* workspace,
-                                                     size_t workspace_bytes, int N, int D, int H, int W, int lddz, int dz_coff,
-                                                     void* stream) {
-    FDN_REQUIRE(!(y_mask && act == FDN_ACT_NONE), "fdn_conv_cout1_dgrad_folded_bf16_mask: a sign mask needs act = RELU or LEAKY");
-    return fdn_conv_cout1_dgrad_folded_launch<uint16_t>(dz, w, y_prev, act, alpha, dz_prev, dbias_prev, workspace,
-                                                        workspace_bytes, N, D, H, W, lddz, dz_coff, (hipStream_t)stream, y_mask);
-}
-
-extern "C" int fdn_conv_cout1_dgrad_folded_bf16(const float* dz, const float* w, const uint16_t* y_prev, int act, float alpha,
-                                                uint16_t* dz_prev, float* dbias_prev, void* workspace, size_t workspace_bytes,
-                                                int N, int D, int H, int W, int lddz, int dz_coff, void* stream) {
-    return fdn_conv_cout1_dgrad_folded_bf16_mask(dz, w, y_prev, nullptr, act, alpha, dz_prev, dbias_prev, workspace, workspace_bytes, N, D, H, W,
-                                                 lddz, dz_coff, stream);
-}
-
-extern "C" int fdn_conv3d_fwd_bf16(const uint16_t* x, const uint16_t* x2, const float* w, const uint16_t* wpack,
-                                   const float* bias, const uint16_t* residual, void* y, int N, int D, int H, int W, int Cin,
-                                   int Cout, int K, int ldy, int y_coff, int act, float alpha, void* stream) {
-    FDN_REQUIRE(x && y, "fdn_conv3d_fwd_bf16: x/y is NULL");
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_conv3d_fwd_bf16: bad dims N=%d D=%d H=%d W=%d", N, D, H, W);
-    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "fdn_conv3d_fwd_bf16: bad act %d", act);
-    hipStream_t s = (hipStream_t)stream;
-    if (Cin == 64 && Cout == 64 && K == 3) {
-        FDN_REQUIRE(ldy == 64 && y_coff == 0, "fdn_conv3d_fwd_bf16: 64->64 path writes dense rows");
-        return fdn_conv64_fwd_bf16(x, wpack, bias, residual, (uint16_t*)y, N, D, H, W, act, alpha, stream);
-    }
-    FDN_REQUIRE(residual == nullptr, "fdn_conv3d_fwd_bf16: residual only on the 64->64 path");
-    if (Cin == 3 && Cout == 64 && K == 3) {
-        FDN_REQUIRE(w && ldy == 64 && y_coff == 0, "fdn_conv3d_fwd_bf16(3->64): needs w, dense output");
-        return fdn_conv_cin3_fwd_launch<uint16_t>(x, w, bias, (uint16_t*)y, N, D, H, W, act, alpha, s);
-    }
-    if (Cin == 64 && Cout == 1 && K == 3) {
-        FDN_REQUIRE(w && ldy >= 1 && y_coff >= 0 && y_coff < ldy, "fdn_conv3d_fwd_bf16(64->1): bad w/ldy/y_coff");
-        return fdn_conv_cout1_fwd_launch<uint16_t>(x, w, bias, (float*)y, N, D, H, W, ldy, y_coff, act, alpha, s);
-    }
-    if (Cin == 128 && Cout == 64 && K == 1) {
-        FDN_REQUIRE(w && x2 && ldy == 64 && y_coff == 0, "fdn_conv3d_fwd_bf16(1x1 128->64): needs w, x2, dense output");
-        return fdn_conv1x1_fwd_launch<uint16_t>(x, x2, w, bias, (uint16_t*)y, (int64_t)N * D * H * W, act, alpha, s);
-    }
-    fdn_set_error("fdn_conv3d_fwd_bf16: unsupported (Cin=%d,Cout=%d,K=%d)", Cin, Cout, K);
-    return FDN_ERR_UNSUPPORTED;
-}
-
-extern "C" size_t fdn_conv3d_wgrad_bf16_workspace_bytes(int N, int D, int H, int W, int Cin, int Cout, int K) {
-    if (Cin == 64 && Cout == 64 && K == 3) return fdn_wgrad64_bf16_workspace_bytes(N, D, H, W);
-    return fdn_small_wgrad_workspace_bytes(Cin, Cout, K);
-}
-
-extern "C" int fdn_conv3d_wgrad_bf16(const uint16_t* x, const uint16_t* x2, const void* dz, float* dw, float* dbias,
-                                     void* workspace, size_t workspace_bytes, int N, int D, int H, int W, int Cin, int Cout,
-                                     int K, int lddz, int dz_coff, void* stream) {
-    FDN_REQUIRE(x && dz && dw, "fdn_conv3d_wgrad_bf16: x/dz/dw is NULL");
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_conv3d_wgrad_bf16: bad dims");
-    const size_t need = fdn_conv3d_wgrad_bf16_workspace_bytes(N, D, H, W, Cin, Cout, K);
-    if (workspace_bytes < need || (need && !workspace)) {
-        fdn_set_error("fdn_conv3d_wgrad_bf16: workspace %zu < %zu bytes", workspace_bytes, need);
-        return FDN_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nvox = (int64_t)N * D * H * W;
-    const uint16_t* dzb = (const uint16_t*)dz;
-    int rc;
-    if (Cin == 64 && Cout == 64 && K == 3) {
-        FDN_REQUIRE(lddz == 64 && dz_coff == 0, "fdn_conv3d_wgrad_bf16: 64->64 path reads dense dz rows");
-        rc = fdn_wgrad64_bf16_launch(x, dzb, dw, workspace, workspace_bytes, N, D, H, W, s);
-    } else if (Cin == 3 && Cout == 64 && K == 3) {
-        FDN_REQUIRE(lddz == 64 && dz_coff == 0, "fdn_conv3d_wgrad_bf16(3->64): dense dz rows");
-        rc = fdn_wgrad_cin3_launch<uint16_t>(x, dzb, dw, workspace, workspace_bytes, N, D, H, W, s);
-    } else if (Cin == 64 && Cout == 1 && K == 3) {      // the head's dz is the fp32 prediction gradient
-        rc = fdn_wgrad_cout1_launch<uint16_t>(x, (const float*)dz, dw, workspace, workspace_bytes, N, D, H, W, lddz, dz_coff, s);
-        if (rc != FDN_OK) return rc;
-        if (dbias) return fdn_bias_grad_launch<float>((const float*)dz, dbias, workspace, workspace_bytes, nvox, 1, lddz, dz_coff, s);
-        return FDN_OK;
-    } else if (Cin == 128 && Cout == 64 && K == 1) {
-        FDN_REQUIRE(x2 && lddz == 64 && dz_coff == 0, "fdn_conv3d_wgrad_bf16(1x1): needs x2, dense dz rows");
-        rc = fdn_wgrad_1x1_launch<uint16_t>(x, x2, dzb, dw, workspace, workspace_bytes, nvox, s);
-    } else {
-        fdn_set_error("fdn_conv3d_wgrad_bf16: unsupported (Cin=%d,Cout=%d,K=%d)", Cin, Cout, K);
-        return FDN_ERR_UNSUPPORTED;
-    }
-    if (rc != FDN_OK) return rc;
-    if (dbias) return fdn_bias_grad_launch<uint16_t>(dzb, dbias, workspace, workspace_bytes, nvox, Cout, lddz, dz_coff, s);
-    return FDN_OK;
+    return conv3d_wgrad_batch<uint16_t>("fdn_conv3d_wgrad_bf16_batch", x, dz, dw, dbias, n_layers, workspace, workspace_bytes, N, D, H, W,
+                                        FDN_ALGO_AUTO, stream);
 }

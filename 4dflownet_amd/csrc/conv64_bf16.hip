@@ -781,23 +781,22 @@ int launch_boxes(Conv64BfArgs& a, const Box* boxes, int nbox, hipStream_t s) {
 
 }  // namespace
 
-int fdn_conv64_bf16_launch(const uint16_t* x, const uint16_t* wpack, const float* bias, const uint16_t* residual, uint16_t* y,
-                           float* ypad, const uint16_t* fskip, const uint16_t* fy, uint16_t* fout, int N, int ID, int IH,
-                           int IW, int OD, int OH, int OW, int off, int zero_mode, int act, float alpha, hipStream_t s,
-                           uint16_t* ymask, const uint16_t* fmask, const FdnExtraSrcBf* extra) {
+int fdn_conv64_bf16_launch(const FdnConv64BfCall& c) {
+    const bool fused = c.op == FDN_CONV64_DGRAD_FUSED;
+    const int ID = c.ID, IH = c.IH, IW = c.IW, OD = c.OD, OH = c.OH, OW = c.OW;
     Conv64BfArgs a;
-    a.x = x; a.wp = wpack; a.bias = bias; a.res = residual; a.y = y; a.ypad = ypad;
+    a.x = c.x; a.wp = c.wpack; a.bias = c.bias; a.res = c.residual; a.y = c.y; a.ypad = c.ypad;
     a.x1 = a.x2 = a.wp1 = a.wp2 = nullptr; a.nsrc = 1;
-    if (extra && extra->nsrc > 1) {
-        FDN_REQUIRE(fout && zero_mode && off == -1 && extra->nsrc <= 3, "conv64 (bf16): further sources belong to a fused dgrad, 1..3 in all");
-        a.x1 = extra->x1; a.x2 = extra->x2; a.wp1 = extra->wp1; a.wp2 = extra->wp2; a.nsrc = extra->nsrc;
+    if (c.nsrc > 1) {
+        FDN_REQUIRE(fused && c.nsrc <= 3, "conv64 (bf16): further sources belong to a fused dgrad, 1..3 in all");
+        a.x1 = c.x1; a.x2 = c.x2; a.wp1 = c.wp1; a.wp2 = c.wp2; a.nsrc = c.nsrc;
     }
-    a.fskip = fskip; a.fy = fmask ? nullptr : fy; a.fout = fout;
-    a.ymask = ymask; a.fmask = fmask;
-    a.N = N; a.ID = ID; a.IH = IH; a.IW = IW; a.OD = OD; a.OH = OH; a.OW = OW;
-    a.off = off; a.zero_mode = zero_mode; a.act = act; a.alpha = alpha; a.dbg = fdn_conv64bf_dbg;
+    a.fskip = c.fskip; a.fy = c.fmask ? nullptr : c.fy; a.fout = c.fout;
+    a.ymask = c.ymask; a.fmask = c.fmask;
+    a.N = c.N; a.ID = ID; a.IH = IH; a.IW = IW; a.OD = OD; a.OH = OH; a.OW = OW;
+    a.off = c.off(); a.zero_mode = c.zero_mode(); a.act = c.act; a.alpha = c.alpha; a.dbg = fdn_conv64bf_dbg;
     const Box full{0, 0, 0, OD, OH, OW, 0, 2, 0, 2, 0, 2, 0};
-    if (!(fout && zero_mode && off == -1)) return launch_boxes(a, &full, 1, s);
+    if (!fused) return launch_boxes(a, &full, 1, c.s);
     // fused dgrad on the padded grid: inner box (27 taps) + six 1-voxel shell slabs (9 taps), as in conv64_mfma.hip
     // The d faces (one depth tap) are handed over in kernel order (h, d): the kernel slides its accumulator planes along the first
     // axis, which needs the 3-tap axis there -- planes = 8 h rows x (1 x <=64 w) positions instead of 1 plane x 60 positions per tile
@@ -807,20 +806,14 @@ int fdn_conv64_bf16_launch(const uint16_t* x, const uint16_t* wpack, const float
         {0, 0, 0, OH, 1, OW, 0, 2, 2, 2, 0, 2, 1},    {0, ID + 1, 0, OH, 1, OW, 0, 2, 0, 0, 0, 2, 1},     // d faces: (h, d = 0 | ID+1, w)
         {1, 0, 0, ID, 1, OW, 0, 2, 2, 2, 0, 2, 0},    {1, IH + 1, 0, ID, 1, OW, 0, 2, 0, 0, 0, 2, 0},
         {1, 1, 0, ID, IH, 1, 0, 2, 0, 2, 2, 2, 0},    {1, 1, IW + 1, ID, IH, 1, 0, 2, 0, 2, 0, 0, 0}};
-    return launch_boxes(a, boxes, 7, s);
+    return launch_boxes(a, boxes, 7, c.s);
 }
 
-int fdn_fold_halo_border_bf16_launch(const float* s0, const float* s1, const float* s2, int nsrc, const uint16_t* skip,
-                                     const uint16_t* yprev, int act, float alpha, uint16_t* out, int N, int D, int H, int W,
-                                     hipStream_t s) {
-    const int ID = D > 2 ? D - 2 : 0, IH = H > 2 ? H - 2 : 0;
-    const int64_t per_n = (int64_t)(D > 1 ? 2 : 1) * H * W + (int64_t)ID * (H > 1 ? 2 : 1) * W + (int64_t)ID * IH * (W > 1 ? 2 : 1);
-    const int64_t total = (int64_t)N * per_n * 8;
-    int64_t nb = (total + 255) / 256;
-    if (nb < 1) nb = 1;
-    if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(fold_halo_border_bf16_kernel, dim3((unsigned)nb), dim3(256), 0, s, s0, s1, s2, nsrc, skip, yprev, act,
-                       alpha, out, N, D, H, W);
+int fdn_fold_halo_border_launch(const float* s0, const float* s1, const float* s2, int nsrc, const uint16_t* skip,
+                                const uint16_t* yprev, int act, float alpha, uint16_t* out, int N, int D, int H, int W,
+                                hipStream_t s) {
+    hipLaunchKernelGGL(fold_halo_border_bf16_kernel, dim3(fdn_fold_halo_border_blocks(N, D, H, W, 8)), dim3(256), 0, s, s0, s1, s2,
+                       nsrc, skip, yprev, act, alpha, out, N, D, H, W);
     FDN_CHECK_LAUNCH("fold_halo_border_bf16_kernel");
     return FDN_OK;
 }

@@ -863,14 +863,8 @@ int fdn_conv64_launch_ex(const FdnConv64Call& c, int parts, int algo) {
 int fdn_fold_halo_border_launch(const float* s0, const float* s1, const float* s2, int nsrc, const float* skip,
                                 const float* yprev, int act, float alpha, float* out, int N, int D, int H, int W,
                                 hipStream_t s) {
-    const int ID = D > 2 ? D - 2 : 0, IH = H > 2 ? H - 2 : 0;
-    const int64_t per_n = (int64_t)(D > 1 ? 2 : 1) * H * W + (int64_t)ID * (H > 1 ? 2 : 1) * W + (int64_t)ID * IH * (W > 1 ? 2 : 1);
-    const int64_t total = (int64_t)N * per_n * 16;
-    int64_t nb = (total + 255) / 256;
-    if (nb < 1) nb = 1;
-    if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(fold_halo_border_kernel, dim3((unsigned)nb), dim3(256), 0, s, s0, s1, s2, nsrc, skip, yprev, act, alpha,
-                       out, N, D, H, W);
+    hipLaunchKernelGGL(fold_halo_border_kernel, dim3(fdn_fold_halo_border_blocks(N, D, H, W, 16)), dim3(256), 0, s, s0, s1, s2, nsrc,
+                       skip, yprev, act, alpha, out, N, D, H, W);
     FDN_CHECK_LAUNCH("fold_halo_border_kernel");
     return FDN_OK;
 }

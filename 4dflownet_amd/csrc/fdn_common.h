@@ -238,7 +238,18 @@ struct FdnTile { int td, th, tw, ntd, nth, ntw; };
 //   FDN_CONV64_DGRAD_FUSED: the same, with the mirror-pad fold of the interior finished into fout = (sum + fskip) * act'(fy or fmask).
 // The op values are the FDN_ROLE_* of fdn_conv64_pack_streams.
 enum FdnConv64Op { FDN_CONV64_FWD = FDN_ROLE_FWD, FDN_CONV64_DGRAD = FDN_ROLE_DGRAD, FDN_CONV64_DGRAD_FUSED = FDN_ROLE_DGRAD_FUSED };
-struct FdnConv64Call {
+// what a call says of either storage type: the op, its grids, the activation and the stream
+struct FdnConv64Grid {
+    int N = 0, ID = 0, IH = 0, IW = 0, OD = 0, OH = 0, OW = 0;
+    FdnConv64Op op = FDN_CONV64_FWD;
+    int act = FDN_ACT_NONE;
+    float alpha = 0.f;
+    hipStream_t s = nullptr;
+    // the kernels' boundary arguments: output p reads input p + tap - 1 + off; zero_mode: zero outside the input, else edge clamp
+    int off() const { return op == FDN_CONV64_FWD ? 0 : -1; }
+    int zero_mode() const { return op == FDN_CONV64_FWD ? 0 : 1; }
+};
+struct FdnConv64Call : FdnConv64Grid {
     // x: input rows (dz of a dgrad); wpack: the pack (FDN_CONV64_PACK_FLOATS), each launcher reads its own stream of it; y: output rows
     // (the padded scratch of a dgrad); fskip, fy, fout: skip, y_prev and dz_prev of the fused fold
     const float *x = nullptr, *wpack = nullptr, *bias = nullptr, *residual = nullptr, *fskip = nullptr, *fy = nullptr;
@@ -250,14 +261,17 @@ struct FdnConv64Call {
     // at the same offset inside it, so one distance serves the 2-D and the 1-D kernel)
     int nsrc = 1, wd1 = 0, wd2 = 0;
     const float *x1 = nullptr, *x2 = nullptr;
-    int N = 0, ID = 0, IH = 0, IW = 0, OD = 0, OH = 0, OW = 0;
-    FdnConv64Op op = FDN_CONV64_FWD;
-    int act = FDN_ACT_NONE;
-    float alpha = 0.f;
-    hipStream_t s = nullptr;
-    // the kernels' boundary arguments: output p reads input p + tap - 1 + off; zero_mode: zero outside the input, else edge clamp
-    int off() const { return op == FDN_CONV64_FWD ? 0 : -1; }
-    int zero_mode() const { return op == FDN_CONV64_FWD ? 0 : 1; }
+};
+// The same convolution on bf16 activations, as fdn_conv64_bf16_launch takes it (conv64_bf16.hip; FDN_CONV64_FWD and _DGRAD_FUSED): x, y,
+// residual, fskip, fy, fout are bf16 rows, the padded scratch of the dgrad (ypad) stays fp32, and the further sources of a multi-source
+// fused dgrad come with the pointers of their own packs (any order, any distance)
+struct FdnConv64BfCall : FdnConv64Grid {
+    const uint16_t *x = nullptr, *wpack = nullptr, *residual = nullptr, *fskip = nullptr, *fy = nullptr, *fmask = nullptr;
+    const float* bias = nullptr;
+    uint16_t *y = nullptr, *fout = nullptr, *ymask = nullptr;
+    float* ypad = nullptr;
+    int nsrc = 1;
+    const uint16_t *x1 = nullptr, *x2 = nullptr, *wp1 = nullptr, *wp2 = nullptr;
 };
 // the source fields of a kernel argument struct (WinoArgs, Wino2Args)
 template <typename Args> void fdn_conv64_set_sources(Args& a, const FdnConv64Call& c) {
@@ -290,6 +304,14 @@ int fdn_pack_conv64_wino2d_launch(const float* w, float* uf, float* ud, hipStrea
 int fdn_fold_halo_border_launch(const float* s0, const float* s1, const float* s2, int nsrc, const float* skip,
                                 const float* yprev, int act, float alpha, float* out, int N, int D, int H, int W,
                                 hipStream_t s);
+// workgroups of a fold_halo_border launch of either storage type: one thread per 16-B vector of the border voxels' 64-channel rows
+// (vecs: 16 per fp32 row, 8 per bf16 row), 256 threads each, 1..4096
+inline unsigned fdn_fold_halo_border_blocks(int N, int D, int H, int W, int vecs) {
+    const int ID = D > 2 ? D - 2 : 0, IH = H > 2 ? H - 2 : 0;
+    const int64_t per_n = (int64_t)(D > 1 ? 2 : 1) * H * W + (int64_t)ID * (H > 1 ? 2 : 1) * W + (int64_t)ID * IH * (W > 1 ? 2 : 1);
+    const int64_t nb = ((int64_t)N * per_n * vecs + 255) / 256;
+    return (unsigned)(nb < 1 ? 1 : (nb > 4096 ? 4096 : nb));
+}
 int fdn_wgrad64_launch(const float* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H,
                        int W, hipStream_t s);
 size_t fdn_wgrad64_workspace_bytes(int N, int D, int H, int W);
@@ -304,15 +326,10 @@ int fdn_wgrad64_wino_batch_launch(const float* const* x, const float* const* dz,
 int fdn_wgrad64_reduce_launch(const float* partial, float* dw, int S, hipStream_t s);
 
 // bf16 activation path (conv64_bf16.hip)
-// further sources of a multi-source fused dgrad in bf16 mode (fdn_conv64_dgrad_fused_bf16_multi): rows and packs of sources 1, 2
-struct FdnExtraSrcBf { int nsrc; const uint16_t* x1; const uint16_t* x2; const uint16_t* wp1; const uint16_t* wp2; };
-int fdn_conv64_bf16_launch(const uint16_t* x, const uint16_t* wpack, const float* bias, const uint16_t* residual, uint16_t* y,
-                           float* ypad, const uint16_t* fskip, const uint16_t* fy, uint16_t* fout, int N, int ID, int IH,
-                           int IW, int OD, int OH, int OW, int off, int zero_mode, int act, float alpha, hipStream_t s,
-                           uint16_t* ymask = nullptr, const uint16_t* fmask = nullptr, const struct FdnExtraSrcBf* extra = nullptr);
-int fdn_fold_halo_border_bf16_launch(const float* s0, const float* s1, const float* s2, int nsrc, const uint16_t* skip,
-                                     const uint16_t* yprev, int act, float alpha, uint16_t* out, int N, int D, int H, int W,
-                                     hipStream_t s);
+int fdn_conv64_bf16_launch(const FdnConv64BfCall& c);
+int fdn_fold_halo_border_launch(const float* s0, const float* s1, const float* s2, int nsrc, const uint16_t* skip,
+                                const uint16_t* yprev, int act, float alpha, uint16_t* out, int N, int D, int H, int W,
+                                hipStream_t s);
 size_t fdn_wgrad64_bf16_workspace_bytes(int N, int D, int H, int W);
 int fdn_wgrad64_bf16_launch(const uint16_t* x, const uint16_t* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H,
                             int W, hipStream_t s);

@@ -727,18 +727,18 @@ int fdn_wgrad_cout1_launch(const T* x, const float* dz, float* dw, void* ws, siz
 }
 
 template <typename T>
-int fdn_conv_cout1_dgrad_folded_launch(const float* dz, const float* w, const T* y_prev, int act, float alpha, T* dz_prev,
-                                       float* dbias_prev, void* workspace, size_t workspace_bytes, int N, int D, int H, int W,
-                                       int lddz, int dz_coff, hipStream_t s, const uint16_t* ymask) {
-    FDN_REQUIRE(dz && w && dz_prev && N > 0 && D > 0 && H > 0 && W > 0, "fdn_conv_cout1_dgrad_folded: bad argument");
-    FDN_REQUIRE(!(ymask && sizeof(T) == 4) || (W % 4 == 0 && fdn_heads_use_mfma), "fdn_conv_cout1_dgrad_folded: the fp32 sign mask (planar words) needs W %% 4 == 0");
+int fdn_conv_cout1_dgrad_folded_launch(const char* who, const float* dz, const float* w, const T* y_prev, int act, float alpha,
+                                       T* dz_prev, float* dbias_prev, void* workspace, size_t workspace_bytes, int N, int D, int H,
+                                       int W, int lddz, int dz_coff, hipStream_t s, const uint16_t* ymask) {
+    FDN_REQUIRE(dz && w && dz_prev && N > 0 && D > 0 && H > 0 && W > 0, "%s: bad argument", who);
+    FDN_REQUIRE(!(ymask && sizeof(T) == 4) || (W % 4 == 0 && fdn_heads_use_mfma), "%s: the fp32 sign mask (planar words) needs W %% 4 == 0", who);
 #ifdef FDN_TEST_HOOKS
     if (!fdn_heads_use_mfma) {
-        FDN_REQUIRE(W <= 4096, "fdn_conv_cout1_dgrad_folded: W too large for the row stage");
+        FDN_REQUIRE(W <= 4096, "%s: W too large for the row stage", who);
         const int nrows = N * D * H;
         const int nb = nrows < 2048 ? nrows : 2048;
         if (dbias_prev && (!workspace || workspace_bytes < (size_t)nb * 64 * sizeof(float))) {
-            fdn_set_error("fdn_conv_cout1_dgrad_folded: workspace %zu < %zu bytes", workspace_bytes, (size_t)nb * 64 * sizeof(float));
+            fdn_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, (size_t)nb * 64 * sizeof(float));
             return FDN_ERR_WORKSPACE;
         }
         const size_t lds = (size_t)(27 * 64 + 9 * W + 16) * sizeof(float);
@@ -751,7 +751,7 @@ int fdn_conv_cout1_dgrad_folded_launch(const float* dz, const float* w, const T*
 #endif
     const int nb = fdn_head_dgrad_blocks(N, D, H, W);
     if (dbias_prev && (!workspace || workspace_bytes < (size_t)nb * 64 * sizeof(float))) {
-        fdn_set_error("fdn_conv_cout1_dgrad_folded: workspace %zu < %zu bytes", workspace_bytes, (size_t)nb * 64 * sizeof(float));
+        fdn_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, (size_t)nb * 64 * sizeof(float));
         return FDN_ERR_WORKSPACE;
     }
     const int rc = fdn_head_dgrad_launch<T>(dz, w, y_prev, act, alpha, dz_prev, dbias_prev ? (float*)workspace : nullptr, N, D,
@@ -801,8 +801,9 @@ int fdn_bias_grad_launch(const T* dz, float* db, void* ws, size_t ws_bytes, int6
     template int fdn_wgrad_cin3_launch<T>(const T*, const T*, float*, void*, size_t, int, int, int, int, hipStream_t);         \
     template int fdn_wgrad_cout1_launch<T>(const T*, const float*, float*, void*, size_t, int, int, int, int, int, int,        \
                                            hipStream_t);                                                                       \
-    template int fdn_conv_cout1_dgrad_folded_launch<T>(const float*, const float*, const T*, int, float, T*, float*, void*,    \
-                                                       size_t, int, int, int, int, int, int, hipStream_t, const uint16_t*);   \
+    template int fdn_conv_cout1_dgrad_folded_launch<T>(const char*, const float*, const float*, const T*, int, float, T*,      \
+                                                       float*, void*, size_t, int, int, int, int, int, int, hipStream_t,      \
+                                                       const uint16_t*);                                                      \
     template int fdn_wgrad_1x1_launch<T>(const T*, const T*, const T*, float*, void*, size_t, int64_t, hipStream_t);           \
     template int fdn_bias_grad_launch<T>(const T*, float*, void*, size_t, int64_t, int, int, int, hipStream_t);
 FDN_INSTANTIATE_SMALL(float)

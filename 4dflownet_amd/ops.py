@@ -4,6 +4,7 @@ Every function launches asynchronously on torch's current HIP stream and returns
 Tensors must be fp32, contiguous and on a ROCm device; anything else raises (no CPU path)."""
 import ctypes
 import functools
+import math
 import operator
 
 import torch
@@ -57,16 +58,22 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def input_features(u, v, w, mu, mv, mw, phase=None, pc=None):
+# An operator whose two storage types differ only in the type of the activation tensors and the suffix of the library's entry point has
+# ONE body here, a private helper both modules' public functions forward to: `entry` names the entry point, act_dtype is the type of the
+# activation tensors (parameters, their gradients, the padded dgrad scratch and workspaces are fp32 in both modes).
+def _input_features(entry, act_dtype, u, v, w, mu, mv, mw, phase, pc):
     shp = u.shape[:-1] if u.shape[-1] == 1 else u.shape
-    nvox = u.numel()
     if phase is None:
-        phase = torch.empty(tuple(shp) + (3,), device=u.device, dtype=torch.float32)
+        phase = torch.empty(tuple(shp) + (3,), device=u.device, dtype=act_dtype)
     if pc is None:
-        pc = torch.empty(tuple(shp) + (3,), device=u.device, dtype=torch.float32)
-    check(_lib.load().fdn_input_features(_p(u), _p(v), _p(w), _p(mu), _p(mv), _p(mw), _p(phase), _p(pc), nvox, _stream()),
-          "fdn_input_features")
+        pc = torch.empty(tuple(shp) + (3,), device=u.device, dtype=act_dtype)
+    check(getattr(_lib.load(), entry)(_p(u, "u"), _p(v, "v"), _p(w, "w"), _p(mu, "mu"), _p(mv, "mv"), _p(mw, "mw"),
+                                      _ptr(act_dtype, phase, "phase"), _ptr(act_dtype, pc, "pc"), u.numel(), _stream()), entry)
     return phase, pc
+
+
+def input_features(u, v, w, mu, mv, mw, phase=None, pc=None):
+    return _input_features("fdn_input_features", ACT_DTYPE, u, v, w, mu, mv, mw, phase, pc)
 
 
 def _volume_geometry(frames, patch_size, counts, g0, count, who):
@@ -205,16 +212,21 @@ def pack_patch_cores(pred, side, out=None):
     return out
 
 
-def pack_conv64_weights(w, wp_fwd=None, wp_dgrad=None, want_dgrad=True):
+def _pack_conv64_weights(entry, act_dtype, elems, w, wp_fwd, wp_dgrad, want_dgrad):
+    """pack_conv64_weights of either storage type: a pack holds `elems` elements of act_dtype."""
     if tuple(w.shape) != (3, 3, 3, 64, 64):
         raise FdnError("pack_conv64_weights: expected (3,3,3,64,64), got %s" % (tuple(w.shape),))
     if wp_fwd is None:
-        wp_fwd = torch.empty(CONV64_PACK_FLOATS, device=w.device, dtype=torch.float32)
+        wp_fwd = torch.empty(elems, device=w.device, dtype=act_dtype)
     if wp_dgrad is None and want_dgrad:
-        wp_dgrad = torch.empty(CONV64_PACK_FLOATS, device=w.device, dtype=torch.float32)
-    check(_lib.load().fdn_pack_conv64_weights(_p(w), _p(wp_fwd), _p(wp_dgrad, allow_none=True), _stream()),
-          "fdn_pack_conv64_weights")
+        wp_dgrad = torch.empty(elems, device=w.device, dtype=act_dtype)
+    check(getattr(_lib.load(), entry)(_p(w, "w"), _ptr(act_dtype, wp_fwd, "wp_fwd"), _ptr(act_dtype, wp_dgrad, "wp_dgrad", allow_none=True),
+                                      _stream()), entry)
     return wp_fwd, wp_dgrad
+
+
+def pack_conv64_weights(w, wp_fwd=None, wp_dgrad=None, want_dgrad=True):
+    return _pack_conv64_weights("fdn_pack_conv64_weights", ACT_DTYPE, PACK_ELEMS, w, wp_fwd, wp_dgrad, want_dgrad)
 
 
 def conv64_mask_ok(N, D, H, W, algo=ALGO_AUTO):
@@ -275,27 +287,31 @@ def conv3d_dgrad(dz, w, wpack_dgrad=None, out=None, lddz=None, dz_coff=0, spatia
     return out
 
 
+def _conv_cout1_dgrad_folded(entry, act_dtype, src, dz, w, spatial, act, alpha, lddz, dz_coff, out, dbias_prev, workspace):
+    """conv_cout1_dgrad_folded of either storage type (dz is the fp32 prediction gradient in both).  src: the checked pointers the entry
+    point reads act' from -- y_prev, or its sign mask, or both."""
+    N, D, H, W = spatial
+    if out is None:
+        out = torch.empty((N, D, H, W, 64), device=dz.device, dtype=act_dtype)
+    if dbias_prev is not None and workspace is None:
+        workspace = torch.empty(2048 * 64, device=dz.device, dtype=torch.float32)
+    wsb = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    check(getattr(_lib.load(), entry)(_p(dz, "dz"), _p(w, "w"), *src, act, float(alpha), _ptr(act_dtype, out, "out"),
+                                      _p(dbias_prev, "dbias_prev", allow_none=True), _p(workspace, "workspace", allow_none=True), wsb,
+                                      N, D, H, W, lddz, dz_coff, _stream()), entry)
+    return out
+
+
 def conv_cout1_dgrad_folded(dz, w, spatial, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA, lddz=1, dz_coff=0, out=None,
                             dbias_prev=None, workspace=None, mask=None):
     """64->1 head dgrad + halo fold + act'(y_prev) in one kernel.  Returns (N,D,H,W,64).  With dbias_prev (64 floats) it
     also emits the producing layer's bias gradient (sum of the result over voxels); needs a >= 512 KB workspace.
     mask: the sign mask conv3d_fwd(mask=...) wrote beside y_prev (W % 4 == 0), read instead of y_prev's rows."""
-    N, D, H, W = spatial
-    if out is None:
-        out = torch.empty((N, D, H, W, 64), device=dz.device, dtype=torch.float32)
-    if dbias_prev is not None and workspace is None:
-        workspace = torch.empty(2048 * 64, device=dz.device, dtype=torch.float32)
-    wsb = 0 if workspace is None else workspace.numel() * workspace.element_size()
     if mask is not None:
-        check(_lib.load().fdn_conv_cout1_dgrad_folded_mask(_p(dz, "dz"), _p(w, "w"), _mask_ptr(mask, N * D * H * W, "conv_cout1_dgrad_folded"),
-                                                           act, float(alpha), _p(out), _p(dbias_prev, allow_none=True),
-                                                           _p(workspace, allow_none=True), wsb, N, D, H, W, lddz, dz_coff, _stream()),
-              "fdn_conv_cout1_dgrad_folded_mask")
-        return out
-    check(_lib.load().fdn_conv_cout1_dgrad_folded(_p(dz, "dz"), _p(w, "w"), _p(y_prev, allow_none=True), act, float(alpha),
-                                                  _p(out), _p(dbias_prev, allow_none=True), _p(workspace, allow_none=True), wsb,
-                                                  N, D, H, W, lddz, dz_coff, _stream()), "fdn_conv_cout1_dgrad_folded")
-    return out
+        entry, src = "fdn_conv_cout1_dgrad_folded_mask", (_mask_ptr(mask, math.prod(spatial), "conv_cout1_dgrad_folded"),)
+    else:
+        entry, src = "fdn_conv_cout1_dgrad_folded", (_p(y_prev, "y_prev", allow_none=True),)
+    return _conv_cout1_dgrad_folded(entry, ACT_DTYPE, src, dz, w, spatial, act, alpha, lddz, dz_coff, out, dbias_prev, workspace)
 
 
 def fold_halo(dxpads, skip=None, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA, out=None):
@@ -370,32 +386,41 @@ def conv64_dgrad_multi_ok(algos):
     return len(set(algos)) == 1
 
 
-def fold_halo_border(dxpads, out, skip=None, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA):
+def _fold_halo_border(entry, pa, dxpads, out, skip, y_prev, act, alpha):
+    """fold_halo_border of either storage type: pa checks an activation pointer (the padded scratches are fp32 in both)."""
     N, D, H, W = out.shape[:4]
-    ptrs = [_p(t) for t in dxpads] + [None] * (3 - len(dxpads))
-    check(_lib.load().fdn_fold_halo_border(ptrs[0], ptrs[1], ptrs[2], len(dxpads), _p(skip, allow_none=True),
-                                           _p(y_prev, allow_none=True), act, float(alpha), _p(out), N, D, H, W, _stream()),
-          "fdn_fold_halo_border")
+    ptrs = [_p(t, "dxpad") for t in dxpads] + [None] * (3 - len(dxpads))
+    check(getattr(_lib.load(), entry)(ptrs[0], ptrs[1], ptrs[2], len(dxpads), pa(skip, "skip", allow_none=True),
+                                      pa(y_prev, "y_prev", allow_none=True), act, float(alpha), pa(out, "out"), N, D, H, W, _stream()), entry)
     return out
 
 
-def conv1x1_dgrad(dz, w, ya, yb, dxa=None, dxb=None):
+def fold_halo_border(dxpads, out, skip=None, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA):
+    return _fold_halo_border("fdn_fold_halo_border", _p, dxpads, out, skip, y_prev, act, alpha)
+
+
+def _conv1x1_dgrad(entry, pa, dz, w, ya, yb, dxa, dxb):
     nvox = dz.numel() // 64
     if dxa is None:
         dxa = torch.empty_like(ya)
     if dxb is None:
         dxb = torch.empty_like(yb)
-    check(_lib.load().fdn_conv1x1_dgrad(_p(dz), _p(w), _p(ya), _p(yb), _p(dxa), _p(dxb), nvox, _stream()),
-          "fdn_conv1x1_dgrad")
+    check(getattr(_lib.load(), entry)(pa(dz, "dz"), _p(w, "w"), pa(ya, "ya"), pa(yb, "yb"), pa(dxa, "dxa"), pa(dxb, "dxb"), nvox, _stream()),
+          entry)
     return dxa, dxb
+
+
+def conv1x1_dgrad(dz, w, ya, yb, dxa=None, dxb=None):
+    return _conv1x1_dgrad("fdn_conv1x1_dgrad", _p, dz, w, ya, yb, dxa, dxb)
 
 
 def wgrad_workspace_bytes(N, D, H, W, Cin, Cout, K):
     return int(_lib.load().fdn_conv3d_wgrad_workspace_bytes(N, D, H, W, Cin, Cout, K))
 
 
-def conv3d_wgrad(x, dz, K, Cin, Cout, x2=None, want_bias=False, dw=None, dbias=None, workspace=None, lddz=None,
-                 dz_coff=0, algo=ALGO_AUTO):
+def _conv3d_wgrad(entry, act_dtype, need, x, dz, K, Cin, Cout, x2, want_bias, dw, dbias, workspace, lddz, dz_coff, *algo):
+    """conv3d_wgrad of either storage type: need is wgrad_workspace_bytes of the module, algo is (algo,) where the entry point takes one.
+    x (and x2) are act_dtype; so is dz, except for Cout == 1, where it is the fp32 prediction gradient; dw / dbias are fp32."""
     N, D, H, W = x.shape[:4]
     if lddz is None:
         lddz = dz.shape[-1]
@@ -403,14 +428,21 @@ def conv3d_wgrad(x, dz, K, Cin, Cout, x2=None, want_bias=False, dw=None, dbias=N
         dw = torch.empty((K, K, K, Cin, Cout), device=x.device, dtype=torch.float32)
     if want_bias and dbias is None:
         dbias = torch.empty((Cout,), device=x.device, dtype=torch.float32)
-    need = wgrad_workspace_bytes(N, D, H, W, Cin, Cout, K)
+    nbytes = need(N, D, H, W, Cin, Cout, K)
     if workspace is None:
-        workspace = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
-    check(_lib.load().fdn_conv3d_wgrad(_p(x, "x"), _p(x2, allow_none=True), _p(dz, "dz"), _p(dw, "dw"),
-                                       _p(dbias, allow_none=True), _p(workspace, "workspace"),
-                                       workspace.numel() * workspace.element_size(), N, D, H, W, Cin, Cout, K, lddz,
-                                       dz_coff, int(algo), _stream()), "fdn_conv3d_wgrad")
+        workspace = torch.empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)
+    check(getattr(_lib.load(), entry)(_ptr(act_dtype, x, "x"), _ptr(act_dtype, x2, "x2", allow_none=True),
+                                      _ptr(torch.float32 if Cout == 1 else act_dtype, dz, "dz"), _p(dw, "dw"),
+                                      _p(dbias, "dbias", allow_none=True), _p(workspace, "workspace"),
+                                      workspace.numel() * workspace.element_size(), N, D, H, W, Cin, Cout, K, lddz, dz_coff, *algo,
+                                      _stream()), entry)
     return dw, dbias
+
+
+def conv3d_wgrad(x, dz, K, Cin, Cout, x2=None, want_bias=False, dw=None, dbias=None, workspace=None, lddz=None,
+                 dz_coff=0, algo=ALGO_AUTO):
+    return _conv3d_wgrad("fdn_conv3d_wgrad", ACT_DTYPE, wgrad_workspace_bytes, x, dz, K, Cin, Cout, x2, want_bias, dw, dbias, workspace,
+                         lddz, dz_coff, int(algo))
 
 
 def wgrad_batch_workspace_bytes(n_layers, N, D, H, W):
@@ -449,22 +481,30 @@ def conv64_wgrad_batch_ok(algo=ALGO_AUTO):
     return algo in (ALGO_AUTO, ALGO_WINO_H2, ALGO_WINO_BF16X3)
 
 
-def upsample_trilinear_fwd(x, R, out=None):
+def _upsample_trilinear_fwd(entry, act_dtype, x, R, out):
     N, D, H, W, C = x.shape
     if out is None:
-        out = torch.empty((N, D * R, H * R, W * R, C), device=x.device, dtype=torch.float32)
-    check(_lib.load().fdn_upsample_trilinear_fwd(_p(x), _p(out), N, D, H, W, C, R, _stream()), "fdn_upsample_trilinear_fwd")
+        out = torch.empty((N, D * R, H * R, W * R, C), device=x.device, dtype=act_dtype)
+    check(getattr(_lib.load(), entry)(_ptr(act_dtype, x, "x"), _ptr(act_dtype, out, "out"), N, D, H, W, C, R, _stream()), entry)
+    return out
+
+
+def upsample_trilinear_fwd(x, R, out=None):
+    return _upsample_trilinear_fwd("fdn_upsample_trilinear_fwd", ACT_DTYPE, x, R, out)
+
+
+def _upsample_trilinear_bwd(entry, act_dtype, dy, R, y_prev, act, alpha, out):
+    N, OD, OH, OW, C = dy.shape
+    D, H, W = OD // R, OH // R, OW // R
+    if out is None:
+        out = torch.empty((N, D, H, W, C), device=dy.device, dtype=act_dtype)
+    check(getattr(_lib.load(), entry)(_ptr(act_dtype, dy, "dy"), _ptr(act_dtype, y_prev, "y_prev", allow_none=True), act, float(alpha),
+                                      _ptr(act_dtype, out, "out"), N, D, H, W, C, R, _stream()), entry)
     return out
 
 
 def upsample_trilinear_bwd(dy, R, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA, out=None):
-    N, OD, OH, OW, C = dy.shape
-    D, H, W = OD // R, OH // R, OW // R
-    if out is None:
-        out = torch.empty((N, D, H, W, C), device=dy.device, dtype=torch.float32)
-    check(_lib.load().fdn_upsample_trilinear_bwd(_p(dy), _p(y_prev, allow_none=True), act, float(alpha), _p(out), N, D, H, W,
-                                                 C, R, _stream()), "fdn_upsample_trilinear_bwd")
-    return out
+    return _upsample_trilinear_bwd("fdn_upsample_trilinear_bwd", ACT_DTYPE, dy, R, y_prev, act, alpha, out)
 
 
 def loss_metrics(pred, uh, vh, wh, mask, want_grad=True, out=None, dpred=None, scratch=None, div_weight=0.0):

@@ -2,16 +2,19 @@
 fp32 parameters / parameter gradients / prediction -> raw pointers -> lib4dflow_hip.so.
 
 Same function names, parameters and defaults as ops.py for everything network.py reaches through `self.ops`, so it selects one of the
-two modules by dtype and asks nothing more (tests/test_abi.py holds the two to that).  Same rules: GPU only, no fallback."""
+two modules by dtype and asks nothing more (tests/test_abi.py holds the two to that).  Same rules: GPU only, no fallback.  An operator
+that differs from its ops.py namesake only in the storage type is a call of the one body in ops.py."""
 import functools
+import math
 
 import torch
 
 from . import _lib
 from ._lib import FdnError, check
 from .ops import (ACT_NONE, ACT_RELU, ACT_LEAKY, LEAKY_ALPHA, ALGO_AUTO, ROLE_FWD, _stream, loss_metrics, l2_sumsq, adam_step,  # noqa: F401
-                  stitch_patches, pack_patch_cores, unrotate_accumulate, self_ensemble_orientations, volume_metrics, _ptr, _p as _pf, _mask_ptr, _input_features_volume, _dgrad_fused_multi,
-                  _wgrad_batch)
+                  stitch_patches, pack_patch_cores, unrotate_accumulate, self_ensemble_orientations, volume_metrics, _ptr, _p as _pf, _mask_ptr,
+                  _input_features, _input_features_volume, _pack_conv64_weights, _conv_cout1_dgrad_folded, _dgrad_fused_multi, _fold_halo_border,
+                  _conv1x1_dgrad, _conv3d_wgrad, _wgrad_batch, _upsample_trilinear_fwd, _upsample_trilinear_bwd)
 
 BF16 = torch.bfloat16
 ACT_DTYPE = BF16
@@ -20,14 +23,7 @@ _pb = functools.partial(_ptr, BF16)
 
 
 def input_features(u, v, w, mu, mv, mw, phase=None, pc=None):
-    shp = u.shape[:-1] if u.shape[-1] == 1 else u.shape
-    if phase is None:
-        phase = torch.empty(tuple(shp) + (3,), device=u.device, dtype=BF16)
-    if pc is None:
-        pc = torch.empty(tuple(shp) + (3,), device=u.device, dtype=BF16)
-    check(_lib.load().fdn_input_features_bf16(_pf(u), _pf(v), _pf(w), _pf(mu), _pf(mv), _pf(mw), _pb(phase), _pb(pc),
-                                              u.numel(), _stream()), "fdn_input_features_bf16")
-    return phase, pc
+    return _input_features("fdn_input_features_bf16", BF16, u, v, w, mu, mv, mw, phase, pc)
 
 
 def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None, orientation=None):
@@ -37,15 +33,7 @@ def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=No
 
 def pack_conv64_weights(w, wp_fwd=None, wp_dgrad=None, want_dgrad=True):
     """fp32 (3,3,3,64,64) -> bf16 operand streams (27*64*64 each)."""
-    if tuple(w.shape) != (3, 3, 3, 64, 64):
-        raise FdnError("pack_conv64_weights: expected (3,3,3,64,64), got %s" % (tuple(w.shape),))
-    if wp_fwd is None:
-        wp_fwd = torch.empty(PACK_ELEMS, device=w.device, dtype=BF16)
-    if wp_dgrad is None and want_dgrad:
-        wp_dgrad = torch.empty(PACK_ELEMS, device=w.device, dtype=BF16)
-    check(_lib.load().fdn_pack_conv64_weights_bf16(_pf(w, "w"), _pb(wp_fwd), _pb(wp_dgrad, allow_none=True), _stream()),
-          "fdn_pack_conv64_weights_bf16")
-    return wp_fwd, wp_dgrad
+    return _pack_conv64_weights("fdn_pack_conv64_weights_bf16", BF16, PACK_ELEMS, w, wp_fwd, wp_dgrad, want_dgrad)
 
 
 def pack_conv64_weights_batch(w_flat, w_offsets, packs, streams=None):
@@ -149,40 +137,20 @@ def conv3d_dgrad_fused_multi(dzs, wpacks_dgrad, dxpad, out, skip=None, y_prev=No
 
 
 def fold_halo_border(dxpads, out, skip=None, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA):
-    N, D, H, W = out.shape[:4]
-    ptrs = [_pf(t) for t in dxpads] + [None] * (3 - len(dxpads))
-    check(_lib.load().fdn_fold_halo_border_bf16(ptrs[0], ptrs[1], ptrs[2], len(dxpads), _pb(skip, allow_none=True),
-                                                _pb(y_prev, allow_none=True), act, float(alpha), _pb(out), N, D, H, W,
-                                                _stream()), "fdn_fold_halo_border_bf16")
-    return out
+    return _fold_halo_border("fdn_fold_halo_border_bf16", _pb, dxpads, out, skip, y_prev, act, alpha)
 
 
 def conv_cout1_dgrad_folded(dz, w, spatial, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA, lddz=1, dz_coff=0, out=None,
                             dbias_prev=None, workspace=None, mask=None):
     """64->1 head dgrad (dz = fp32 prediction gradient) + halo fold + act'(y_prev): bf16 (N,D,H,W,64).
     mask: the sign mask conv64_fwd(mask=...) wrote beside y_prev; read instead of y_prev for act'."""
-    N, D, H, W = spatial
-    if out is None:
-        out = torch.empty((N, D, H, W, 64), device=dz.device, dtype=BF16)
-    if dbias_prev is not None and workspace is None:
-        workspace = torch.empty(2048 * 64, device=dz.device, dtype=torch.float32)
-    wsb = 0 if workspace is None else workspace.numel() * workspace.element_size()
-    check(_lib.load().fdn_conv_cout1_dgrad_folded_bf16_mask(_pf(dz, "dz"), _pf(w, "w"), _pb(y_prev, allow_none=True),
-                                                            _mask_ptr(mask, N * D * H * W, "conv_cout1_dgrad_folded"), act, float(alpha), _pb(out), _pf(dbias_prev, allow_none=True),
-                                                            _pf(workspace, allow_none=True), wsb, N, D, H, W, lddz, dz_coff,
-                                                            _stream()), "fdn_conv_cout1_dgrad_folded_bf16_mask")
-    return out
+    src = (_pb(y_prev, "y_prev", allow_none=True), _mask_ptr(mask, math.prod(spatial), "conv_cout1_dgrad_folded"))
+    return _conv_cout1_dgrad_folded("fdn_conv_cout1_dgrad_folded_bf16_mask", BF16, src, dz, w, spatial, act, alpha, lddz, dz_coff, out,
+                                    dbias_prev, workspace)
 
 
 def conv1x1_dgrad(dz, w, ya, yb, dxa=None, dxb=None):
-    nvox = dz.numel() // 64
-    if dxa is None:
-        dxa = torch.empty_like(ya)
-    if dxb is None:
-        dxb = torch.empty_like(yb)
-    check(_lib.load().fdn_conv1x1_dgrad_bf16(_pb(dz), _pf(w), _pb(ya), _pb(yb), _pb(dxa), _pb(dxb), nvox, _stream()),
-          "fdn_conv1x1_dgrad_bf16")
-    return dxa, dxb
+    return _conv1x1_dgrad("fdn_conv1x1_dgrad_bf16", _pb, dz, w, ya, yb, dxa, dxb)
 
 
 def wgrad_workspace_bytes(N, D, H, W, Cin, Cout, K):
@@ -192,22 +160,8 @@ def wgrad_workspace_bytes(N, D, H, W, Cin, Cout, K):
 def conv3d_wgrad(x, dz, K, Cin, Cout, x2=None, want_bias=False, dw=None, dbias=None, workspace=None, lddz=None,
                  dz_coff=0, algo=ALGO_AUTO):
     """x bf16; dz bf16, except Cout == 1 where dz is the fp32 prediction gradient; dw / dbias fp32."""
-    N, D, H, W = x.shape[:4]
-    if lddz is None:
-        lddz = dz.shape[-1]
-    if dw is None:
-        dw = torch.empty((K, K, K, Cin, Cout), device=x.device, dtype=torch.float32)
-    if want_bias and dbias is None:
-        dbias = torch.empty((Cout,), device=x.device, dtype=torch.float32)
-    need = wgrad_workspace_bytes(N, D, H, W, Cin, Cout, K)
-    if workspace is None:
-        workspace = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
-    check(_lib.load().fdn_conv3d_wgrad_bf16(_pb(x, "x"), _pb(x2, allow_none=True),
-                                            _ptr(torch.float32 if Cout == 1 else BF16, dz, "dz"), _pf(dw, "dw"),
-                                            _pf(dbias, allow_none=True), _pf(workspace, "workspace"),
-                                            workspace.numel() * workspace.element_size(), N, D, H, W, Cin, Cout, K, lddz,
-                                            dz_coff, _stream()), "fdn_conv3d_wgrad_bf16")
-    return dw, dbias
+    return _conv3d_wgrad("fdn_conv3d_wgrad_bf16", BF16, wgrad_workspace_bytes, x, dz, K, Cin, Cout, x2, want_bias, dw, dbias, workspace,
+                         lddz, dz_coff)
 
 
 def wgrad_batch_workspace_bytes(n_layers, N, D, H, W):
@@ -221,19 +175,8 @@ def conv3d_wgrad_batch(xs, dzs, dws, dbiases=None, workspace=None, algo=ALGO_AUT
 
 
 def upsample_trilinear_fwd(x, R, out=None):
-    N, D, H, W, C = x.shape
-    if out is None:
-        out = torch.empty((N, D * R, H * R, W * R, C), device=x.device, dtype=BF16)
-    check(_lib.load().fdn_upsample_trilinear_fwd_bf16(_pb(x), _pb(out), N, D, H, W, C, R, _stream()),
-          "fdn_upsample_trilinear_fwd_bf16")
-    return out
+    return _upsample_trilinear_fwd("fdn_upsample_trilinear_fwd_bf16", BF16, x, R, out)
 
 
 def upsample_trilinear_bwd(dy, R, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA, out=None):
-    N, OD, OH, OW, C = dy.shape
-    D, H, W = OD // R, OH // R, OW // R
-    if out is None:
-        out = torch.empty((N, D, H, W, C), device=dy.device, dtype=BF16)
-    check(_lib.load().fdn_upsample_trilinear_bwd_bf16(_pb(dy), _pb(y_prev, allow_none=True), act, float(alpha), _pb(out), N,
-                                                      D, H, W, C, R, _stream()), "fdn_upsample_trilinear_bwd_bf16")
-    return out
+    return _upsample_trilinear_bwd("fdn_upsample_trilinear_bwd_bf16", BF16, dy, R, y_prev, act, alpha, out)
