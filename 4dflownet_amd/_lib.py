@@ -14,6 +14,7 @@ TEST_LIB_PATH = os.path.join(_HERE, "lib4dflow_hip_test.so")     # same sources 
 c_fp = ctypes.c_void_p      # device pointer to float
 c_i = ctypes.c_int
 c_i64 = ctypes.c_int64
+c_u64 = ctypes.c_uint64
 c_f = ctypes.c_float
 c_sz = ctypes.c_size_t
 
@@ -52,6 +53,8 @@ SIGNATURES = {
     "fdn_pack_patch_cores": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp]),
     "fdn_input_features_volume_oriented": (c_i, [c_fp] + [c_i] * 8 + [c_i64, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
     "fdn_unrotate_accumulate": (c_i, [c_fp, c_fp] + [c_i] * 6 + [c_fp]),
+    "fdn_kspace_downsample_workspace_bytes": (c_sz, [c_i] * 7),
+    "fdn_kspace_downsample": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 7 + [c_fp, c_u64, c_u64] + [c_fp] * 5),
     "fdn_l2_sumsq": (c_i, [c_fp, c_fp, c_i64, c_fp, c_fp]),
     "fdn_adam_step": (c_i, [c_fp] * 5 + [c_i64] + [c_f] * 5 + [c_fp, c_fp, c_fp]),
     "fdn_adam_step_dev": (c_i, [c_fp] * 5 + [c_i64, c_fp] + [c_f] * 4 + [c_fp, c_fp, c_fp]),

@@ -3,11 +3,17 @@
 Every HDF5 volume is decoded once and uploaded once; a batch is then produced by ten launches of
 fdn_gather_patches (slice + np.rot90 + component swap/sign + /venc, /4095 or mask threshold), driven by a
 descriptor table built from the CSV rows.  Outputs are device tensors, bit-identical to the host loader
-(data.PatchHandler3D), which in turn is bit-identical to the reference's loader."""
+(data.PatchHandler3D), which in turn is bit-identical to the reference's loader.
+
+resynthesize=dict(seed=s): the low-res side is not read from a file but synthesised from the resident high-res volumes at the start of
+every pass (fdn_kspace_downsample: k-space crop + noise, prepare_lowres.py's draws from private generators) -- a fresh noise
+realisation, SNR, VENC set and magnitude level per frame and epoch."""
+import os
+
 import numpy as np
 import torch
 
-from . import _lib, parallel
+from . import _lib, h5io, ops, parallel, prepare_lowres
 from ._lib import check
 from .data import _ROT, PatchHandler3D
 
@@ -22,20 +28,87 @@ class _DeviceBatches:
         self.indexes = np.atleast_2d(indexes)
         self.sampler = parallel.ShardedIndexSampler(len(self.indexes), handler.batch_size, shuffle, seed,
                                                     rank_=shard[0], world=shard[1])
+        self.passes = 0                                      # the epoch a resynthesising handler degrades for
 
     def __len__(self):
         return len(self.sampler)
 
     def __iter__(self):
+        if self.h.resynthesize is not None:
+            self.h.resynthesize_lowres(self.passes, self.indexes)
+            self.passes += 1
         for rows in self.sampler:
             yield self.h.load_batch_device([self.indexes[r] for r in rows])
 
 
 class DevicePatchHandler3D(PatchHandler3D):
-    def __init__(self, data_dir, patch_size, res_increase, batch_size, mask_threshold=0.6, device=None):
+    def __init__(self, data_dir, patch_size, res_increase, batch_size, mask_threshold=0.6, device=None, resynthesize=None):
+        """resynthesize: None, or dict(seed=s[, downsample=res_increase]): every pass over a dataset of
+        initialize_dataset begins with resynthesize_lowres(pass number); the low-res files the index rows name need not exist."""
         super().__init__(data_dir, patch_size, res_increase, batch_size, mask_threshold)
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self._dev = {}
+        self._venc_override = {}                             # lr_path -> (T,3) float32, installed by resynthesize_lowres
+        self.resynthesize = None if resynthesize is None else dict(resynthesize)
+        if self.resynthesize is not None:
+            unknown = set(self.resynthesize) - {"seed", "downsample"}
+            if unknown or "seed" not in self.resynthesize:
+                raise ValueError("resynthesize must be dict(seed=..[, downsample=..]), got %r" % (resynthesize,))
+            if self.resynthesize.setdefault("downsample", res_increase) != res_increase:
+                raise ValueError("resynthesize: downsample=%r must equal res_increase=%r" % (self.resynthesize["downsample"], res_increase))
+
+    def _vencs(self, lr_path, idx):
+        """venc_u, venc_v, venc_w of a frame: what resynthesize_lowres installed, else the file's."""
+        if lr_path in self._venc_override:
+            return self._venc_override[lr_path][idx]
+        return [self._cache.get(lr_path, n)[idx] for n in self.venc_colnames]
+
+    def resynthesize_lowres(self, epoch, indexes):
+        """Degrade u, v, w of every frame of every high-res file the index rows name, on the device, and install the results as the
+        resident low-res volumes (u, v, w, mag_u, mag_v, mag_w) and VENCs of the low-res name in those rows.  Per file and frame
+        prepare_lowres.draw_degradations(seed, epoch, ordinal of the file) gives the SNR, the VENCs and the magnitude level
+        (mag = mask * level); the noise is Philox in the kernel with stream_id = epoch << 32 | ordinal << 20 | frame.  High-res
+        volumes and the mask are untouched."""
+        rs = self.resynthesize
+        if rs is None:
+            raise ValueError("this handler was built without resynthesize=dict(seed=..)")
+        R = self.res_increase
+        pairs = sorted({(str(self._cell(r[0])), str(self._cell(r[1]))) for r in np.atleast_2d(indexes)})
+        for ordinal, (lr_name, hr_name) in enumerate(pairs):
+            lr_path = '{}/{}'.format(self.data_directory, lr_name)
+            hr_path = '{}/{}'.format(self.data_directory, hr_name)
+            hr = [self._dvol(hr_path, n) for n in self.hr_colnames]
+            mask = self._dvol(hr_path, self.mask_colname)[0]
+            T, shape = hr[0].shape[0], tuple(hr[0].shape[1:])
+            if T >= 1 << 20 or ordinal >= 1 << 12:
+                raise ValueError("resynthesize: %d frames / %d files exceed the stream_id layout" % (T, len(pairs)))
+            crops = ops.kspace_crops(shape, 1 / R)
+            lr_shape = tuple(2 * c for c in crops)                     # 2 * int((N // 2) / R) per axis
+            if os.path.exists(lr_path):                                # a prepared file beside it: the index rows were made for ITS extents
+                with h5io.open_read(lr_path) as f:
+                    have = tuple(int(n) for n in f[self.lr_colnames[0]].shape[1:])
+                if have != lr_shape:
+                    raise ValueError("resynthesize: %s holds low-res volumes of %s, the synthesis of %s at 1/%d gives %s"
+                                     % (lr_name, have, hr_name, R, lr_shape))
+            snr, vencs, mags = prepare_lowres.draw_degradations(
+                *[self._cache.get(hr_path, n + "_max") for n in self.hr_colnames], seed=rs["seed"], epoch=epoch, ordinal=ordinal)
+            names = self.lr_colnames + self.mag_colnames
+            if (lr_path, names[0]) not in self._dev or tuple(self._dev[(lr_path, names[0])].shape) != (T,) + lr_shape:
+                for n in names:
+                    self._dev[(lr_path, n)] = torch.empty((T,) + lr_shape, device=self.device, dtype=torch.float32)
+            stage = torch.empty((3,) + shape, device=self.device, dtype=torch.float32)
+            out = (torch.empty((3,) + lr_shape, device=self.device, dtype=torch.float32),
+                   torch.empty((3,) + lr_shape, device=self.device, dtype=torch.float32))
+            ws = torch.empty((ops.kspace_workspace_bytes(3, shape, crops) + 3) // 4, device=self.device, dtype=torch.float32)
+            for t in range(T):
+                for c in range(3):
+                    stage[c].copy_(hr[c][t])
+                ops.kspace_downsample(stage, mask, vencs[t], snr[t], crops, noise=None, seed=rs["seed"],
+                                      stream_id=(int(epoch) << 32) | (ordinal << 20) | t, mag_scale=mags[t], out=out, workspace=ws)
+                for c in range(3):
+                    self._dev[(lr_path, self.lr_colnames[c])][t].copy_(out[0][c])
+                    self._dev[(lr_path, self.mag_colnames[c])][t].copy_(out[1][c])
+            self._venc_override[lr_path] = vencs.astype(np.float32)
 
     def _dvol(self, path, name):
         key = (path, name)
@@ -69,7 +142,7 @@ class DevicePatchHandler3D(PatchHandler3D):
             idx = int(row[2])
             x0, y0, z0 = int(row[3]), int(row[4]), int(row[5])
             is_rotate, plane, k = int(row[6]), int(row[7]), int(row[8])
-            venc = np.max([self._cache.get(lr_path, n)[idx] for n in self.venc_colnames])
+            venc = np.max(self._vencs(lr_path, idx))
             vencs[b] = venc
             rot = _ROT.get((plane, k)) if is_rotate > 0 else None
             perm, sign = rot if rot else ((0, 1, 2), (1, 1, 1))

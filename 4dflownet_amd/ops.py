@@ -7,6 +7,7 @@ import functools
 import math
 import operator
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -162,6 +163,65 @@ def unrotate_accumulate(pred, acc, orientation, first, divisor=1):
     check(_lib.load().fdn_unrotate_accumulate(_p(pred, "pred"), _p(acc, "acc"), pred.shape[0], S, plane, k, int(bool(first)), int(divisor),
                                               _stream()), "fdn_unrotate_accumulate")
     return acc
+
+
+def kspace_crops(shape, crop_ratio):
+    """The crop half-widths of fft_downsampling.rectangular_crop3d, int((N // 2) * crop_ratio) per axis: the output extents are twice these."""
+    return tuple(int((int(n) // 2) * crop_ratio) for n in shape)
+
+
+def kspace_workspace_bytes(nvol, shape, crops):
+    X, Y, Z = (int(n) for n in shape)
+    cx, cy, cz = (int(c) for c in crops)
+    return _lib.load().fdn_kspace_downsample_workspace_bytes(int(nvol), X, Y, Z, cx, cy, cz)
+
+
+def kspace_downsample(vel, mag, venc, snr_db, crops, noise=None, seed=0, stream_id=0, mag_scale=None, out=None, workspace=None):
+    """Low-res synthesis on the device (fdn_kspace_downsample; fft_downsampling.downsample_phase_img): vel (nvol,X,Y,Z) velocity volumes that
+    share the magnitude volume mag (X,Y,Z) -> (lr_vel, lr_mag, sigma), the first two (nvol,2cx,2cy,2cz) with crops = (cx,cy,cz) =
+    kspace_crops(shape, crop_ratio), sigma (nvol,) the noise level of each volume.  venc, snr_db and mag_scale (default 1: mag is used as
+    it is) are scalars or one value per volume; 10**(snr_db/10) is formed in float64 and rounded once.  noise: a device tensor
+    (nvol,2cx,2cy,2cz) of standard normals, or None: Philox4x32-10 in the kernel, keyed by (seed, stream_id).  out = (lr_vel, lr_mag)
+    and workspace (kspace_workspace_bytes, any fp32 tensor) may be supplied by a caller that repeats the call; nothing here waits for the
+    device."""
+    if vel.dim() != 4 or mag.dim() != 3 or tuple(vel.shape[1:]) != tuple(mag.shape):
+        raise FdnError("kspace_downsample: vel must be (nvol,X,Y,Z) and mag (X,Y,Z), got %s and %s" % (tuple(vel.shape), tuple(mag.shape)))
+    nvol, X, Y, Z = (int(n) for n in vel.shape)
+    cx, cy, cz = (int(c) for c in crops)
+    lr_shape = (nvol, 2 * cx, 2 * cy, 2 * cz)
+    per_vol = lambda a, name: _per_volume(a, nvol, "kspace_downsample: " + name)
+    table = np.zeros((nvol, 4), np.float64)
+    table[:, 0] = per_vol(venc, "venc")
+    table[:, 1] = per_vol(1.0 if mag_scale is None else mag_scale, "mag_scale")
+    table[:, 2] = 10.0 ** (per_vol(snr_db, "snr_db") / 10.0)
+    pv, pm = _p(vel, "vel"), _p(mag, "mag")
+    lib = _lib.load()
+    need = lib.fdn_kspace_downsample_workspace_bytes(nvol, X, Y, Z, cx, cy, cz)
+    if need == 0:
+        raise FdnError("kspace_downsample: extents %s (1..1024 each), crops %s (1..N//2 each) or nvol=%d are out of range" % ((X, Y, Z), (cx, cy, cz), nvol))
+    if noise is not None and tuple(noise.shape) != lr_shape:
+        raise FdnError("kspace_downsample: noise must be %s, got %s" % (lr_shape, tuple(noise.shape)))
+    if out is None:
+        out = (torch.empty(lr_shape, device=vel.device, dtype=torch.float32), torch.empty(lr_shape, device=vel.device, dtype=torch.float32))
+    elif tuple(out[0].shape) != lr_shape or tuple(out[1].shape) != lr_shape:
+        raise FdnError("kspace_downsample: out must be two tensors of %s" % (lr_shape,))
+    sigma = torch.empty(nvol, device=vel.device, dtype=torch.float32)
+    if workspace is None:
+        workspace = torch.empty((need + 3) // 4, device=vel.device, dtype=torch.float32)
+    elif workspace.numel() * 4 < need:
+        raise FdnError("kspace_downsample: workspace of %d bytes expected, got %d" % (need, workspace.numel() * 4))
+    params = torch.from_numpy(table.astype(np.float32)).to(vel.device)
+    check(lib.fdn_kspace_downsample(pv, pm, _p(params, "params"), nvol, X, Y, Z, cx, cy, cz, _p(noise, "noise", allow_none=True),
+                                    int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 64 - 1), _p(out[0], "out[0]"), _p(out[1], "out[1]"),
+                                    _p(sigma, "sigma"), _p(workspace, "workspace"), _stream()), "fdn_kspace_downsample")
+    return out[0], out[1], sigma
+
+
+def _per_volume(a, nvol, name):
+    a = np.asarray(a, np.float64).reshape(-1)
+    if a.size not in (1, nvol):
+        raise FdnError("%s must be a scalar or one value per volume (%d), got %d" % (name, nvol, a.size))
+    return np.broadcast_to(a, (nvol,))
 
 
 def _pred_edge(pred, who):

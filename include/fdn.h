@@ -354,6 +354,33 @@ int fdn_input_features_volume_oriented(const float* frames, int F, int X, int Y,
  * ranges that overlap. */
 int fdn_unrotate_accumulate(const float* pred, float* acc, int count, int S, int plane, int k, int first, int divisor, void* stream);
 
+/* Low-res synthesis (prepare_data/fft_downsampling.py:6-137, downsample_phase_img): nvol velocity volumes vel (nvol,X,Y,Z) that share one
+ * magnitude volume mag (X,Y,Z) -> out_vel, out_mag (nvol,2cx,2cy,2cz), all fp32 on the device.  params is a DEVICE table (nvol,4) of
+ * {venc, mag_scale, snr_linear = 10^(SNRdb/10), 0}.  The crop half-widths are integers, c = int((N / 2) * crop_ratio) as the reference
+ * computes them.  Per volume, in this order:
+ *   1. x = mag * mag_scale * exp(i pi vel / venc)                         (sincospif(vel / venc): |vel| > venc wraps as in the reference)
+ *   2. along X, Y, Z the truncated DFT that equals fftn -> fftshift -> centre crop -> fftshift: with M = 2c,
+ *      F[k'] = sum_n x[n] exp(-2 pi i ((k n) mod N) / N),  k = k' for k' < c, else k' - M  (frequencies 0..c-1, -c..-1),  k' in 0..M-1
+ *   3. P = mean |F|^2 over the 2cx*2cy*2cz samples, sigma = sqrt(P / snr_linear)   (per-workgroup partial sums, added in a fixed order by
+ *      the kernel behind fdn_sum_partials: no atomics, reproducible bit for bit; sigma stays on the device)
+ *   4. Re F += sigma * g: real noise on the complex spectrum (fft_downsampling.py:63-69).  g = noise[e], a caller's array of standard
+ *      normals (nvol,2cx,2cy,2cz), or with noise == NULL generated in the kernel: e the element's linear index in that array,
+ *      (x0,x1,..) = Philox4x32-10(counter (e lo32, e hi32, stream_id lo32, stream_id hi32), key (seed lo32, seed hi32)),
+ *      u1 = ((x0 >> 9) + 0.5f) 2^-23, u2 = (x1 >> 8) 2^-24, g = sqrtf(-2 logf(u1)) cospif(2 u2)
+ *   5. along X, Y, Z  z[m] = (1/M) sum_k' F[k'] exp(+2 pi i ((k' m) mod M) / M)
+ *   6. out_mag = |z| * (2cx*2cy*2cz)/(X*Y*Z),  out_vel = atan2(Im z, Re z) / pi * venc
+ * Six launches of the gather kernel (two further runtime modes; the N or M unit roots of a stage sit in dynamic LDS, entry r =
+ * sincospif(2.f * r / N), the index (k n) mod N formed in integers) with complex fp32 intermediates in `workspace`
+ * (fdn_kspace_downsample_workspace_bytes, 16-byte aligned, caller-owned), plus the one-block sums.  No host synchronisation, no memcpy.
+ * sigma_out (nvol floats on the device) may be NULL.
+ * Refused before the device is touched, the message naming the argument: NULL vel, mag, params, out_vel, out_mag or workspace,
+ * nvol outside 1..65535, an extent outside 1..1024, a crop outside 1..N/2, an output range that overlaps an input range or the other
+ * output.  The workspace query returns 0 for arguments the call would refuse. */
+size_t fdn_kspace_downsample_workspace_bytes(int nvol, int X, int Y, int Z, int cx, int cy, int cz);
+int fdn_kspace_downsample(const float* vel, const float* mag, const float* params, int nvol, int X, int Y, int Z, int cx, int cy, int cz,
+                          const float* noise, uint64_t seed, uint64_t stream_id, float* out_vel, float* out_mag, float* sigma_out,
+                          void* workspace, void* stream);
+
 /* sum of squares of the kernel (non-bias) parameters: the l2(5e-7) regulariser value is 5e-7 * out[0].
  * src/Network/TrainerController.py:129-141.  is_kernel: one byte per parameter. */
 int fdn_l2_sumsq(const float* w, const uint8_t* is_kernel, int64_t n, float* out, void* stream);

@@ -16,12 +16,16 @@ parallel = importlib.import_module("4dflownet_amd.parallel")
 trainer = importlib.import_module("4dflownet_amd.trainer")
 
 
-def make_handler(data_dir, patch_size, res_increase, batch_size, mask_threshold):
-    """(handler, kwargs for initialize_dataset): the on-device loader unless FDN_HOST_LOADER is set."""
+def make_handler(data_dir, patch_size, res_increase, batch_size, mask_threshold, resynthesize=None):
+    """(handler, kwargs for initialize_dataset): the on-device loader unless FDN_HOST_LOADER is set.  resynthesize (device loader only):
+    see DevicePatchHandler3D."""
     if os.environ.get("FDN_HOST_LOADER", "0") not in ("", "0"):
+        if resynthesize is not None:
+            raise ValueError("resynthesize needs the on-device loader (unset FDN_HOST_LOADER)")
         return data.PatchHandler3D(data_dir, patch_size, res_increase, batch_size, mask_threshold), {"pinned": True}
     data_device = importlib.import_module("4dflownet_amd.data_device")
-    return data_device.DevicePatchHandler3D(data_dir, patch_size, res_increase, batch_size, mask_threshold), {}
+    extra = {} if resynthesize is None else {"resynthesize": resynthesize}
+    return data_device.DevicePatchHandler3D(data_dir, patch_size, res_increase, batch_size, mask_threshold, **extra), {}
 
 
 if __name__ == "__main__":
@@ -40,6 +44,9 @@ if __name__ == "__main__":
     epochs = 60
     batch_size = 20
     accum_steps = 1          # optimiser step = accum_steps consecutive batches of batch_size (x ranks); 1 = the reference's schedule
+    # None = train on the low-res volumes of the files; dict(seed=s) = every epoch the training set's low-res volumes are synthesised anew
+    # on the device from the high-res ones (fresh noise, SNR, VENCs and magnitude level; DevicePatchHandler3D(resynthesize=...))
+    resynthesize = None
     mask_threshold = 0.6
     network_name = '4DFlowNet'
     patch_size = 16
@@ -54,7 +61,7 @@ if __name__ == "__main__":
     parallel.init_from_env()
     trainset = data.load_indexes(training_file)
     valset = data.load_indexes(validate_file)
-    z, kw = make_handler(data_dir, patch_size, res_increase, batch_size, mask_threshold)
+    z, kw = make_handler(data_dir, patch_size, res_increase, batch_size, mask_threshold, resynthesize=resynthesize)
     trainset = z.initialize_dataset(trainset, shuffle=True, n_parallel=None, **kw)
     valdh, kw = make_handler(data_dir, patch_size, res_increase, batch_size, mask_threshold)
     valset = valdh.initialize_dataset(valset, shuffle=True, n_parallel=None, **kw)
