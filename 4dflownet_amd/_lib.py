@@ -53,6 +53,9 @@ SIGNATURES = {
     "fdn_pack_patch_cores": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp]),
     "fdn_input_features_volume_oriented": (c_i, [c_fp] + [c_i] * 8 + [c_i64, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
     "fdn_unrotate_accumulate": (c_i, [c_fp, c_fp] + [c_i] * 6 + [c_fp]),
+    "fdn_input_features_volume_strided": (c_i, [c_fp] + [c_i] * 8 + [c_i64, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
+    "fdn_blend_patches": (c_i, [c_fp, c_fp] + [c_i] * 10 + [c_i64, c_i, c_fp]),
+    "fdn_finish_volume": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 4 + [c_fp]),
     "fdn_kspace_downsample_workspace_bytes": (c_sz, [c_i] * 7),
     "fdn_kspace_downsample": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 7 + [c_fp, c_u64, c_u64] + [c_fp] * 5),
     "fdn_l2_sumsq": (c_i, [c_fp, c_fp, c_i64, c_fp, c_fp]),
@@ -81,6 +84,7 @@ SIGNATURES = {
     "fdn_input_features_bf16": (c_i, [c_fp] * 8 + [c_i64, c_fp]),
     "fdn_input_features_volume_bf16": (c_i, [c_fp] + [c_i] * 8 + [c_i64, c_i, c_fp, c_fp, c_fp]),
     "fdn_input_features_volume_oriented_bf16": (c_i, [c_fp] + [c_i] * 8 + [c_i64, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
+    "fdn_input_features_volume_strided_bf16": (c_i, [c_fp] + [c_i] * 8 + [c_i64, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
     "fdn_conv3d_fwd_bf16": (c_i, [c_fp] * 7 + [c_i] * 10 + [c_f, c_fp]),
     "fdn_conv3d_wgrad_bf16_workspace_bytes": (c_sz, [c_i] * 7),
     "fdn_conv3d_wgrad_bf16": (c_i, [c_fp] * 6 + [c_sz] + [c_i] * 9 + [c_fp]),

@@ -22,10 +22,12 @@ __device__ __forceinline__ float norm3(float a, float b, float c) {
 // (src/Network/PatchHandler3D.py:97-108,166-274) would turn it -- voxel (a,b,c) reads the window voxel np.rot90 puts there, the zero
 // fill comes first, then the components are permuted and signed by multiplication (a padded zero under a negative sign is -0.0, as on
 // the host), and norm3 takes the permuted components in their new order.  0: the plain window.
+// stride: voxels the window advances by, P - 4 for the plain tiler and less for overlapping cores (fdn_input_features_volume_strided).
 struct InputGeom {
     int32_t P, X, Y, Z;
     int32_t nx, ny, nz, orient;
     int64_t g0;
+    int32_t stride;
 };
 
 template <typename T>
@@ -33,7 +35,7 @@ __global__ void input_features_kernel(const float* __restrict__ u, const float* 
                                       const float* __restrict__ mu, const float* __restrict__ mv,
                                       const float* __restrict__ mw, T* __restrict__ phase, T* __restrict__ pc,
                                       int64_t nvox, InputGeom geo) {
-    const int P = geo.P, E = P - 4;
+    const int P = geo.P, E = geo.stride;
     const int64_t per = (int64_t)P * P * P, plane = (int64_t)geo.X * geo.Y * geo.Z;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvox; i += (int64_t)gridDim.x * blockDim.x) {
         float a, b, c, ma, mb, mc;
@@ -856,7 +858,8 @@ static int input_features_t(const float* u, const float* v, const float* w, cons
 }
 template <typename T>
 static int input_features_volume_t(const char* who, const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz,
-                                   int64_t g0, int count, T* phase, T* pc, void* stream, int plane = 0, int k = 0) {
+                                   int64_t g0, int count, T* phase, T* pc, void* stream, int plane = 0, int k = 0, int stride = 0,
+                                   bool strided = false) {
     FDN_REQUIRE(frames && phase && pc, "%s: NULL argument", who);
     FDN_REQUIRE(F > 0 && X > 0 && Y > 0 && Z > 0, "%s: bad frames (F=%d, X=%d, Y=%d, Z=%d)", who, F, X, Y, Z);
     FDN_REQUIRE(P > 4 && P <= 1024, "%s: patch size P=%d must be in 5..1024 (the window advances by P - 4)", who, P);
@@ -867,9 +870,11 @@ static int input_features_volume_t(const char* who, const float* frames, int F, 
                 (long long)(g0 + count), (long long)((int64_t)F * nx * ny * nz));
     const int word = fdn_orient_word(plane, k, 0);
     FDN_REQUIRE(word >= 0, "%s: orientation (plane=%d, k=%d) is neither (0,0) nor plane in 1..3 with k in 1..3", who, plane, k);
+    FDN_REQUIRE(!strided || (stride >= 1 && stride <= P - 4), "%s: stride=%d must be in 1..P-4 = %d", who, stride, P - 4);
     const int64_t nvox = (int64_t)count * P * P * P;
     InputGeom geo{};
     geo.orient = plane ? word : 0;
+    geo.stride = strided ? stride : P - 4;
     geo.P = P; geo.X = X; geo.Y = Y; geo.Z = Z; geo.nx = nx; geo.ny = ny; geo.nz = nz; geo.g0 = g0;
     hipLaunchKernelGGL(input_features_kernel<T>, dim3(grid_for(nvox)), dim3(256), 0, (hipStream_t)stream, frames,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
@@ -905,6 +910,18 @@ extern "C" int fdn_input_features_volume_oriented_bf16(const float* frames, int 
                                                        void* stream) {
     return input_features_volume_t<uint16_t>("fdn_input_features_volume_oriented_bf16", frames, F, X, Y, Z, P, nx, ny, nz, g0, count, phase,
                                              pc, stream, plane, k);
+}
+
+extern "C" int fdn_input_features_volume_strided(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
+                                                 int count, int stride, int plane, int k, float* phase, float* pc, void* stream) {
+    return input_features_volume_t<float>("fdn_input_features_volume_strided", frames, F, X, Y, Z, P, nx, ny, nz, g0, count, phase, pc,
+                                          stream, plane, k, stride, true);
+}
+extern "C" int fdn_input_features_volume_strided_bf16(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz,
+                                                      int64_t g0, int count, int stride, int plane, int k, uint16_t* phase, uint16_t* pc,
+                                                      void* stream) {
+    return input_features_volume_t<uint16_t>("fdn_input_features_volume_strided_bf16", frames, F, X, Y, Z, P, nx, ny, nz, g0, count, phase,
+                                             pc, stream, plane, k, stride, true);
 }
 
 extern "C" int fdn_fold_halo(const float* dxpad0, const float* dxpad1, const float* dxpad2, int nsrc, const float* skip,

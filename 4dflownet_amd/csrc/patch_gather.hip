@@ -34,6 +34,13 @@ struct PatchDesc {          // one per (sample, output tensor); mirrored by data
 // (reads are strided for planes 2 and 3) and no two threads meet.
 // modes 5 and 6, fdn_kspace_downsample: one forward / inverse truncated-DFT stage of the low-res synthesis (kspace_dft.h), driven by the
 // by-value KspaceGeom; the only modes that are launched with dynamic LDS (the twiddle table).
+// mode 7, fdn_blend_patches: overlap-add stitching.  The cores advance by sg.stride < core HR voxels, so up to two cores per axis -- eight
+// per voxel -- cover an output voxel, each with the separable linear ramp of blend_weight.  The DESTINATION is walked: frames sg.f0 ..
+// sg.f0 + sg.nf - 1, rows sg.x0 .. sg.x0 + sg.xs - 1 (the slab the patches of the call can touch), one (voxel, component) per thread and
+// step.  The thread finds the covering patches from its coordinates, keeps those inside [g0, g0 + B) and adds them in ascending g:
+// acc = acc + fl(w * p), the multiply and the add rounded separately (blend_add).  No atomics, no two threads on one voxel, and the bits
+// do not depend on how the patch list is cut into calls that come in ascending g0.
+// mode 8, fdn_finish_volume: mode 2's finish on an accumulated fp32 volume, `pred` (F,3,Xo,Yo,Zo) -> `out` float64 of the same shape.
 struct StitchGeom {
     const float* pred;
     int64_t g0;
@@ -41,14 +48,82 @@ struct StitchGeom {
     int32_t nx, ny, nz, orient;
     const double* scale;    // mode 2 only
     int32_t first, divisor; // mode 4 only
+    int32_t stride, f0;     // mode 7 only: HR stride of the cores, first frame of the slab
+    int32_t nf, x0, xs;     // mode 7 only: frames of the slab, its first row and its rows
 };
+
+// Weight of HR core coordinate t in [0, cs) along one axis for patch i of n: the ramp (2t+1)/(2r) over the first r = cs - stride voxels
+// where a lower neighbour overlaps, (2(cs-t)-1)/(2r) over the last r where an upper one does, 1 elsewhere.  One correctly rounded divide;
+// the two ramps of an overlap sum to 1.  r <= cs - r (at most two cores overlap), so the two conditions exclude each other.
+__device__ __forceinline__ float blend_weight(int i, int n, int t, int cs, int r) {
+    if (i > 0 && t < r) return (float)(2 * t + 1) / (float)(2 * r);
+    if (i < n - 1 && t >= cs - r) return (float)(2 * (cs - t) - 1) / (float)(2 * r);
+    return 1.f;
+}
+
+// acc + fl(w * p): never contracted into a fused multiply-add, whatever the surrounding code invites the compiler to do
+__device__ __forceinline__ float blend_add(float acc, float w, float p) {
+#pragma clang fp contract(off)
+    const float t = w * p;
+    return acc + t;
+}
 
 __global__ __launch_bounds__(256) void gather_patches_kernel(const PatchDesc* __restrict__ desc, float* __restrict__ out, int B,
                                                               int S, int mode, StitchGeom sg, KspaceGeom kg) {
-    if (mode >= 5) {                                                    // fdn_kspace_downsample: 5 a forward stage, 6 an inverse one
+    if (mode == 5 || mode == 6) {                                       // fdn_kspace_downsample: 5 a forward stage, 6 an inverse one
         extern __shared__ __attribute__((aligned(16))) float ks_lds[];
         if (mode == 5) fdn_ks_stage<false>(kg, ks_lds);
         else fdn_ks_stage<true>(kg, ks_lds);
+        return;
+    }
+    if (mode == 8) {
+        const int64_t per = (int64_t)3 * sg.Xo * sg.Yo * sg.Zo;
+        const int64_t total = per * B;                                  // B frames
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t f = i / per;
+            double d = (double)sg.pred[i] * sg.scale[2 * f];            // de-normalise (:103)
+            if (fabs(d) < sg.scale[2 * f + 1]) d = 0.0;                 // strict: a product equal to the threshold stays (:104-107)
+            ((double*)out)[i] = d;
+        }
+        return;
+    }
+    if (mode == 7) {
+        const int cs = S - 2 * sg.side, sh = sg.stride, r = cs - sh;
+        const int64_t yz = (int64_t)sg.Yo * sg.Zo;
+        const int64_t per = 3 * sg.xs * yz;                              // one frame of the slab
+        const int64_t total = per * sg.nf;
+        const int64_t g1 = sg.g0 + B;
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t fl = i / per;
+            int64_t q = i - fl * per;
+            const int comp = (int)(q / (sg.xs * yz)); q -= comp * (sg.xs * yz);
+            const int xl = (int)(q / yz); q -= xl * yz;
+            const int y = (int)(q / sg.Zo), z = (int)(q - (int64_t)y * sg.Zo);
+            const int x = sg.x0 + xl;
+            const int64_t f = sg.f0 + fl;
+            // per axis: the last patch that starts at or before the voxel, and the one before it where its core still reaches the voxel
+            const int i1 = min(x / sh, sg.nx - 1), j1 = min(y / sh, sg.ny - 1), k1 = min(z / sh, sg.nz - 1);
+            const int i0 = (i1 > 0 && x - (i1 - 1) * sh < cs) ? i1 - 1 : i1;
+            const int j0 = (j1 > 0 && y - (j1 - 1) * sh < cs) ? j1 - 1 : j1;
+            const int k0 = (k1 > 0 && z - (k1 - 1) * sh < cs) ? k1 - 1 : k1;
+            const int64_t dst = (((f * 3 + comp) * sg.Xo + x) * sg.Yo + y) * sg.Zo + z;
+            float v = 0.f;
+            bool touched = false;
+            for (int pi = i0; pi <= i1; ++pi)
+                for (int pj = j0; pj <= j1; ++pj)
+                    for (int pk = k0; pk <= k1; ++pk) {                  // ascending g
+                        const int64_t g = ((f * sg.nx + pi) * sg.ny + pj) * sg.nz + pk;
+                        if (g < sg.g0 || g >= g1) continue;
+                        const int a = x - pi * sh, b = y - pj * sh, c = z - pk * sh;
+                        const float w = blend_weight(pi, sg.nx, a, cs, r) * blend_weight(pj, sg.ny, b, cs, r) *
+                                        blend_weight(pk, sg.nz, c, cs, r);           // fl(fl(wx * wy) * wz)
+                        const int64_t n = g - sg.g0;
+                        const float p = sg.pred[(((n * S + sg.side + a) * S + sg.side + b) * S + sg.side + c) * 3 + comp];
+                        if (!touched) { v = out[dst]; touched = true; }
+                        v = blend_add(v, w, p);
+                    }
+            if (touched) out[dst] = v;
+        }
         return;
     }
     if (mode == 4) {
@@ -169,6 +244,62 @@ extern "C" int fdn_stitch_patches(const float* pred, float* vol, int F, int Xo, 
 extern "C" int fdn_stitch_patches_finish(const float* pred, double* vol, const double* frame_scale, int F, int Xo, int Yo, int Zo, int S,
                                          int side, int nx, int ny, int nz, int64_t g0, int count, void* stream) {
     return stitch_launch("fdn_stitch_patches_finish", pred, vol, frame_scale, 2, F, Xo, Yo, Zo, S, side, nx, ny, nz, g0, count, stream);
+}
+
+extern "C" int fdn_blend_patches(const float* pred, float* acc, int F, int Xo, int Yo, int Zo, int S, int side, int stride_hr, int nx,
+                                 int ny, int nz, int64_t g0, int count, void* stream) {
+    const char* who = "fdn_blend_patches";
+    FDN_REQUIRE(pred && acc, "%s: NULL argument", who);
+    FDN_REQUIRE(side >= 0 && S > 2 * side && S <= 512, "%s: S=%d must exceed 2*side (side=%d) and not 512", who, S, side);
+    FDN_REQUIRE(F > 0 && nx > 0 && ny > 0 && nz > 0, "%s: bad frame / patch counts (F=%d, %d,%d,%d)", who, F, nx, ny, nz);
+    FDN_REQUIRE(count > 0, "%s: count=%d", who, count);
+    FDN_REQUIRE(g0 >= 0, "%s: g0=%lld", who, (long long)g0);
+    FDN_REQUIRE(g0 + count <= (int64_t)F * nx * ny * nz, "%s: patches [%lld, %lld) exceed F*nx*ny*nz = %lld", who,
+                (long long)g0, (long long)(g0 + count), (long long)((int64_t)F * nx * ny * nz));
+    const int64_t cs = S - 2 * side;
+    FDN_REQUIRE(stride_hr >= 1 && stride_hr <= cs, "%s: stride_hr=%d must be in 1..S-2*side = %lld", who, stride_hr, (long long)cs);
+    FDN_REQUIRE(2 * (cs - stride_hr) <= cs, "%s: stride_hr=%d lets more than two cores of edge %lld overlap per axis", who, stride_hr,
+                (long long)cs);
+    const int64_t sh = stride_hr;
+    FDN_REQUIRE(Xo > 0 && Yo > 0 && Zo > 0 && Xo <= (nx - 1) * sh + cs && Yo <= (ny - 1) * sh + cs && Zo <= (nz - 1) * sh + cs,
+                "%s: output extents (%d,%d,%d) must be in 1..(n-1)*stride_hr+(S-2*side) = (%lld,%lld,%lld)", who, Xo, Yo, Zo,
+                (long long)((nx - 1) * sh + cs), (long long)((ny - 1) * sh + cs), (long long)((nz - 1) * sh + cs));
+    // the slab of the destination the patches of this call can touch: their frames, and within a single frame the rows of their
+    // patch planes (a call that spans frames walks them whole)
+    const int64_t per_frame = (int64_t)nx * ny * nz, yzp = (int64_t)ny * nz;
+    const int64_t f0 = g0 / per_frame, f1 = (g0 + count - 1) / per_frame;
+    int64_t x0 = 0, x1 = Xo;
+    if (f0 == f1) {
+        const int64_t i0 = (g0 - f0 * per_frame) / yzp, i1 = (g0 + count - 1 - f0 * per_frame) / yzp;
+        x0 = i0 * sh;
+        x1 = i1 * sh + cs < Xo ? i1 * sh + cs : Xo;
+        if (x0 >= x1) return FDN_OK;                                     // every patch of the call lies in the cropped far pad
+    }
+    StitchGeom sg{};
+    sg.pred = pred; sg.g0 = g0; sg.Xo = Xo; sg.Yo = Yo; sg.Zo = Zo; sg.side = side; sg.nx = nx; sg.ny = ny; sg.nz = nz;
+    sg.stride = stride_hr; sg.f0 = (int32_t)f0; sg.nf = (int32_t)(f1 - f0 + 1); sg.x0 = (int32_t)x0; sg.xs = (int32_t)(x1 - x0);
+    const int64_t total = (int64_t)sg.nf * 3 * sg.xs * Yo * Zo;
+    int64_t nb = (total + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    hipLaunchKernelGGL(gather_patches_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const PatchDesc*)nullptr, acc,
+                       count, S, 7, sg, KspaceGeom{});
+    FDN_CHECK_LAUNCH("gather_patches_kernel");
+    return FDN_OK;
+}
+
+extern "C" int fdn_finish_volume(const float* acc, double* vol, const double* frame_scale, int F, int Xo, int Yo, int Zo, void* stream) {
+    const char* who = "fdn_finish_volume";
+    FDN_REQUIRE(acc && vol && frame_scale, "%s: NULL argument", who);
+    FDN_REQUIRE(F > 0 && Xo > 0 && Yo > 0 && Zo > 0, "%s: bad volume (F=%d, %d,%d,%d)", who, F, Xo, Yo, Zo);
+    const int64_t total = (int64_t)F * 3 * Xo * Yo * Zo;
+    int64_t nb = (total + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    StitchGeom sg{};
+    sg.pred = acc; sg.Xo = Xo; sg.Yo = Yo; sg.Zo = Zo; sg.scale = frame_scale;
+    hipLaunchKernelGGL(gather_patches_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const PatchDesc*)nullptr,
+                       (float*)vol, F, 0, 8, sg, KspaceGeom{});
+    FDN_CHECK_LAUNCH("gather_patches_kernel");
+    return FDN_OK;
 }
 
 extern "C" int fdn_pack_patch_cores(const float* pred, float* cores, int S, int side, int count, void* stream) {

@@ -126,9 +126,12 @@ def self_ensemble_orientations(self_ensemble):
     return res
 
 
-def _input_features_volume(entry, act_dtype, frames, patch_size, counts, g0, count, phase, pc, orientation=None):
+def _input_features_volume(entry, act_dtype, frames, patch_size, counts, g0, count, phase, pc, orientation=None, stride=None):
     """input_features_volume of either storage type: `entry` names the library's entry point, act_dtype is the type of phase / pc."""
     plane, k = _orientation(orientation, "input_features_volume")
+    if stride is not None:
+        if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 1 <= stride <= int(patch_size) - 4:
+            raise ValueError("input_features_volume: stride must be an integer in 1..patch_size-4 = %d, got %r" % (int(patch_size) - 4, stride))
     geo = _volume_geometry(frames, patch_size, counts, g0, count, "input_features_volume")
     P, count = geo[4], geo[9]
     if phase is None:
@@ -137,19 +140,25 @@ def _input_features_volume(entry, act_dtype, frames, patch_size, counts, g0, cou
         pc = torch.empty((max(count, 0), P, P, P, 3), device=frames.device, dtype=act_dtype)
     if min(phase.numel(), pc.numel()) < max(count, 0) * P ** 3 * 3:
         raise FdnError("input_features_volume: phase / pc hold fewer than (%d,%d,%d,%d,3) elements" % (count, P, P, P))
-    if plane:                                                 # (0, 0) is the plain entry point
+    if stride is not None:                                    # the window of overlapping cores (tiler.PatchGenerator(blend=))
+        entry = entry.replace("_volume", "_volume_strided")
+        geo = geo + (int(stride), plane, k)
+    elif plane:                                               # (0, 0) is the plain entry point
         entry = entry.replace("_volume", "_volume_oriented")
         geo = geo + (plane, k)
     check(getattr(_lib.load(), entry)(_p(frames, "frames"), *geo, _ptr(act_dtype, phase, "phase"), _ptr(act_dtype, pc, "pc"), _stream()), entry)
     return phase, pc
 
 
-def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None, orientation=None):
+def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None, stride=None, orientation=None):
     """input_features of patches [g0, g0 + count) of the sliding window over resident frames (F,6,X,Y,Z) (u,v,w,mag_u,mag_v,mag_w,
     normalised): the patches are never materialised.  counts = (nx,ny,nz) of tiler.PatchGenerator.plan; patch g = frame g // (nx*ny*nz),
     then (i,j,k) with k fastest.  Returns (phase, pc), each (count,P,P,P,3).
-    orientation=(plane, k): the features of the patches as data.rotate_vector_field turns them (fdn_input_features_volume_oriented)."""
-    return _input_features_volume("fdn_input_features_volume", ACT_DTYPE, frames, patch_size, counts, g0, count, phase, pc, orientation)
+    orientation=(plane, k): the features of the patches as data.rotate_vector_field turns them (fdn_input_features_volume_oriented).
+    stride (None: patch_size - 4): the voxels the window advances by, with counts of PatchGenerator(blend=).plan
+    (fdn_input_features_volume_strided); ValueError outside 1..patch_size-4."""
+    return _input_features_volume("fdn_input_features_volume", ACT_DTYPE, frames, patch_size, counts, g0, count, phase, pc, orientation,
+                                  stride)
 
 
 def unrotate_accumulate(pred, acc, orientation, first, divisor=1):
@@ -253,6 +262,39 @@ def stitch_patches(pred, vol, side, counts, g0=0, frame_scale=None):
                                                 F, Xo, Yo, Zo, S, int(side), nx, ny, nz, int(g0), pred.shape[0], _stream()),
           "fdn_stitch_patches_finish")
     return vol
+
+
+def blend_patches(pred, acc, side, stride_hr, counts, g0=0):
+    """Overlap-add stitching (fdn_blend_patches): the cores of the predicted patches [g0, g0 + len(pred)) -- pred (count,S,S,S,3), core =
+    S - 2*side, advancing by stride_hr HR voxels -- are added with their linear-ramp weights into acc (F,3,Xo,Yo,Zo) fp32, which the
+    caller zeroes once per volume.  acc = acc + fl(w * p) per covering patch in ascending g: calls in ascending g0 give the same bits
+    however the patch list is cut.  side = 0: cores packed by pack_patch_cores.  Returns acc."""
+    S = _pred_edge(pred, "blend_patches")
+    if acc.dim() != 5 or acc.shape[1] != 3:
+        raise FdnError("blend_patches: acc must be (F,3,Xo,Yo,Zo), got %s" % (tuple(acc.shape),))
+    F, _, Xo, Yo, Zo = acc.shape
+    nx, ny, nz = (int(n) for n in counts)
+    check(_lib.load().fdn_blend_patches(_p(pred, "pred"), _p(acc, "acc"), F, Xo, Yo, Zo, S, int(side), int(stride_hr), nx, ny, nz, int(g0),
+                                        pred.shape[0], _stream()), "fdn_blend_patches")
+    return acc
+
+
+def finish_volume(acc, frame_scale, out=None):
+    """The predictor's post-processing on an accumulated volume (fdn_finish_volume): acc (F,3,Xo,Yo,Zo) fp32 -> float64 of the same shape,
+    acc * venc with +0.0 where the magnitude is below the threshold; frame_scale a float64 device tensor (F,2) of {venc, threshold} per
+    frame (the rule of stitch_patches(frame_scale=))."""
+    if acc.dim() != 5 or acc.shape[1] != 3:
+        raise FdnError("finish_volume: acc must be (F,3,Xo,Yo,Zo), got %s" % (tuple(acc.shape),))
+    F, _, Xo, Yo, Zo = acc.shape
+    if tuple(frame_scale.shape) != (F, 2):
+        raise FdnError("finish_volume: frame_scale must be (F,2) = (%d,2), got %s" % (F, tuple(frame_scale.shape)))
+    if out is None:
+        out = torch.empty(tuple(acc.shape), device=acc.device, dtype=torch.float64)
+    elif tuple(out.shape) != tuple(acc.shape):
+        raise FdnError("finish_volume: out must be %s, got %s" % (tuple(acc.shape), tuple(out.shape)))
+    check(_lib.load().fdn_finish_volume(_p(acc, "acc"), _p64(out, "out"), _p64(frame_scale, "frame_scale"), F, Xo, Yo, Zo, _stream()),
+          "fdn_finish_volume")
+    return out
 
 
 def pack_patch_cores(pred, side, out=None):

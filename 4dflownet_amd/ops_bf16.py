@@ -12,7 +12,7 @@ import torch
 from . import _lib
 from ._lib import FdnError, check
 from .ops import (ACT_NONE, ACT_RELU, ACT_LEAKY, LEAKY_ALPHA, ALGO_AUTO, ROLE_FWD, _stream, loss_metrics, l2_sumsq, adam_step,  # noqa: F401
-                  stitch_patches, pack_patch_cores, unrotate_accumulate, self_ensemble_orientations, volume_metrics, _ptr, _p as _pf, _mask_ptr,
+                  stitch_patches, pack_patch_cores, blend_patches, finish_volume, unrotate_accumulate, self_ensemble_orientations, volume_metrics, _ptr, _p as _pf, _mask_ptr,
                   _input_features, _input_features_volume, _pack_conv64_weights, _conv_cout1_dgrad_folded, _dgrad_fused_multi, _fold_halo_border,
                   _conv1x1_dgrad, _conv3d_wgrad, _wgrad_batch, _upsample_trilinear_fwd, _upsample_trilinear_bwd)
 
@@ -26,9 +26,10 @@ def input_features(u, v, w, mu, mv, mw, phase=None, pc=None):
     return _input_features("fdn_input_features_bf16", BF16, u, v, w, mu, mv, mw, phase, pc)
 
 
-def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None, orientation=None):
+def input_features_volume(frames, patch_size, counts, g0=0, count=None, phase=None, pc=None, stride=None, orientation=None):
     """ops.input_features_volume with bf16 phase / pc (the frames stay fp32)."""
-    return _input_features_volume("fdn_input_features_volume_bf16", BF16, frames, patch_size, counts, g0, count, phase, pc, orientation)
+    return _input_features_volume("fdn_input_features_volume_bf16", BF16, frames, patch_size, counts, g0, count, phase, pc, orientation,
+                                  stride)
 
 
 def pack_conv64_weights(w, wp_fwd=None, wp_dgrad=None, want_dgrad=True):

@@ -15,7 +15,7 @@ from . import h5io, parallel
 from .data import ImageDataset
 from .network import Input, SR4DFlowNet
 from .ops import self_ensemble_orientations
-from .tiler import PatchGenerator
+from .tiler import PatchGenerator, check_blend
 
 
 def prepare_network(patch_size, res_increase, low_resblock, hi_resblock, device=None, dtype="float32"):
@@ -184,24 +184,26 @@ def _ensemble_acc(network, batch_size, S):
     return st[1]
 
 
-def _predict_batch(network, frames, patch_size, counts, g0, count, batch_size, orientations):
+def _predict_batch(network, frames, patch_size, counts, g0, count, batch_size, orientations, stride=None):
     """The predictions (count,S,S,S,3) fp32 of global patches [g0, g0 + count) of resident frames.  orientations (a tuple of (plane, k),
     or None): for each one in order the features are formed in the rotated frame (ops.input_features_volume(orientation=)), the network
     runs on them and the prediction is turned back into the accumulator (ops.unrotate_accumulate); the last one divides by their
-    number.  The mean lives in the accumulator until the next batch: the caller stitches or packs it before asking for another."""
+    number.  The mean lives in the accumulator until the next batch: the caller stitches or packs it before asking for another.
+    stride (None: patch_size - 4): the window's advance for overlapping cores (PatchGenerator(blend=).stride)."""
+    window = {} if stride is None else {"stride": stride}
     if orientations is None:
-        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, count)
+        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, count, **window)
         return network.forward_features(phase, pc)
     acc = _ensemble_acc(network, batch_size, patch_size * network.res_increase)[:count]
     last = len(orientations) - 1
     for j, o in enumerate(orientations):
-        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, count, orientation=o)
+        phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, count, orientation=o, **window)
         network.ops.unrotate_accumulate(network.forward_features(phase, pc), acc, o, first=j == 0,
                                         divisor=len(orientations) if j == last else 1)
     return acc
 
 
-def predict_volume(network, frames, patch_size, batch_size, out=None, frame_scale=None, patch_range=None, self_ensemble=None):
+def predict_volume(network, frames, patch_size, batch_size, out=None, frame_scale=None, patch_range=None, self_ensemble=None, blend=0):
     """Sliding-window inference with the tiler on the device (predictor.py:67-115 without its host work).  frames: (F,6,X,Y,Z)
     normalised fp32 (u,v,w,mag_u,mag_v,mag_w as ImageDataset.load_vectorfield leaves them), numpy or a device tensor; they are
     uploaded once.  Runs batches of `batch_size` consecutive global patches -- a batch may span two frames, so only the last one is
@@ -215,24 +217,39 @@ def predict_volume(network, frames, patch_size, batch_size, out=None, frame_scal
     patches are left as they are.  Everything is queued on the current stream.
     self_ensemble ("rot90", or a sequence of (plane, k) orientations; ops.self_ensemble_orientations): every batch is predicted under each
     orientation -- the rotations the loader trains with, data.rotate_vector_field -- turned back and averaged in fp32 on the device before
-    it is stitched (_predict_batch): len(orientations) forwards per patch.  None, False or [(0, 0)]: the plain path."""
+    it is stitched (_predict_batch): len(orientations) forwards per patch.  None, False or [(0, 0)]: the plain path.
+    blend=b > 0 (tiler.PatchGenerator(blend=b); 2*b <= patch_size - 4, else ValueError): overlap-add stitching.  Neighbouring cores overlap
+    by b low-res voxels -- (E/(E-b))^3 times the patches, E = patch_size - 4 -- and every batch (the averaged one under self_ensemble) is
+    added with its linear-ramp weights into an fp32 accumulator (ops.blend_patches), in ascending patch order: the bits do not depend on
+    batch_size.  Without frame_scale the accumulator is the result: a fresh zeroed tensor, or `out`, which the caller zeroed and which
+    is ADDED to -- this is how patch_range parts, run in ascending order, compose to the whole.  With frame_scale the accumulator is
+    internal and the float64 output is finished from it at the end (ops.finish_volume): it holds the patches of patch_range alone."""
+    blend = check_blend(blend, patch_size, "predict_volume")
     orientations = _orientations(self_ensemble)
     frames = network._to_dev(frames)
     if frames.dim() != 5 or frames.shape[1] != 6:
         raise ValueError("predict_volume: frames must be (F,6,X,Y,Z), got %s" % (tuple(frames.shape),))
     R = network.res_increase
     F = frames.shape[0]
-    counts, _, extents = PatchGenerator(patch_size, R).plan(tuple(frames.shape[2:]))
+    pgen = PatchGenerator(patch_size, R, blend)
+    counts, _, extents = pgen.plan(tuple(frames.shape[2:]))
     scale = None if frame_scale is None else _frame_scale_tensor(frame_scale, F, frames.device)
     dtype = torch.float32 if scale is None else torch.float64
     if out is None:
-        out = torch.empty((F, 3) + extents, device=frames.device, dtype=dtype)    # every voxel belongs to one patch core
+        # without blend every voxel belongs to one patch core; with it the fp32 result is accumulated into
+        out = (torch.zeros if blend and scale is None else torch.empty)((F, 3) + extents, device=frames.device, dtype=dtype)
     elif tuple(out.shape) != (F, 3) + extents or out.dtype != dtype:
         raise ValueError("predict_volume: out must be %s %s, got %s %s" % (dtype, (F, 3) + extents, out.dtype, tuple(out.shape)))
     total = F * counts[0] * counts[1] * counts[2]
     lo, hi = (0, total) if patch_range is None else (int(patch_range[0]), int(patch_range[1]))
     if not 0 <= lo <= hi <= total:
         raise ValueError("predict_volume: patch_range (%d, %d) outside [0, %d]" % (lo, hi, total))
+    if blend:
+        acc = out if scale is None else torch.zeros((F, 3) + extents, device=frames.device, dtype=torch.float32)
+        for g0 in range(lo, hi, batch_size):
+            pred = _predict_batch(network, frames, patch_size, counts, g0, min(batch_size, hi - g0), batch_size, orientations, pgen.stride)
+            network.ops.blend_patches(pred, acc, 2 * R, pgen.stride * R, counts, g0)
+        return out if scale is None else network.ops.finish_volume(acc, scale, out=out)
     for g0 in range(lo, hi, batch_size):
         pred = _predict_batch(network, frames, patch_size, counts, g0, min(batch_size, hi - g0), batch_size, orientations)
         network.ops.stitch_patches(pred, out, 2 * R, counts, g0, frame_scale=scale)
@@ -247,18 +264,22 @@ def shard_frame_span(lo, hi, per_frame):
     return lo // per_frame, (hi - 1) // per_frame + 1
 
 
-def predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=0, self_ensemble=None):
+def predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=0, self_ensemble=None, blend=0):
     """The shard of a data-parallel rank: global patches [lo, hi) in batches of `batch_size` consecutive patches, the core of every
     prediction packed (ops.pack_patch_cores) into ONE (hi - lo, c, c, c, 3) fp32 device buffer, c = (patch_size - 4) * R -- what the
     rank sends; the receiver stitches it with side 0 at g0 = lo.  frames as in predict_volume; they may hold only the frames the range
     touches (shard_frame_span), first_frame being the global index of frames[0].  self_ensemble: as in predict_volume; the mean over the
-    orientations is formed before the cores are packed, so what travels and what the receiver does are the same."""
+    orientations is formed before the cores are packed, so what travels and what the receiver does are the same.
+    blend: as in predict_volume -- the patches are those of the overlapping window; the receiver blends the cores (ops.blend_patches with
+    side 0 at g0 = lo) instead of stitching them."""
+    blend = check_blend(blend, patch_size, "predict_cores")
     orientations = _orientations(self_ensemble)
     frames = network._to_dev(frames)
     if frames.dim() != 5 or frames.shape[1] != 6:
         raise ValueError("predict_cores: frames must be (F,6,X,Y,Z), got %s" % (tuple(frames.shape),))
     R = network.res_increase
-    counts, _, _ = PatchGenerator(patch_size, R).plan(tuple(frames.shape[2:]))
+    pgen = PatchGenerator(patch_size, R, blend)
+    counts, _, _ = pgen.plan(tuple(frames.shape[2:]))
     per_frame = counts[0] * counts[1] * counts[2]
     lo, hi, base = int(lo), int(hi), int(first_frame) * per_frame
     if not base <= lo <= hi <= base + frames.shape[0] * per_frame:
@@ -268,7 +289,8 @@ def predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=0
     cores = torch.empty((hi - lo, c, c, c, 3), device=frames.device, dtype=torch.float32)
     for s in range(lo, hi, batch_size):
         e = min(s + batch_size, hi)
-        pred = _predict_batch(network, frames, patch_size, counts, s - base, e - s, batch_size, orientations)
+        pred = _predict_batch(network, frames, patch_size, counts, s - base, e - s, batch_size, orientations,
+                              pgen.stride if blend else None)
         network.ops.pack_patch_cores(pred, 2 * R, out=cores[s - lo:e - lo])
     return cores
 
@@ -336,7 +358,7 @@ def _recv_cores(network, shapes):
 
 
 def _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size, round_small_values, verbose,
-                         frames_per_group, on_group=None, device_finish=None, self_ensemble=None):
+                         frames_per_group, on_group=None, device_finish=None, self_ensemble=None, blend=0):
     """predict_file with the tiler on the device: rows in groups whose frames and stitched output fit DEVICE_TILER_GROUP_BYTES (or
     frames_per_group rows), one predict_volume per group, de-normalised and zeroed inside its stitch launches (frame_scale); the
     finished float64 group travels to pinned host memory on the copy stream while the next group computes and is then appended exactly
@@ -347,7 +369,11 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
     on_group(rows, vol): called on rank 0 for every group once it is stitched (the peers' cores included), before the copy-out, with the
     row numbers and the group's (len(rows),3,X*R,Y*R,Z*R) device tensor; what it queues on the current stream runs before the next group
     (evaluate_file).  output_filepath=None: no staging buffers, no copy to the host and no file; nothing is returned per row.
-    device_finish: overrides FDN_DEVICE_FINISH.  self_ensemble: handed to predict_volume and, on the peers, predict_cores."""
+    device_finish: overrides FDN_DEVICE_FINISH.  self_ensemble: handed to predict_volume and, on the peers, predict_cores.
+    blend > 0: overlap-add stitching (predict_volume(blend=)).  Rank 0 blends its own batches into the group's fp32 accumulator, then every
+    peer's cores with side 0 at that peer's first patch, in rank order -- ascending patch order, so the bits are those of a single rank --
+    and finishes the accumulator into the float64 group (ops.finish_volume); the byte budget counts the accumulator."""
+    blend = check_blend(blend, patch_size, "predict_file")
     orientations = _orientations(self_ensemble)
     world, rank = parallel.world_size(), parallel.rank()
     if device_finish is None:
@@ -360,10 +386,12 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
     lr_shape = dataset.get_volume_shape(input_filepath)
     R = res_increase
     if frames_per_group is None:                                       # depends on the file alone: all ranks walk the same groups
-        per_frame = int(np.prod(lr_shape)) * (24 + (24 if device_finish else 12) * R ** 3)
+        # the six fp32 inputs, the stitched output (float64 when finished here) and, under blend, the fp32 accumulator beside it
+        per_frame = int(np.prod(lr_shape)) * (24 + ((36 if blend else 24) if device_finish else 12) * R ** 3)
         frames_per_group = max(1, DEVICE_TILER_GROUP_BYTES // per_frame)
     fpg = max(1, min(int(frames_per_group), nr_rows))
-    counts, _, _ = PatchGenerator(patch_size, R).plan(lr_shape)
+    pgen = PatchGenerator(patch_size, R, blend)
+    counts, _, _ = pgen.plan(lr_shape)
     per_frame_patches = counts[0] * counts[1] * counts[2]
     core = (patch_size - 4) * R
 
@@ -386,7 +414,7 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
                 f0, f1 = shard_frame_span(lo, hi, per_frame_patches)
                 frames, _ = load(list(range(r0 + f0, r0 + f1)))
                 _send_cores(network, predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=f0,
-                                                   self_ensemble=orientations))
+                                                   self_ensemble=orientations, blend=blend))
         return written
 
     write = output_filepath is not None
@@ -429,12 +457,17 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
         if device_finish:                                              # the doubles the host finish multiplies and compares with
             scale = _frame_scale_tensor([(venc, vpp if round_small_values else 0.0) for venc, vpp, _ in meta], len(rows), network.device)
         bounds = shard_bounds(len(rows) * per_frame_patches, world)
-        vol = predict_volume(network, frames, patch_size, batch_size, frame_scale=scale, patch_range=(bounds[0], bounds[1]),
-                             self_ensemble=orientations)
+        vol = predict_volume(network, frames, patch_size, batch_size, frame_scale=None if blend else scale,
+                             patch_range=(bounds[0], bounds[1]), self_ensemble=orientations, blend=blend)
         peers = {r: (bounds[r + 1] - bounds[r], core, core, core, 3) for r in range(1, world) if bounds[r + 1] > bounds[r]}
         if peers:                                                      # posted after the own shard (see predict_patches)
-            for r, cores in _recv_cores(network, peers).items():
-                network.ops.stitch_patches(cores, vol, 0, counts, bounds[r], frame_scale=scale)
+            for r, cores in sorted(_recv_cores(network, peers).items()):
+                if blend:
+                    network.ops.blend_patches(cores, vol, 0, pgen.stride * R, counts, bounds[r])
+                else:
+                    network.ops.stitch_patches(cores, vol, 0, counts, bounds[r], frame_scale=scale)
+        if blend and scale is not None:                                # the accumulator is complete: de-normalise and zero (:103-107)
+            vol = network.ops.finish_volume(vol, scale)
         if on_group is not None:
             on_group(rows, vol)
         if not write:
@@ -455,7 +488,7 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
 
 
 def predict_file(network, input_filepath, output_filepath, patch_size, res_increase, batch_size=8,
-                 round_small_values=True, verbose=True, device_tiler=False, frames_per_group=None, self_ensemble=None):
+                 round_small_values=True, verbose=True, device_tiler=False, frames_per_group=None, self_ensemble=None, blend=0):
     """predictor.py:67-115 for every row of the input file.  Returns the list of (u,v,w) volumes written (rank 0; the other ranks
     of a data-parallel run compute their shard of every row's patches and return an empty list).
     device_tiler=True (or FDN_DEVICE_TILER=1): patchify and stitch run on the device (predict_volume) over groups of rows --
@@ -465,11 +498,15 @@ def predict_file(network, input_filepath, output_filepath, patch_size, res_incre
     and writes (_predict_file_device).
     self_ensemble ("rot90" or a sequence of (plane, k) orientations, see predict_volume): every patch is predicted under each orientation
     and the predictions are averaged.  It exists on the device tiler only: when set, the file goes through _predict_file_device whatever
-    device_tiler says (FDN_DEVICE_FINISH=0 keeps working); the host tiler path below does not have it."""
+    device_tiler says (FDN_DEVICE_FINISH=0 keeps working); the host tiler path below does not have it.
+    blend=b > 0: overlap-add stitching, neighbouring cores overlap by b low-res voxels and are cross-faded (predict_volume(blend=));
+    like self_ensemble it goes through _predict_file_device whatever device_tiler says.  ValueError for a blend that is not an integer
+    with 0 <= blend and 2*blend <= patch_size - 4.  (PatchGenerator(blend=b) + predict_patches is the same computation on the host.)"""
+    blend = check_blend(blend, patch_size, "predict_file")
     orientations = _orientations(self_ensemble)
-    if orientations is not None or device_tiler or os.environ.get("FDN_DEVICE_TILER", "0") not in ("", "0"):
+    if blend or orientations is not None or device_tiler or os.environ.get("FDN_DEVICE_TILER", "0") not in ("", "0"):
         return _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size,
-                                    round_small_values, verbose, frames_per_group, self_ensemble=orientations)
+                                    round_small_values, verbose, frames_per_group, self_ensemble=orientations, blend=blend)
     pgen = PatchGenerator(patch_size, res_increase)
     dataset = ImageDataset()
     nr_rows = dataset.get_dataset_len(input_filepath)
@@ -549,7 +586,8 @@ def write_metrics_csv(csv_path, metrics, first_row=0):
 
 
 def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase, batch_size=8, round_small_values=True,
-                  output_filepath=None, csv_path=None, frames_per_group=None, verbose=True, return_sums=False, self_ensemble=None):
+                  output_filepath=None, csv_path=None, frames_per_group=None, verbose=True, return_sums=False, self_ensemble=None,
+                  blend=0):
     """Predict every row of the low-resolution file with the tiler on the device (_predict_file_device) and score the finished float64
     prediction, in m/s, against u, v, w of the same row of the high-resolution file (m/s as well: nothing is rescaled), where the
     prediction already is: ops.volume_metrics on every stitched group, 26 doubles per row to the host, metrics_from_sums there.  The
@@ -559,8 +597,10 @@ def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase
     predict_file(device_tiler=True) writes.  csv_path: write_metrics_csv.  Data-parallel: the peers send their cores as in
     _predict_file_device; rank 0 evaluates (and writes) and returns the list, the other ranks return [].
     self_ensemble: as in predict_file -- the scores are those of the averaged prediction, what the option buys on this checkpoint.
-    ValueError, before any GPU work: an invalid self_ensemble, the two files hold different numbers of rows, the HR volume is not
+    blend: as in predict_file -- the scores are those of the blended volume.
+    ValueError, before any GPU work: an invalid self_ensemble or blend, the two files hold different numbers of rows, the HR volume is not
     res_increase x the LR volume, or the mask has neither one row nor one per row."""
+    blend = check_blend(blend, patch_size, "evaluate_file")
     orientations = _orientations(self_ensemble)
     dataset = ImageDataset()
     nr_rows = dataset.get_dataset_len(input_filepath)
@@ -595,7 +635,7 @@ def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase
     t0 = time.time()
     _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size, round_small_values,
                          verbose and output_filepath is not None, frames_per_group, on_group=score, device_finish=True,
-                         self_ensemble=orientations)
+                         self_ensemble=orientations, blend=blend)
     if parallel.rank() != 0:
         return ([], np.empty((0, len(VOLUME_SUM_NAMES)))) if return_sums else []
     sums = np.empty((nr_rows, len(VOLUME_SUM_NAMES)), dtype=np.float64)
@@ -616,8 +656,9 @@ def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase
 def main(data_dir='../data', filename='example_data.h5', output_dir="../result", output_filename='example_result.h5',
          model_path="../models/4DFlowNet/4DFlowNet.h5", patch_size=24, res_increase=2, batch_size=8,
          round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32", device_tiler=False, frames_per_group=None,
-         self_ensemble=None):
-    """Same hard-coded surface as predictor.py:31-47 (+ dtype, + the device tiler switch and self_ensemble of predict_file)."""
+         self_ensemble=None, blend=0):
+    """Same hard-coded surface as predictor.py:31-47 (+ dtype, + the device tiler switch, self_ensemble and blend of predict_file)."""
+    check_blend(blend, patch_size, "main")
     parallel.init_from_env()
     network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype)
     network.load_weights(model_path)
@@ -625,7 +666,7 @@ def main(data_dir='../data', filename='example_data.h5', output_dir="../result",
         os.makedirs(output_dir)
     predict_file(network, '{}/{}'.format(data_dir, filename), '{}/{}'.format(output_dir, output_filename), patch_size,
                  res_increase, batch_size, round_small_values, device_tiler=device_tiler, frames_per_group=frames_per_group,
-                 self_ensemble=self_ensemble)
+                 self_ensemble=self_ensemble, blend=blend)
     if parallel.rank() == 0:
         print("Done!")
 
@@ -633,9 +674,10 @@ def main(data_dir='../data', filename='example_data.h5', output_dir="../result",
 def evaluate_main(data_dir='../data', filename='example_data.h5', hr_filename='example_data_HR.h5', output_dir="../result",
                   csv_filename='example_metrics.csv', output_filename=None, model_path="../models/4DFlowNet/4DFlowNet.h5", patch_size=24,
                   res_increase=2, batch_size=8, round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32",
-                  frames_per_group=None, self_ensemble=None):
+                  frames_per_group=None, self_ensemble=None, blend=0):
     """The surface of main() for scoring a checkpoint: + hr_filename, the ground truth beside `filename`, and csv_filename; the
     prediction itself is written only with output_filename."""
+    check_blend(blend, patch_size, "evaluate_main")
     parallel.init_from_env()
     network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype)
     network.load_weights(model_path)
@@ -644,7 +686,7 @@ def evaluate_main(data_dir='../data', filename='example_data.h5', hr_filename='e
     evaluate_file(network, '{}/{}'.format(data_dir, filename), '{}/{}'.format(data_dir, hr_filename), patch_size, res_increase, batch_size,
                   round_small_values, output_filepath=None if output_filename is None else '{}/{}'.format(output_dir, output_filename),
                   csv_path='{}/{}'.format(output_dir, csv_filename) if parallel.rank() == 0 else None, frames_per_group=frames_per_group,
-                  self_ensemble=self_ensemble)
+                  self_ensemble=self_ensemble, blend=blend)
     if parallel.rank() == 0:
         print("Done!")
 

@@ -354,6 +354,37 @@ int fdn_input_features_volume_oriented(const float* frames, int F, int X, int Y,
  * ranges that overlap. */
 int fdn_unrotate_accumulate(const float* pred, float* acc, int count, int S, int plane, int k, int first, int divisor, void* stream);
 
+/* Overlap-add stitching: neighbouring cores overlap by b low-res voxels and are cross-faded, which removes the step a one-verdict-per-voxel
+ * stitch leaves at every core boundary.  With E = P - 4 the window advances by stride = E - b (1 <= stride <= E, 2b <= E: at most two cores
+ * overlap per axis, eight per voxel); per axis nr = max(1, ceil((n - E) / stride) + 1) patches (tiler.PatchGenerator.plan_blend).
+ *
+ * fdn_input_features_volume_oriented with the window advancing by `stride`: voxel (a,b,c) of patch (i,j,k) reads source
+ * (i*stride + a - 2, j*stride + b - 2, k*stride + c - 2), zero outside the volume.  stride == P - 4 equals the oriented entry point bit
+ * for bit (and with (plane,k) = (0,0) the plain one).  A path of the same kernel (the by-value geometry carries the stride).  Refusals:
+ * those of fdn_input_features_volume_oriented, and stride < 1 or stride > P - 4. */
+int fdn_input_features_volume_strided(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
+                                      int count, int stride, int plane, int k, float* phase, float* pc, void* stream);
+/* The weighted accumulate.  pred (count,S,S,S,3) fp32, the predictions of global patches g0 .. g0 + count - 1; acc (F,3,Xo,Yo,Zo) fp32,
+ * zeroed by the caller once per volume.  core = S - 2*side, stride_hr = stride * res_increase, r = core - stride_hr the ramp width.  Core
+ * voxel t (per axis, 0 <= t < core) of patch i of nr has the weight  (float)(2t+1) / (float)(2r)  for t < r when i > 0 (a lower neighbour),
+ * (float)(2(core-t)-1) / (float)(2r)  for t >= core - r when i < nr - 1 (an upper neighbour), 1 elsewhere: one correctly rounded fp32
+ * divide each, the two ramps of an overlap sum to 1, and a volume face has no ramp.  The voxel weight is w = fl(fl(wx*wy)*wz).  For
+ * every output voxel and component the call does  acc = acc + fl(w_g * p_g)  for the patches g of the call whose core covers the voxel, in
+ * ascending g, the multiply and the add rounded separately (never fused).  The destination is walked -- each voxel finds its at most eight
+ * covering patches from its coordinates and keeps those inside [g0, g0 + count) -- over the slab of the frames the patches of the call can
+ * touch: no atomics, no two threads on one voxel, and after all patches of a volume the bits of acc do not depend on how [0, total) was
+ * cut into calls, as long as the calls come in ascending g0; numpy float32 reproduces them exactly.  Voxels no patch of the call covers
+ * are not written.  side = 0 with S = core blends cores packed by fdn_pack_patch_cores.  stride_hr == core is the disjoint stitch
+ * (acc = 0 + p).  A runtime mode of the gather kernel.  Refused before the device is touched: what fdn_stitch_patches refuses (with the
+ * extent limit (n-1)*stride_hr + core per axis: extents the counts do not cover), stride_hr < 1, stride_hr > core, 2*(core - stride_hr) > core. */
+int fdn_blend_patches(const float* pred, float* acc, int F, int Xo, int Yo, int Zo, int S, int side, int stride_hr, int nx, int ny, int nz,
+                      int64_t g0, int count, void* stream);
+/* The predictor's post-processing (src/predictor.py:103-107, src/utils/ImageDataset.py:31) on an accumulated volume: acc (F,3,Xo,Yo,Zo) fp32
+ * -> vol of the same shape in FLOAT64 with the device table frame_scale (F,2) of doubles {venc_f, threshold_f}: d = (double)acc * venc_f,
+ * +0.0 where fabs(d) < threshold_f (strict) -- the rule of fdn_stitch_patches_finish, word for word.  Another runtime mode of the gather
+ * kernel.  Refused before the device is touched: NULL pointers, non-positive F or extents. */
+int fdn_finish_volume(const float* acc, double* vol, const double* frame_scale, int F, int Xo, int Yo, int Zo, void* stream);
+
 /* Low-res synthesis (prepare_data/fft_downsampling.py:6-137, downsample_phase_img): nvol velocity volumes vel (nvol,X,Y,Z) that share one
  * magnitude volume mag (X,Y,Z) -> out_vel, out_mag (nvol,2cx,2cy,2cz), all fp32 on the device.  params is a DEVICE table (nvol,4) of
  * {venc, mag_scale, snr_linear = 10^(SNRdb/10), 0}.  The crop half-widths are integers, c = int((N / 2) * crop_ratio) as the reference
@@ -543,6 +574,9 @@ int fdn_input_features_volume_bf16(const float* frames, int F, int X, int Y, int
 /* fdn_input_features_volume_oriented with bf16 phase / pc (src/Network/PatchHandler3D.py:97-108,166-274); frames stay fp32. */
 int fdn_input_features_volume_oriented_bf16(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
                                             int count, int plane, int k, uint16_t* phase, uint16_t* pc, void* stream);
+/* fdn_input_features_volume_strided with bf16 phase / pc; frames stay fp32. */
+int fdn_input_features_volume_strided_bf16(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
+                                           int count, int stride, int plane, int k, uint16_t* phase, uint16_t* pc, void* stream);
 int fdn_conv3d_fwd_bf16(const uint16_t* x, const uint16_t* x2, const float* w, const uint16_t* wpack, const float* bias,
                         const uint16_t* residual, void* y, int N, int D, int H, int W, int Cin, int Cout, int K, int ldy,
                         int y_coff, int act, float alpha, void* stream);

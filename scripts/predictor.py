@@ -1,6 +1,8 @@
 """Counterpart of the reference's src/predictor.py (same hard-coded surface; see 4dflownet_amd/predictor.py:main).
 --self-ensemble [rot90]: average every patch's prediction over the training rotations (predict_file(self_ensemble=); ten forwards per
-patch, on the device tiler)."""
+patch, on the device tiler).
+--blend B: overlap-add stitching, neighbouring patch cores overlap by B low-res voxels and are cross-faded (predict_file(blend=B);
+(E/(E-B))^3 times the forwards with E = patch_size - 4, on the device tiler)."""
 import importlib
 import os
 import sys
@@ -16,5 +18,16 @@ def _self_ensemble(argv):
     return nxt[0] if nxt and not nxt[0].startswith("--") else "rot90"
 
 
+def _blend(argv):
+    """The integer behind --blend, or 0 without the switch; a missing or non-integer value ends the run."""
+    if "--blend" not in argv:
+        return 0
+    nxt = argv[argv.index("--blend") + 1:][:1]
+    try:
+        return int(nxt[0])
+    except (IndexError, ValueError):
+        raise SystemExit("--blend needs an integer: the overlap of neighbouring cores in low-res voxels") from None
+
+
 if __name__ == '__main__':
-    importlib.import_module("4dflownet_amd.predictor").main(self_ensemble=_self_ensemble(sys.argv[1:]))
+    importlib.import_module("4dflownet_amd.predictor").main(self_ensemble=_self_ensemble(sys.argv[1:]), blend=_blend(sys.argv[1:]))

@@ -13,7 +13,12 @@ fewer devices than ranks the lines are marked oversubscribed and are no scaling 
 process.  Per batch of 8 patches (24^3 -> 48^3), by device events: the forward, and for each of the ten orientations the oriented window
 features and the rotate-back-and-accumulate launch, with the two new paths together as a share of the forward.  Then predict_volume on
 synthetic 100^3 frames, plain (four frames, 500 patches) and with the ten orientations (one frame, 125 patches), alternately, N >= 3 timed
-runs each: every run, median, spread and patches/s.  --plain-only: the plain leg alone (the command of a tools/ab_source.sh comparison)."""
+runs each: every run, median, spread and patches/s.  --plain-only: the plain leg alone (the command of a tools/ab_source.sh comparison).
+
+--blend [--runs N]: overlap-add stitching (predict_volume(blend=)) on the example volume, single process, randomly initialised weights.
+For blend 0, 2 and 4: patches per volume and the wall time of one finished volume, alternately, N >= 3 timed runs each; the stitch launches
+of one volume alone by device events (blend_patches + finish_volume against stitch_patches(frame_scale=)); and the seam figure for blend 0
+against 4 -- the mean absolute step across the planes where two cores of the plain tiling meet over that across all other planes, per axis."""
 import importlib
 import os
 import sys
@@ -128,6 +133,74 @@ def self_ensemble_leg(net, dtype, runs, plain_only=False):
         print("rot90 / plain patches/s: %.4f (1/K = %.4f)" % (rate["rot90"] / rate["plain"], 1.0 / len(orientations)))
 
 
+def blend_leg(net, dtype, runs, blends=(0, 2, 4)):
+    """The cost and the effect of predict_volume(blend=) on the example volume at the cfg5 shapes; see the module docstring."""
+    import statistics
+    P, R, B = 24, 2, 8
+    print(_stamp_line())
+    print("# tools/bench_predictor.py --blend --runs %d%s: example_data.h5 row 0, patch 24, res x2, batch 8, 8+4 ResBlocks, %s, randomly "
+          "initialised weights, %s" % (runs, " --bf16" if dtype != "float32" else "", dtype, torch.cuda.get_device_name(0)))
+    ds = data.ImageDataset()
+    ds.load_vectorfield(os.path.join(ROOT, "tests", "golden", "data", "example_data.h5"), 0)
+    frames = np.stack([ds.u, ds.v, ds.w, ds.mag_u, ds.mag_v, ds.mag_w])[None].astype(np.float32)
+    dframes = torch.from_numpy(frames).cuda()
+    scale = predictor._frame_scale_tensor([(ds.venc, ds.velocity_per_px)], 1, dframes.device)
+    E = P - 4
+    plans = {b: tiler.PatchGenerator(P, R, blend=b) for b in blends}
+    times = {b: [] for b in blends}
+    for r in range(runs + 1):                                  # run 0 warms every leg up
+        for b in blends:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            predictor.predict_volume(net, dframes, P, B, frame_scale=scale, blend=b)
+            torch.cuda.synchronize()
+            if r:
+                times[b].append(time.perf_counter() - t0)
+    base = statistics.median(times[blends[0]])
+    for b in blends:
+        counts, _, extents = plans[b].plan(frames.shape[2:])
+        n = counts[0] * counts[1] * counts[2]
+        t = times[b]
+        med = statistics.median(t)
+        print("predict_volume blend=%d: %s = %3d patches per volume ((E/(E-b))^3 = %.2f); runs %s s; median %.3f s per volume (min %.3f .. "
+              "max %.3f) = %.2f x blend=%d" % (b, "x".join(str(c) for c in counts), n, (E / (E - b)) ** 3, " ".join("%.3f" % x for x in t),
+                                               med, min(t), max(t), med / base, blends[0]))
+    # the stitch launches of one volume alone, by device events, on one batch of random predictions
+    pred = torch.from_numpy(np.random.default_rng(0).standard_normal((B, P * R, P * R, P * R, 3)).astype(np.float32)).cuda()
+    for b in blends:
+        counts, _, extents = plans[b].plan(frames.shape[2:])
+        n = counts[0] * counts[1] * counts[2]
+        out64 = torch.empty((1, 3) + extents, device="cuda", dtype=torch.float64)
+        if b == 0:
+            def launches():
+                for g0 in range(0, n, B):
+                    net.ops.stitch_patches(pred[:min(B, n - g0)], out64, 2 * R, counts, g0, frame_scale=scale)
+            what = "stitch_patches(frame_scale=)"
+        else:
+            acc = torch.zeros((1, 3) + extents, device="cuda")
+
+            def launches():
+                for g0 in range(0, n, B):
+                    net.ops.blend_patches(pred[:min(B, n - g0)], acc, 2 * R, plans[b].stride * R, counts, g0)
+                net.ops.finish_volume(acc, scale, out=out64)
+            what = "blend_patches + one finish_volume"
+        us = _event_us(launches, reps=20)
+        print("blend=%d: the %d %s launches of one volume: %.1f us = %.2f %% of its wall time"
+              % (b, (n + B - 1) // B, what, us, 100.0 * us * 1e-6 / statistics.median(times[b])))
+    # the seam figure: mean |step| of the normalised prediction across the planes where two cores of the plain tiling (blend=0) meet, over the
+    # mean |step| across all other planes, per axis -- 1.0 means the core boundaries cannot be told from the rest of the volume
+    C = E * R
+    for b in (blends[0], blends[-1]):
+        vol = predictor.predict_volume(net, dframes, P, B, blend=b)[0].double()
+        figs = []
+        for ax in range(3):
+            step = vol.diff(dim=ax + 1).abs().mean(dim=[d for d in range(4) if d != ax + 1])      # step[x]: between planes x and x + 1
+            seam = torch.zeros_like(step, dtype=torch.bool)
+            seam[C - 1::C] = True
+            figs.append("%s %.4f (%d of %d planes)" % ("xyz"[ax], float(step[seam].mean() / step[~seam].mean()), int(seam.sum()), step.numel()))
+        print("seam figure blend=%d: %s" % (b, ", ".join(figs)))
+
+
 def device_tiler_leg(net, dtype, runs, rank=0, world=1):
     """predict_file end to end (load, patchify, forward, stitch, post-processing) with the file append replaced by a no-op."""
     import statistics
@@ -194,6 +267,12 @@ def main():
             raise SystemExit("--self-ensemble is a single-process measurement")
         runs = int(sys.argv[sys.argv.index("--runs") + 1]) if "--runs" in sys.argv else 3
         self_ensemble_leg(net, dtype, max(runs, 3), plain_only="--plain-only" in sys.argv)
+        return
+    if "--blend" in sys.argv:
+        if world > 1:
+            raise SystemExit("--blend is a single-process measurement")
+        runs = int(sys.argv[sys.argv.index("--runs") + 1]) if "--runs" in sys.argv else 3
+        blend_leg(net, dtype, max(runs, 3))
         return
     if "--device-tiler" in sys.argv:
         runs = int(sys.argv[sys.argv.index("--runs") + 1]) if "--runs" in sys.argv else 3
