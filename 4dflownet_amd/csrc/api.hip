@@ -155,7 +155,9 @@ static int conv3d_fwd(const char* who, const T* x, const T* x2, const float* w, 
     FDN_REQUIRE(x && y, "%s: x/y is NULL", who);
     FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "%s: bad algo %d", who, algo);
     FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "%s: bad dims N=%d D=%d H=%d W=%d", who, N, D, H, W);
-    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= FDN_ACT_LEAKY, "%s: bad act %d", who, act);
+    // (FDN_ACT_TANH: the heads' route alone; elsewhere it is the bad act it was before it had a name)
+    FDN_REQUIRE(act >= FDN_ACT_NONE && act <= ((Cin == 64 && Cout == 1 && K == 3) ? FDN_ACT_TANH : FDN_ACT_LEAKY),
+                "%s: bad act %d%s", who, act, act == FDN_ACT_TANH ? " (FDN_ACT_TANH is the output activation of the (64,1,3) route only)" : "");
     hipStream_t s = (hipStream_t)stream;
     if (Cin == 64 && Cout == 64 && K == 3) {
         FDN_REQUIRE(wpack, "%s: the 64->64 MFMA path needs wpack (fdn_pack_conv64_weights%s)", who, kBf16<T> ? "_bf16" : "");
@@ -325,6 +327,7 @@ extern "C" int fdn_conv64_dgrad_fused_bf16_multi(const uint16_t* const* dz, cons
 template <typename T>
 static int fold_halo_border(const char* who, const float* dxpad0, const float* dxpad1, const float* dxpad2, int nsrc, const T* skip,
                             const T* y_prev, int act, float alpha, T* dz_prev, int N, int D, int H, int W, void* stream) {
+    FDN_REFUSE_TANH(act, who);
     FDN_REQUIRE(dxpad0 && dz_prev, "%s: NULL argument", who);
     FDN_REQUIRE(nsrc >= 1 && nsrc <= 3 && (nsrc < 2 || dxpad1) && (nsrc < 3 || dxpad2), "%s: bad nsrc %d", who, nsrc);
     FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "%s: bad dims", who);
@@ -363,6 +366,7 @@ static int conv_cout1_dgrad_folded(const char* who, bool mask_form, const float*
                                    int D, int H, int W, int lddz, int dz_coff, void* stream) {
     if (mask_form) FDN_REQUIRE(y_mask && (act == FDN_ACT_RELU || act == FDN_ACT_LEAKY), "%s: a sign mask and act = RELU or LEAKY", who);
     else FDN_REQUIRE(!(y_mask && act == FDN_ACT_NONE), "%s: a sign mask needs act = RELU or LEAKY", who);
+    FDN_REFUSE_TANH(act, who);
     return fdn_conv_cout1_dgrad_folded_launch<T>(who, dz, w, y_prev, act, alpha, dz_prev, dbias_prev, workspace, workspace_bytes, N, D, H, W,
                                                  lddz, dz_coff, (hipStream_t)stream, y_mask);
 }

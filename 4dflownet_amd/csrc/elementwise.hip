@@ -560,16 +560,31 @@ __device__ __forceinline__ float div_axis(const float* __restrict__ pred, const 
     return d0;
 }
 
+// fdn_loss_metrics_act, out_act == FDN_ACT_TANH: pred = tanh(z) of the heads' pre-activations z, and dpred is the gradient w.r.t. z -- each
+// component times 1 - y^2 from the output y (TensorFlow's TanhGrad), one fma and one multiply; exactly 0 where y is exactly +-1.
+__device__ __forceinline__ void tanh_grad_store(const float* yb, int64_t i, float* __restrict__ d, float gu, float gv, float gw) {
+    asm volatile("" : "+s"(yb));                // fresh loads (L1 hits): the three outputs do not stay in registers across the stencil gathers
+    const float* y = yb + i;
+    const float yu = y[0];
+    d[0] = gu * fmaf(-yu, yu, 1.f);
+    const float yv = y[1];
+    d[1] = gv * fmaf(-yv, yv, 1.f);
+    const float yw = y[2];
+    d[2] = gw * fmaf(-yw, yw, 1.f);
+}
+
 // div_w == 0: the masked MSE alone, exactly the arithmetic and block -> voxel mapping of the plain loss.  div_w > 0 (fdn_loss_metrics_div):
 // the same pass also gathers each channel's stencil neighbours (e at +-1, +-2 and m at +-1 along its axis; L1 / L2 hits), adds the
 // divergence part of dpred and writes two more per-block partials (sum m d, sum nf d; the weight is applied in loss_finalize_kernel).
 // nparts: partials per block, 3 (plain) or 5.  (The branch's gathers in flight take the kernel from 26 to 68 VGPRs: seven waves per
-// SIMD instead of eight; capping it at 64 spills.)
+// SIMD instead of eight; capping it at 64 spills.)  nf_w (fdn_loss_metrics_act): the non-fluid region's weight, folded into inv_nf, so it
+// reaches the region's part of dpred -- MSE and divergence -- through the existing arithmetic; the sums stay unweighted and
+// loss_finalize_kernel applies it.
 __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict__ pred, const float* __restrict__ uh,
                                                          const float* __restrict__ vh, const float* __restrict__ wh,
                                                          const float* __restrict__ mask, float* __restrict__ scratch,
                                                          float* __restrict__ dpred, int64_t V, int D, int H, int W, float div_w,
-                                                         int nparts, int vm) {
+                                                         int nparts, int vm, float nf_w, int out_act) {
     __shared__ float red[4];
     __shared__ double redd[4];
     if (vm) {                                                        // pred: fp32 or float64; uh: truth; scratch: doubles; D,H,W = X,Y,Z
@@ -578,7 +593,7 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
     }
     const int n = blockIdx.y;
     const float inv_f = 1.f / (scratch[n * 8 + 0] + 1.f);
-    const float inv_nf = 1.f / (scratch[n * 8 + 1] + 1.f);
+    const float inv_nf = nf_w * (1.f / (scratch[n * 8 + 1] + 1.f));     // non_fluid_weight rides on the region's scalar: exact at 1
     if (div_w != 0.f) {
         const float two_w = 2.f * div_w;
         const int64_t HW = (int64_t)H * W;
@@ -611,7 +626,10 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
             const float dd = au * au + av * av + aw * aw;
             sdf += dd * m;
             sdn += dd * nf;
-            if (dpred) { dpred[g * 3] = gu; dpred[g * 3 + 1] = gv; dpred[g * 3 + 2] = gw; }
+            if (dpred) {
+                if (out_act == FDN_ACT_TANH) tanh_grad_store(pred, g * 3, dpred + g * 3, gu, gv, gw);
+                else { dpred[g * 3] = gu; dpred[g * 3 + 1] = gv; dpred[g * 3 + 2] = gw; }
+            }
         }
         const float a = block_sum(sf, red);
         const float b = block_sum(snf, red);
@@ -644,7 +662,8 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
         if (m == 1.0f) srel += corr;
         if (dpred) {
             const float wgt = 2.f * (m * inv_f + nf * inv_nf);
-            dpred[g * 3] = du * wgt; dpred[g * 3 + 1] = dv * wgt; dpred[g * 3 + 2] = dw * wgt;
+            if (out_act == FDN_ACT_TANH) tanh_grad_store(pred, g * 3, dpred + g * 3, du * wgt, dv * wgt, dw * wgt);
+            else { dpred[g * 3] = du * wgt; dpred[g * 3 + 1] = dv * wgt; dpred[g * 3 + 2] = dw * wgt; }
         }
     }
     const float a = block_sum(sf, red);
@@ -661,9 +680,10 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
 
 // one wave per sample: lane t sums the partials of blocks t, t + 64, ..., then a shuffle tree -- a fixed order, so the reported loss /
 // metric stays run-to-run identical (one THREAD per sample walked the 256 partials as a chain of dependent loads: 24 us).
-// nparts 3: out (N,4); nparts 5: out (N,5), column 4 = div_w * (sum m d / (sum m + 1) + sum nf d / (sum nf + 1)).
+// nparts 3: out (N,4); nparts 5: out (N,5), column 4 = div_w * (sum m d / (sum m + 1) + nf_w * sum nf d / (sum nf + 1)); nf_w also weighs
+// the non-fluid part of column 0 (a multiplication by 1.f, exact, everywhere but in fdn_loss_metrics_act).
 __global__ __launch_bounds__(64) void loss_finalize_kernel(const float* __restrict__ scratch, float* __restrict__ out, int N, int nblk,
-                                                           int nparts, float div_w, int vm) {
+                                                           int nparts, float div_w, int vm, float nf_w) {
     if (vm) {                                                        // scratch, out: the doubles of fdn_volume_metrics
         volume_finalize(VolumeMetrics{nullptr, nullptr, nullptr, (double*)scratch, (double*)out, VM_PASS(vm), 0, 0, 0, 0, 0}, nblk);
         return;
@@ -683,11 +703,11 @@ __global__ __launch_bounds__(64) void loss_finalize_kernel(const float* __restri
     if (threadIdx.x) return;
     const float sm = scratch[n * 8 + 0], snf = scratch[n * 8 + 1];
     const int nc = nparts == 5 ? 5 : 4;
-    out[n * nc + 0] = sf / (sm + 1.f) + sn / (snf + 1.f);
+    out[n * nc + 0] = sf / (sm + 1.f) + nf_w * (sn / (snf + 1.f));
     out[n * nc + 1] = sr / (sm + 1.f) * 100.f;
     out[n * nc + 2] = sm;
     out[n * nc + 3] = snf;
-    if (nparts == 5) out[n * 5 + 4] = div_w * (sdf / (sm + 1.f) + sdn / (snf + 1.f));
+    if (nparts == 5) out[n * 5 + 4] = div_w * (sdf / (sm + 1.f) + nf_w * (sdn / (snf + 1.f)));
 }
 
 // ONE block (fixed summation order, no atomics): this pass only runs when the parameters changed outside the optimizer
@@ -927,6 +947,7 @@ extern "C" int fdn_input_features_volume_strided_bf16(const float* frames, int F
 extern "C" int fdn_fold_halo(const float* dxpad0, const float* dxpad1, const float* dxpad2, int nsrc, const float* skip,
                              const float* y_prev, int act, float alpha, float* dz_prev, int N, int D, int H, int W, int C,
                              void* stream) {
+    FDN_REFUSE_TANH(act, "fdn_fold_halo");
     FDN_REQUIRE(dxpad0 && dz_prev, "fdn_fold_halo: NULL argument");
     FDN_REQUIRE(nsrc >= 1 && nsrc <= 3 && (nsrc < 2 || dxpad1) && (nsrc < 3 || dxpad2), "fdn_fold_halo: bad nsrc %d", nsrc);
     FDN_REQUIRE(C % 4 == 0 && N > 0 && D > 0 && H > 0 && W > 0, "fdn_fold_halo: bad dims (C must be a multiple of 4)");
@@ -966,6 +987,7 @@ template <typename T>
 static int upsample_bwd_t(const T* dy, const T* y_prev, int act, float alpha, T* dx, int N, int D, int H, int W, int C, int R,
                           void* stream) {
     constexpr int E = 16 / (int)sizeof(T);
+    FDN_REFUSE_TANH(act, sizeof(T) == 2 ? "fdn_upsample_trilinear_bwd_bf16" : "fdn_upsample_trilinear_bwd");
     FDN_REQUIRE(dy && dx && C % E == 0 && R >= 1 && N > 0 && D > 0 && H > 0 && W > 0, "fdn_upsample_trilinear_bwd: bad argument");
     const int64_t rows = (int64_t)N * D * H;
     const size_t row_lds = (size_t)W * R * C * sizeof(float);
@@ -1023,7 +1045,8 @@ extern "C" int fdn_upsample_trilinear_bwd_bf16(const uint16_t* dy, const uint16_
 
 // the three launches of both loss entry points; nparts 3: out (N,4) (fdn_loss_metrics), 5: out (N,5) (fdn_loss_metrics_div)
 static int loss_launch(const char* who, const float* pred, const float* uh, const float* vh, const float* wh, const float* mask, float* out,
-                       float* dpred, float* scratch, int N, int64_t V, int D, int H, int W, float div_w, int nparts, void* stream) {
+                       float* dpred, float* scratch, int N, int64_t V, int D, int H, int W, float div_w, int nparts, void* stream,
+                       float nf_w = 1.f, int out_act = FDN_ACT_NONE) {
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(scratch, 0, (size_t)N * 8 * sizeof(float), s);
     if (e != hipSuccess) { fdn_set_error("%s: memset: %s", who, hipGetErrorString(e)); return FDN_ERR_HIP; }
@@ -1031,9 +1054,10 @@ static int loss_launch(const char* who, const float* pred, const float* uh, cons
     // (16 blocks per sample: with 256 the 2 x 256 x N atomics on 2 N words took longer than reading the mask -- 29 us at cfg2)
     hipLaunchKernelGGL(mask_sums_kernel, dim3(gx < 16 ? gx : 16, N), dim3(256), 0, s, mask, scratch, V, 0);
     FDN_CHECK_LAUNCH("mask_sums_kernel");
-    hipLaunchKernelGGL(loss_main_kernel, dim3(gx, N), dim3(256), 0, s, pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts, 0);
+    hipLaunchKernelGGL(loss_main_kernel, dim3(gx, N), dim3(256), 0, s, pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts, 0,
+                       nf_w, out_act);
     FDN_CHECK_LAUNCH("loss_main_kernel");
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(N), dim3(64), 0, s, (const float*)scratch, out, N, gx, nparts, div_w, 0);
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(N), dim3(64), 0, s, (const float*)scratch, out, N, gx, nparts, div_w, 0, nf_w);
     FDN_CHECK_LAUNCH("loss_finalize_kernel");
     return FDN_OK;
 }
@@ -1057,6 +1081,25 @@ extern "C" int fdn_loss_metrics_div(const float* pred, const float* uh, const fl
                        stream);
 }
 
+// the loss with the reference's non_fluid_weight and the heads' activation: the same three launches
+extern "C" int fdn_loss_metrics_act(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask,
+                                    float div_weight, float non_fluid_weight, int out_act, float* out, float* dpred, float* scratch,
+                                    int N, int D, int H, int W, void* stream) {
+    FDN_REQUIRE(pred && uh && vh && wh && mask && out && scratch, "fdn_loss_metrics_act: NULL operand");
+    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_loss_metrics_act: extents N=%d D=%d H=%d W=%d must be positive", N, D, H, W);
+    FDN_REQUIRE((int64_t)D * H * W <= (int64_t)INT32_MAX, "fdn_loss_metrics_act: %d x %d x %d voxels per sample exceed 2^31 - 1", D, H, W);
+    FDN_REQUIRE(__builtin_isfinite(div_weight) && div_weight >= 0.f, "fdn_loss_metrics_act: div_weight %g must be finite and >= 0",
+                (double)div_weight);
+    FDN_REQUIRE(__builtin_isfinite(non_fluid_weight) && non_fluid_weight >= 0.f,
+                "fdn_loss_metrics_act: non_fluid_weight %g must be finite and >= 0", (double)non_fluid_weight);
+    if (out_act != FDN_ACT_NONE && out_act != FDN_ACT_TANH) {
+        fdn_set_error("fdn_loss_metrics_act: out_act %d is not an activation of the heads (FDN_ACT_NONE or FDN_ACT_TANH)", out_act);
+        return FDN_ERR_UNSUPPORTED;
+    }
+    return loss_launch("fdn_loss_metrics_act", pred, uh, vh, wh, mask, out, dpred, scratch, N, (int64_t)D * H * W, D, H, W, div_weight, 5,
+                       stream, non_fluid_weight, out_act);
+}
+
 extern "C" int fdn_volume_metrics(const void* pred, int pred_is_f64, const float* truth, const float* mask, int mask_frames,
                                   double* out, double* scratch, int F, int X, int Y, int Z, void* stream) {
     FDN_REQUIRE(pred, "fdn_volume_metrics: pred is NULL");
@@ -1077,10 +1120,10 @@ extern "C" int fdn_volume_metrics(const void* pred, int pred_is_f64, const float
     for (int pass = 1; pass <= 5; ++pass) {                              // columns 3-8, 9-10, then the five moments of u, v, w
         hipLaunchKernelGGL(loss_main_kernel, dim3(gx, F), dim3(256), 0, s, (const float*)pred, truth, (const float*)nullptr,
                            (const float*)nullptr, mask, (float*)scratch, (float*)nullptr, (int64_t)X * Y * Z, X, Y, Z, 0.f, 0,
-                           VM_MODE(pass, f64, per_frame));
+                           VM_MODE(pass, f64, per_frame), 1.f, FDN_ACT_NONE);
         FDN_CHECK_LAUNCH("loss_main_kernel (volume metrics)");
     }
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(F), dim3(64), 0, s, (const float*)scratch, (float*)out, F, gx, 0, 0.f, VM_MODE(1, 0, 0));
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(F), dim3(64), 0, s, (const float*)scratch, (float*)out, F, gx, 0, 0.f, VM_MODE(1, 0, 0), 1.f);
     FDN_CHECK_LAUNCH("loss_finalize_kernel (volume metrics)");
     return FDN_OK;
 }

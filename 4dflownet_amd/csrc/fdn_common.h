@@ -170,6 +170,18 @@ int fdn_plan_cus();
         }                                                                              \
     } while (0)
 
+// FDN_ACT_TANH is an activation of the heads' forward (and of fdn_loss_metrics_act) alone.  The entry points whose act had no range
+// check (an unknown act meant "none": the folds, the upsample adjoint, the heads' folded dgrad) refuse it with this; the ones that had
+// one (fdn_conv3d_fwd off the heads' route, the 64->64 entry points) keep answering FDN_ERR_BAD_ARG, as for any act they do not know.
+// Either way by name and before anything touches the device.
+#define FDN_REFUSE_TANH(act, who)                                                                                        \
+    do {                                                                                                                 \
+        if ((act) == FDN_ACT_TANH) {                                                                                     \
+            fdn_set_error("%s: FDN_ACT_TANH is the output activation of the (64,1,3) forward only", who);               \
+            return FDN_ERR_UNSUPPORTED;                                                                                  \
+        }                                                                                                                \
+    } while (0)
+
 // floor(r/d) for 0 <= r < 1024 and 1 <= d <= 1024, with magic = ceil(2^20/d).
 __host__ __device__ inline unsigned fdn_magic20(unsigned d) { return ((1u << 20) + d - 1) / d; }
 __device__ __forceinline__ int fdn_div20(int r, unsigned magic) { return (int)(((unsigned)r * magic) >> 20); }

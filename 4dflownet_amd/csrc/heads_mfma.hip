@@ -28,6 +28,33 @@ namespace {
 
 __device__ __forceinline__ int clampi(int v, int hi) { return min(max(v, 0), hi); }
 
+// The heads' own epilogue (fdn_act stays as every other conv kernel inlines it).  FDN_ACT_TANH = Keras' Conv3D(activation='tanh'):
+// everything is computed from a = |z| and the sign copied back, so the function is odd bit for bit.
+//   a <  0.625 : a + a s P(s), s = a^2, P the degree-4 minimax polynomial of (tanh(a) / a - 1) / s on [0, 0.625] (Cephes tanhf)
+//   a >= 0.625 : 1 - 2 / (exp(2 a) + 1), exp(2 a) = v_exp_f32(8 log2(e) min(a / 4, 4)): a capped at 16 (exp(32) = 7.9e13: no overflow; the
+//                comparison lets a NaN pass the cap, and it stays a NaN).  2 / (exp(2 a) + 1) < 2^-25 from a = 9.011 on, where the
+//                subtraction rounds to 1: exactly 1 for |z| >= 9.02 (2.93e-8 against 2^-25 = 2.98e-8 there, the exponent good to 2e-6),
+//                inf included, and never above 1.  IEEE division; the rounding of the exponent's argument and of v_exp_f32 (1 ulp)
+//                reach the result times 2 e / (e + 1)^2 <= 0.35: about 2.3 ulp at a = 0.625, less above.
+// Both sides are computed and one selected, and no constant needs a vector register (the cap of 4 is an inline constant, the top Horner
+// step is a multiply and an add): the fp32 kernel sits 10 VGPRs below its 256 without the activation.
+__device__ __forceinline__ float head_tanh(float z) {
+    const float a = fabsf(z);
+    const float s = a * a;
+    float p = __fadd_rn(__fmul_rn(-5.70498872745e-3f, s), 2.06390887954e-2f);
+    p = fmaf(p, s, -5.37397155531e-2f);
+    p = fmaf(p, s, 1.33314422036e-1f);
+    p = fmaf(p, s, -3.33332819422e-1f);
+    const float q = 0.25f * a;
+    const float e = __builtin_amdgcn_exp2f(11.54156033f * (q > 4.f ? 4.f : q));
+    const float t = a < 0.625f ? fmaf(p * s, a, a) : 1.f - 2.f / (e + 1.f);
+    return copysignf(t, z);
+}
+__device__ __forceinline__ float head_act(float z, int act, float alpha) {
+    if (act == FDN_ACT_TANH) return head_tanh(z);
+    return fdn_act(z, act, alpha);
+}
+
 constexpr int H_TD = 4, H_TH = 8, H_TW = 8;                 // forward tile: 256 outputs, one per thread
 constexpr int H_XD = H_TD + 2, H_XH = H_TH + 2, H_XW = H_TW + 2;
 constexpr int H_HV = H_XD * H_XH * H_XW;                    // 600 halo voxels
@@ -168,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void head_fwd_kernel(const T* __restrict__ 
                 for (int c = 0; c < 3; ++c)
                     s += zbuf[((a * 3 + bb) * 3 + c) * H_HVP + ((od + a) * H_XH + oh + bb) * H_XW + ow + c];
         if (valid && pd < D && ph < H && pw < W)
-            y[((size_t)o.n * D * H * W + ((size_t)pd * H + ph) * W + pw) * ldy + y_coff] = fdn_act(s, act, alpha);
+            y[((size_t)o.n * D * H * W + ((size_t)pd * H + ph) * W + pw) * ldy + y_coff] = head_act(s, act, alpha);
         __syncthreads();               // zbuf is rewritten by the next tile
     };
     u32x4 buf[3][NCH];

@@ -647,6 +647,7 @@ int fdn_conv_cout1_fwd_launch(const T* x, const float* w, const float* bias, flo
                               int y_coff, int act, float alpha, hipStream_t s) {
 #ifdef FDN_TEST_HOOKS
     if (!fdn_heads_use_mfma) {
+        FDN_REFUSE_TANH(act, "fdn_conv3d_fwd(64->1, VALU kernel)");       // (head_fwd_kernel's epilogue alone has it)
         const int64_t nvox = (int64_t)N * D * H * W;
         hipLaunchKernelGGL(conv_cout1_fwd_kernel<T>, dim3(nblocks_for(nvox, 16, 8192)), dim3(256), 0, s, x, w, bias, y, N, D, H,
                            W, ldy, y_coff, act, alpha);

@@ -22,7 +22,17 @@ import torch
 from . import ops, ops_bf16
 from ._lib import FdnError
 
-ACT_NONE, ACT_RELU, ACT_LEAKY = ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LEAKY
+ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_TANH = ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LEAKY, ops.ACT_TANH
+
+
+def output_activation_code(name):
+    """('linear' | 'tanh', ACT_*) of the heads' output activation: None and 'linear' are the reference's v2 network (README.md:11), 'tanh'
+    the bounded heads its first published weights were trained with (Keras' Conv3D(activation='tanh'))."""
+    if name is None or name == "linear":
+        return "linear", ACT_NONE
+    if name == "tanh":
+        return "tanh", ACT_TANH
+    raise ValueError("output_activation must be None, 'linear' or 'tanh', got %r" % (name,))
 
 
 class Input:
@@ -197,7 +207,8 @@ class _T:
 
 
 class FlowNetModel:
-    def __init__(self, res_increase, low_resblock=8, hi_resblock=4, device=None, seed=0, dtype="float32", conv_algo=None):
+    def __init__(self, res_increase, low_resblock=8, hi_resblock=4, device=None, seed=0, dtype="float32", conv_algo=None,
+                 output_activation=None):
         """dtype: storage type of activations and activation gradients -- "float32" (the reference's arithmetic) or
         "bfloat16" (BASELINE.json configs[3]; parameters, their gradients, the prediction and the optimizer stay fp32).
         conv_algo (fp32 mode): algorithm of the 64->64 3x3x3 layers -- "auto" (FDN_ALGO_AUTO: 2-D Winograd forward / dgrad, F(4,3) along
@@ -205,7 +216,11 @@ class FlowNetModel:
         it, else direct -- forward() warns once per grid that falls off the 2-D kernels), "winograd_h2" (FDN_ALGO_WINO_H2: never more
         than F(2,3) along H, round 4's kernels), "winograd_w" (FDN_ALGO_WINO_W: the 1-D kernels only), "direct" (FDN_ALGO_DIRECT
         everywhere), or a dict {layer name: "direct"} that pins single layers (forward, dgrad and wgrad of that layer) to the direct
-        kernels; None reads FDN_CONV_ALGO (default "auto")."""
+        kernels; None reads FDN_CONV_ALGO (default "auto").
+        output_activation: None / 'linear' (the reference's network) or 'tanh' (bounded heads, FDN_ACT_TANH in the heads' epilogue); kept
+        as self.output_activation, its ACT_* code as self.out_act -- what ops.loss_metrics(out_act=) needs to hand backward() the
+        gradient w.r.t. the heads' pre-activations."""
+        self.output_activation, self.out_act = output_activation_code(output_activation)
         if not torch.cuda.is_available():
             raise FdnError("FlowNetModel needs a ROCm GPU: the hot path is HIP-only (no CPU fallback)")
         dtype = {"float32": "float32", "fp32": "float32", "f32": "float32", torch.float32: "float32",
@@ -620,7 +635,7 @@ class FlowNetModel:
         gmasks = []                                         # bf16 training: sign masks of the three head activations (else None)
         for hidx in range(3):
             g, m_g = self._conv_m(rb.t, Ls[li], ACT_RELU, want_mask=want("heads", hidx))
-            self._conv(g, Ls[li + 1], ACT_NONE, out=pred, ldy=3, y_coff=hidx)
+            self._conv(g, Ls[li + 1], self.out_act, out=pred, ldy=3, y_coff=hidx)
             heads.append(g if not training else kept(g, "heads", hidx))
             gmasks.append(m_g)
             del g, m_g
@@ -738,6 +753,9 @@ class FlowNetModel:
     def backward(self, dpred, grad_ready=None):
         """Fill self.flat_g with d(sum_b loss_b)/d(params) given dpred (B,PR,PR,PR,3); L2 is NOT included here
         (it is folded into the Adam kernel).  Consumes the cache of the last forward(training=True).
+        dpred is the gradient w.r.t. the heads' PRE-activations: what ops.loss_metrics(..., out_act=self.out_act) returns.  For the
+        linear model that is the gradient w.r.t. the prediction; under output_activation='tanh' the loss pass has already multiplied
+        it by 1 - pred^2, and nothing below knows about the activation.
         grad_ready(lo, hi), if given, is called once per entry of self.grad_buckets, in that order, as soon as every launch that
         writes flat_g_ext[lo:hi] has been enqueued.
         STREAM of the callback: with overlap_wgrad on (and a weight-gradient stream in existence) it runs with that SIDE stream
@@ -907,10 +925,13 @@ class SR4DFlowNet:
         self.res_increase = res_increase
 
     def build_network(self, u, v, w, u_mag, v_mag, w_mag, low_resblock=8, hi_resblock=4, channel_nr=64, device=None,
-                      seed=0, dtype="float32", conv_algo=None):
+                      seed=0, dtype="float32", conv_algo=None, output_activation=None):
+        """output_activation: None / 'linear' (SR4DFlowNet.py:40,43,46 as shipped) or 'tanh' (the first published weights)."""
         channel_nr = 64   # noqa: F841  (the reference overwrites the argument)
+        output_activation_code(output_activation)         # (refused before anything needs a GPU)
         for t in (u, v, w, u_mag, v_mag, w_mag):
             shp = getattr(t, "shape", None)
             if shp is not None and len(shp) == 5 and shp[-1] != 1:
                 raise ValueError("inputs must have a single channel, got shape %s" % (tuple(shp),))
-        return FlowNetModel(self.res_increase, low_resblock, hi_resblock, device=device, seed=seed, dtype=dtype, conv_algo=conv_algo)
+        return FlowNetModel(self.res_increase, low_resblock, hi_resblock, device=device, seed=seed, dtype=dtype, conv_algo=conv_algo,
+                            output_activation=output_activation)

@@ -14,6 +14,7 @@ from . import _lib
 from ._lib import FdnError, check
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
+ACT_TANH = 3            # FDN_ACT_TANH: the bounded output of the 64->1 heads (conv3d_fwd on that route, loss_metrics(out_act=))
 # FDN_ALGO_*: per-call algorithm of the 64->64 3x3x3 entry points (AUTO = Winograd along W when W % 4 == 0, DIRECT = never)
 # ALGO_WINO_BF16X3: like AUTO, the F(4,3)xF(4,3) products on the bf16 matrix pipe (operands split exactly into 3 bf16 pieces, 6 terms, fp32 accumulation)
 ALGO_AUTO, ALGO_DIRECT, ALGO_WINO_W, ALGO_WINO_H2, ALGO_WINO_BF16X3 = 0, 1, 2, 3, 4
@@ -609,10 +610,21 @@ def upsample_trilinear_bwd(dy, R, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA, 
     return _upsample_trilinear_bwd("fdn_upsample_trilinear_bwd", ACT_DTYPE, dy, R, y_prev, act, alpha, out)
 
 
-def loss_metrics(pred, uh, vh, wh, mask, want_grad=True, out=None, dpred=None, scratch=None, div_weight=0.0):
+def loss_metrics(pred, uh, vh, wh, mask, want_grad=True, out=None, dpred=None, scratch=None, div_weight=0.0, non_fluid_weight=1.0,
+                 out_act=ACT_NONE):
     """Returns out (N,4) = [mse-loss, rel-err %, sum mask, sum nonfluid] and dpred (N,...,3) or None.
     div_weight != 0 (pred (N,D,H,W,3)): fdn_loss_metrics_div, out (N,5) with the weighted divergence loss div_b in column 4 and its
-    gradient in dpred (the sample's loss is out[:, 0] + out[:, 4]).  div_weight == 0 is exactly the plain call."""
+    gradient in dpred (the sample's loss is out[:, 0] + out[:, 4]).  div_weight == 0 is exactly the plain call.
+    non_fluid_weight != 1 or out_act == ACT_TANH (pred (N,D,H,W,3)): fdn_loss_metrics_act, out (N,5): the non-fluid part of the MSE and of
+    the divergence term weighted, and dpred the gradient w.r.t. the heads' PRE-activations (times 1 - pred^2 under ACT_TANH) -- what
+    FlowNetModel.backward takes.  At the defaults the calls are exactly the ones above."""
+    non_fluid_weight = float(non_fluid_weight)
+    if not (math.isfinite(non_fluid_weight) and non_fluid_weight >= 0):
+        raise FdnError("loss_metrics: non_fluid_weight must be a finite number >= 0, got %r" % (non_fluid_weight,))
+    if out_act not in (ACT_NONE, ACT_TANH):
+        raise FdnError("loss_metrics: out_act must be ACT_NONE or ACT_TANH, got %r" % (out_act,))
+    if non_fluid_weight != 1.0 or out_act != ACT_NONE:
+        return _loss_metrics_div(pred, uh, vh, wh, mask, float(div_weight), want_grad, out, dpred, scratch, non_fluid_weight, out_act)
     N = pred.shape[0]
     if div_weight != 0:
         return _loss_metrics_div(pred, uh, vh, wh, mask, float(div_weight), want_grad, out, dpred, scratch)
@@ -629,7 +641,8 @@ def loss_metrics(pred, uh, vh, wh, mask, want_grad=True, out=None, dpred=None, s
     return out, (dpred if want_grad else None)
 
 
-def _loss_metrics_div(pred, uh, vh, wh, mask, div_weight, want_grad, out, dpred, scratch):
+def _loss_metrics_div(pred, uh, vh, wh, mask, div_weight, want_grad, out, dpred, scratch, non_fluid_weight=None, out_act=ACT_NONE):
+    """fdn_loss_metrics_div, or (non_fluid_weight given) fdn_loss_metrics_act: same operands, same buffers."""
     if pred.dim() != 5 or pred.shape[-1] != 3:
         raise FdnError("loss_metrics: the divergence term needs pred of shape (N,D,H,W,3), got %s" % (tuple(pred.shape),))
     N, D, H, W = pred.shape[:4]
@@ -645,6 +658,11 @@ def _loss_metrics_div(pred, uh, vh, wh, mask, div_weight, want_grad, out, dpred,
         dpred = torch.empty_like(pred)
     if out.numel() < N * 5 or scratch.numel() < N * (8 + 5 * 256) or (want_grad and dpred.numel() != pred.numel()):
         raise FdnError("loss_metrics: out needs (N,5), scratch N*(8 + 5*256) floats and dpred pred's shape")
+    if non_fluid_weight is not None:
+        check(_lib.load().fdn_loss_metrics_act(_p(pred), _p(uh), _p(vh), _p(wh), _p(mask), div_weight, non_fluid_weight, int(out_act), _p(out),
+                                               _p(dpred, allow_none=True) if want_grad else None, _p(scratch), N, D, H, W, _stream()),
+              "fdn_loss_metrics_act")
+        return out, (dpred if want_grad else None)
     check(_lib.load().fdn_loss_metrics_div(_p(pred), _p(uh), _p(vh), _p(wh), _p(mask), div_weight, _p(out),
                                            _p(dpred, allow_none=True) if want_grad else None, _p(scratch), N, D, H, W, _stream()),
           "fdn_loss_metrics_div")

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import FdnError, check
-from .ops import (ACT_NONE, ACT_RELU, ACT_LEAKY, LEAKY_ALPHA, ALGO_AUTO, ROLE_FWD, _stream, loss_metrics, l2_sumsq, adam_step,  # noqa: F401
+from .ops import (ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_TANH, LEAKY_ALPHA, ALGO_AUTO, ROLE_FWD, _stream, loss_metrics, l2_sumsq, adam_step,  # noqa: F401
                   stitch_patches, pack_patch_cores, blend_patches, finish_volume, unrotate_accumulate, self_ensemble_orientations, volume_metrics, _ptr, _p as _pf, _mask_ptr,
                   _input_features, _input_features_volume, _pack_conv64_weights, _conv_cout1_dgrad_folded, _dgrad_fused_multi, _fold_halo_border,
                   _conv1x1_dgrad, _conv3d_wgrad, _wgrad_batch, _upsample_trilinear_fwd, _upsample_trilinear_bwd)

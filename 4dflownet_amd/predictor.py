@@ -18,11 +18,14 @@ from .ops import self_ensemble_orientations
 from .tiler import PatchGenerator, check_blend
 
 
-def prepare_network(patch_size, res_increase, low_resblock, hi_resblock, device=None, dtype="float32"):
-    """predictor.py:11-29.  dtype="bfloat16" runs the forward with bf16 activation storage (fp32 weights / prediction)."""
+def prepare_network(patch_size, res_increase, low_resblock, hi_resblock, device=None, dtype="float32", output_activation=None):
+    """predictor.py:11-29.  dtype="bfloat16" runs the forward with bf16 activation storage (fp32 weights / prediction).
+    output_activation: None / 'linear', or 'tanh' for weights trained with bounded heads (the reference's first published set); a
+    weights file does not say which, so the caller does."""
     shape = (patch_size, patch_size, patch_size, 1)
     ins = [Input(shape, n) for n in ('u', 'v', 'w', 'u_mag', 'v_mag', 'w_mag')]
-    return SR4DFlowNet(res_increase).build_network(*ins, low_resblock, hi_resblock, device=device, dtype=dtype)
+    return SR4DFlowNet(res_increase).build_network(*ins, low_resblock, hi_resblock, device=device, dtype=dtype,
+                                                    output_activation=output_activation)
 
 
 def save_to_h5(output_filepath, col_name, dataset, compression=None):
@@ -656,11 +659,12 @@ def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase
 def main(data_dir='../data', filename='example_data.h5', output_dir="../result", output_filename='example_result.h5',
          model_path="../models/4DFlowNet/4DFlowNet.h5", patch_size=24, res_increase=2, batch_size=8,
          round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32", device_tiler=False, frames_per_group=None,
-         self_ensemble=None, blend=0):
-    """Same hard-coded surface as predictor.py:31-47 (+ dtype, + the device tiler switch, self_ensemble and blend of predict_file)."""
+         self_ensemble=None, blend=0, output_activation=None):
+    """Same hard-coded surface as predictor.py:31-47 (+ dtype, + the device tiler switch, self_ensemble and blend of predict_file,
+    + output_activation of prepare_network)."""
     check_blend(blend, patch_size, "main")
     parallel.init_from_env()
-    network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype)
+    network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype, output_activation=output_activation)
     network.load_weights(model_path)
     if not os.path.isdir(output_dir) and parallel.rank() == 0:
         os.makedirs(output_dir)
@@ -674,12 +678,12 @@ def main(data_dir='../data', filename='example_data.h5', output_dir="../result",
 def evaluate_main(data_dir='../data', filename='example_data.h5', hr_filename='example_data_HR.h5', output_dir="../result",
                   csv_filename='example_metrics.csv', output_filename=None, model_path="../models/4DFlowNet/4DFlowNet.h5", patch_size=24,
                   res_increase=2, batch_size=8, round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32",
-                  frames_per_group=None, self_ensemble=None, blend=0):
+                  frames_per_group=None, self_ensemble=None, blend=0, output_activation=None):
     """The surface of main() for scoring a checkpoint: + hr_filename, the ground truth beside `filename`, and csv_filename; the
     prediction itself is written only with output_filename."""
     check_blend(blend, patch_size, "evaluate_main")
     parallel.init_from_env()
-    network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype)
+    network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype, output_activation=output_activation)
     network.load_weights(model_path)
     if not os.path.isdir(output_dir) and parallel.rank() == 0:
         os.makedirs(output_dir)

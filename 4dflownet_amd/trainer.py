@@ -127,7 +127,8 @@ class TrainerController:
     def __init__(self, patch_size, res_increase, initial_learning_rate=1e-4, quicksave_enable=True,
                  network_name='4DFlowNet', low_resblock=8, hi_resblock=4, device=None, seed=0, dtype='float32',
                  bucketed_allreduce=None, conv_algo=None, div_weight=0, accum_steps=1, trainable=None, global_clipnorm=None,
-                 clipvalue=None, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, ema_validation=False):
+                 clipvalue=None, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, ema_validation=False,
+                 output_activation=None, non_fluid_weight=1):
         """Reference arguments: TrainerController.py:18.  Extra (keyword-only in spirit): device, seed (Glorot draw), dtype
         (activation storage, 'float32' | 'bfloat16'), bucketed_allreduce (data parallel only: True = one asynchronous SUM
         all-reduce per gradient bucket started inside backward -- the default --, False = ONE all-reduce of the whole buffer
@@ -158,7 +159,11 @@ class TrainerController:
         ema_overwrite_frequency = k: after every optimiser step with iterations % k == 0 the weights are overwritten with the average.
         finalize_ema() does so on demand, `with ema_weights():` evaluates under the average and restores the weights.  The
         attributes of the same names are read on every optimiser step), ema_validation (True: train_network runs the validation
-        loop, the best-model decision and quicksave under the averaged weights)."""
+        loop, the best-model decision and quicksave under the averaged weights), output_activation (None / 'linear' = the reference's v2
+        network, 'tanh' = the bounded heads its first published weights were trained with; see FlowNetModel), non_fluid_weight
+        ("Weighting for non fluid region", TrainerController.py:24: a finite number >= 0 on the non-fluid part of the MSE and of the
+        divergence term; 1 = the reference's shipped loss, 0 = a fluid-only loss.  Like div_weight the attribute is read on every
+        step)."""
         self.use_ema = use_ema
         self.ema_momentum = ema_momentum
         self.ema_overwrite_frequency = ema_overwrite_frequency
@@ -182,7 +187,8 @@ class TrainerController:
         self._accum_k = 1              # accum_steps as read when the running group started
         self._accum_count = 0          # micro-steps of the running group so far (0: no group is open)
         self._accum_has = False        # the accumulator holds a contribution of the running group (an empty shard contributes nothing)
-        self.non_fluid_weight = 1
+        self.non_fluid_weight = non_fluid_weight   # TrainerController.py:24
+        self._checked_non_fluid_weight()
         self.res_increase = res_increase
         self.patch_size = patch_size
         self.QUICKSAVE_ENABLED = quicksave_enable
@@ -193,7 +199,7 @@ class TrainerController:
         u_mag, v_mag, w_mag = Input(input_shape, 'u_mag'), Input(input_shape, 'v_mag'), Input(input_shape, 'w_mag')
         net = SR4DFlowNet(res_increase)
         self.model = net.build_network(u, v, w, u_mag, v_mag, w_mag, low_resblock, hi_resblock, device=device, seed=seed,
-                                       dtype=dtype, conv_algo=conv_algo)
+                                       dtype=dtype, conv_algo=conv_algo, output_activation=output_activation)
         self.device = self.model.device
         if trainable is not None:
             self.model.set_trainable(trainable)
@@ -242,6 +248,16 @@ class TrainerController:
             raise ValueError("div_weight must be a finite number >= 0, got %r" % (w,))
         return wf
 
+    def _checked_non_fluid_weight(self):
+        w = self.non_fluid_weight
+        try:
+            wf = float(w)
+        except (TypeError, ValueError):
+            raise ValueError("non_fluid_weight must be a finite number >= 0, got %r" % (w,)) from None
+        if not np.isfinite(wf) or wf < 0:
+            raise ValueError("non_fluid_weight must be a finite number >= 0, got %r" % (w,))
+        return wf
+
     def _checked_accum_steps(self):
         k = self.accum_steps
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
@@ -256,10 +272,18 @@ class TrainerController:
         """(use_ema, ema_momentum as float32, ema_overwrite_frequency, ema_validation), validated: see _ema_arguments."""
         return _ema_arguments(self.use_ema, self.ema_momentum, self.ema_overwrite_frequency, self.ema_validation)
 
+    def _loss_call(self, hires, predictions, mask, want_grad):
+        """The loss pass of every step and of quicksave: div_weight and non_fluid_weight as the attributes stand now, the activation the
+        model's heads ended in -- so dpred is the gradient w.r.t. their pre-activations, what model.backward takes.  At the defaults
+        (1, linear) ops.loss_metrics makes the calls it always made.  Returns (out, dpred, div_weight)."""
+        div_weight = self._checked_div_weight()
+        out, dpred = ops.loss_metrics(predictions, hires[0], hires[1], hires[2], mask, want_grad=want_grad, div_weight=div_weight,
+                                      non_fluid_weight=self._checked_non_fluid_weight(), out_act=self.model.out_act)
+        return out, dpred, div_weight
+
     def calculate_and_update_metrics(self, hires, predictions, mask, metric_set, want_grad):
         """TrainerController.py:84-127 (loss_function, the divergence term live when div_weight != 0), :243-256 (metrics)."""
-        div_weight = self._checked_div_weight()
-        out, dpred = ops.loss_metrics(predictions, hires[0], hires[1], hires[2], mask, want_grad=want_grad, div_weight=div_weight)
+        out, dpred, div_weight = self._loss_call(hires, predictions, mask, want_grad)
         mse, rel_error = out[:, 0], out[:, 1]
         div = out[:, 4] if div_weight != 0 else None
         loss = mse if div is None else mse + div
@@ -531,6 +555,10 @@ class TrainerController:
         self._log('Initial learning rate: %s\n' % self.learning_rate)
         self._log('Accuracy metric: %s\n' % self.accuracy_metric)
         self._log('Divergence weight: %s\n' % self.div_weight)
+        if self._checked_non_fluid_weight() != 1:
+            self._log('Non fluid weight: %s\n' % self.non_fluid_weight)
+        if self.model.output_activation != 'linear':
+            self._log('Output activation: %s\n' % self.model.output_activation)
         clipnorm, clipvalue = self._checked_clip()
         if clipnorm is not None or clipvalue is not None:
             self._log('Gradient clipping: %s\n' % ('global_clipnorm=%s' % self.global_clipnorm if clipnorm is not None else
@@ -809,11 +837,10 @@ class TrainerController:
     def quicksave(self, testset, epoch_nr):
         """TrainerController.py:415-454: predict the first benchmark batch, append to quicksave_<name>.h5."""
         from . import h5io
-        div_weight = self._checked_div_weight()
         for data_pairs in testset:
             inputs, hires, venc, mask = self._unpack(data_pairs)
             preds_t = self.model.forward(inputs)
-            out, _ = ops.loss_metrics(preds_t, hires[0], hires[1], hires[2], mask, want_grad=False, div_weight=div_weight)
+            out, _, div_weight = self._loss_call(hires, preds_t, mask, False)
             break
         out = out.cpu().numpy()
         preds = preds_t.cpu().numpy()

@@ -48,6 +48,14 @@ extern "C" {
 #define FDN_ACT_NONE 0
 #define FDN_ACT_RELU 1  /* Conv3D(activation='relu')            src/Network/SR4DFlowNet.py:17-25,39,42,45 */
 #define FDN_ACT_LEAKY 2 /* tf.keras.layers.LeakyReLU(alpha=0.2) src/Network/SR4DFlowNet.py:113,118 */
+/* Conv3D(activation='tanh'): the bounded output of the three 64->1 heads (the first set of published weights was trained with it;
+ * README.md:11,23 of the reference).  Accepted by fdn_conv3d_fwd / fdn_conv3d_fwd_bf16 on the (64,1,3) route and, as out_act, by
+ * fdn_loss_metrics_act.  Everywhere else it is refused before the device is touched, under the entry point's name: FDN_ERR_BAD_ARG
+ * where an act outside NONE..LEAKY always was (the other routes of the two forwards, the 64->64 entry points, fdn_conv_cout1_dgrad_folded_mask),
+ * FDN_ERR_UNSUPPORTED where an unknown act used to mean "none" (fdn_fold_halo[_border][_bf16], fdn_upsample_trilinear_bwd[_bf16],
+ * fdn_conv_cout1_dgrad_folded[_bf16][_mask]).  y = tanh(z) of the value FDN_ACT_NONE stores: odd bit for bit, |y| <= 1, exactly +-1 for |z| >= 9.02 (+-inf included), NaN
+ * only from NaN, within 3 ulp of tanh. */
+#define FDN_ACT_TANH 3
 
 /* Algorithm selector of the 64->64 3x3x3 entry points (fdn_conv3d_fwd / _dgrad / _dgrad_fused[_part] / _wgrad; ignored by
  * every other (Cin,Cout,K)).  Per call, no global state.
@@ -262,6 +270,20 @@ int fdn_loss_metrics(const float* pred, const float* uh, const float* vh, const 
 #define FDN_LOSS_DIV_SCRATCH_FLOATS(N) ((N) * (8 + 5 * FDN_LOSS_BLOCKS))
 int fdn_loss_metrics_div(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask,
                          float div_weight, float* out, float* dpred, float* scratch, int N, int D, int H, int W, void* stream);
+
+/* fdn_loss_metrics_div with the reference's non_fluid_weight ("Weighting for non fluid region", src/Network/TrainerController.py:24)
+ * and the activation of the heads that produced pred.  Same operands, out (N,5) layout, scratch size and determinism.  Per sample
+ *   out[0] = sum(mask e^2) / (sum(mask) + 1) + non_fluid_weight * sum(nf e^2) / (sum(nf) + 1)
+ *   out[4] = div_weight * (sum(mask d) / (sum(mask) + 1) + non_fluid_weight * sum(nf d) / (sum(nf) + 1));
+ * the relative-error column and the two counts do not change.  dpred = d(sum_b (out[0] + out[4])) / d(head PRE-activations): with
+ * out_act == FDN_ACT_TANH every component of the gradient w.r.t. pred is multiplied by fmaf(-y, y, 1.f), y that component of pred
+ * (TensorFlow's TanhGrad: from the output; exactly 0 where y is exactly +-1); with FDN_ACT_NONE the two gradients are the same.
+ * non_fluid_weight == 1 and out_act == FDN_ACT_NONE: out and dpred equal fdn_loss_metrics_div's bit for bit (at div_weight == 0 also
+ * fdn_loss_metrics' columns 0-3 and dpred).  Refused before the device is touched: NULL operands, non-positive extents, D*H*W > 2^31 - 1,
+ * a weight that is negative or not finite, an out_act other than FDN_ACT_NONE / FDN_ACT_TANH (FDN_ERR_UNSUPPORTED). */
+int fdn_loss_metrics_act(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask, float div_weight,
+                         float non_fluid_weight, int out_act, float* out, float* dpred, float* scratch, int N, int D, int H, int W,
+                         void* stream);
 
 /* Whole-volume evaluation of a stitched prediction against the high-resolution truth: 26 sums per frame, from which the host derives the
  * reference's loss and metric (src/Network/TrainerController.py:96-107, src/Network/loss_utils.py:64-101), the divergence term, RMSE

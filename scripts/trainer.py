@@ -57,6 +57,11 @@ if __name__ == "__main__":
     # (TrainerController(trainable=...), the same as `layer.trainable = False` in Keras).  Together with `restore` the run starts from the
     # restored WEIGHTS with a fresh optimiser: the saved slots belong to the variables that were trainable then.
     trainable = None
+    # loss and heads (TrainerController.py:23-24 and the manuscript's bounded heads): weight of the divergence term, weight of the non-fluid
+    # region in both terms (1 = the reference's shipped loss, 0 = fluid only), output activation of the heads (None / 'linear' | 'tanh')
+    div_weight = 0
+    non_fluid_weight = 1
+    output_activation = None
 
     parallel.init_from_env()
     trainset = data.load_indexes(training_file)
@@ -73,7 +78,8 @@ if __name__ == "__main__":
 
     print("4DFlowNet Patch %d, lr %s, batch %d" % (patch_size, initial_learning_rate, batch_size))
     network = trainer.TrainerController(patch_size, res_increase, initial_learning_rate, QUICKSAVE, network_name,
-                                        low_resblock, hi_resblock, accum_steps=accum_steps, trainable=trainable)
+                                        low_resblock, hi_resblock, accum_steps=accum_steps, trainable=trainable, div_weight=div_weight,
+                                        non_fluid_weight=non_fluid_weight, output_activation=output_activation)
     network.init_model_dir()
     if restore and trainable is not None:
         print("Fine-tuning from the weights of %s..." % model_file)
