@@ -15,9 +15,24 @@ __device__ __forceinline__ float norm3(float a, float b, float c) {
     return sqrtf(__builtin_fmaf(c, c, __builtin_fmaf(a, a, b * b)));
 }
 
-// Sliding-window geometry of fdn_input_features_volume (src/Network/PatchGenerator.py:13-40,53-86): with P > 0 the six inputs of output
-// voxel i are gathered from resident frames (F,6,X,Y,Z) at u -- patch g0 + i / P^3 of the window at stride P - 4, shifted by the 2-voxel
-// side pad, zero outside the volume -- instead of being read at u[i] .. mw[i].  P == 0: no geometry (fdn_input_features).
+// fdn_input_features: the six inputs of voxel i are u[i] .. mw[i].
+template <typename T>
+__global__ void input_features_kernel(const float* __restrict__ u, const float* __restrict__ v, const float* __restrict__ w,
+                                      const float* __restrict__ mu, const float* __restrict__ mv,
+                                      const float* __restrict__ mw, T* __restrict__ phase, T* __restrict__ pc, int64_t nvox) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvox; i += (int64_t)gridDim.x * blockDim.x) {
+        const float a = u[i], b = v[i], c = w[i];
+        const float ma = mu[i], mb = mv[i], mc = mw[i];
+        const float speed = norm3(a, b, c);
+        const float mag = norm3(ma, mb, mc);
+        fdn_st1(phase + i * 3 + 0, a); fdn_st1(phase + i * 3 + 1, b); fdn_st1(phase + i * 3 + 2, c);
+        fdn_st1(pc + i * 3 + 0, mag * speed); fdn_st1(pc + i * 3 + 1, mag); fdn_st1(pc + i * 3 + 2, speed);
+    }
+}
+
+// Sliding-window geometry of fdn_input_features_volume (src/Network/PatchGenerator.py:13-40,53-86): the six inputs of output voxel i
+// are gathered from resident frames (F,6,X,Y,Z) -- patch g0 + i / P^3 of the window at `stride`, shifted by the 2-voxel side pad, zero
+// outside the volume.
 // orient != 0 (fdn_input_features_volume_oriented, an fdn_orient_word): the features of the patch as PatchHandler3D.apply_rotation
 // (src/Network/PatchHandler3D.py:97-108,166-274) would turn it -- voxel (a,b,c) reads the window voxel np.rot90 puts there, the zero
 // fill comes first, then the components are permuted and signed by multiplication (a padded zero under a negative sign is -0.0, as on
@@ -31,45 +46,37 @@ struct InputGeom {
 };
 
 template <typename T>
-__global__ void input_features_kernel(const float* __restrict__ u, const float* __restrict__ v, const float* __restrict__ w,
-                                      const float* __restrict__ mu, const float* __restrict__ mv,
-                                      const float* __restrict__ mw, T* __restrict__ phase, T* __restrict__ pc,
-                                      int64_t nvox, InputGeom geo) {
+__global__ void input_features_volume_kernel(const float* __restrict__ frames, T* __restrict__ phase, T* __restrict__ pc, int64_t nvox,
+                                             InputGeom geo) {
     const int P = geo.P, E = geo.stride;
     const int64_t per = (int64_t)P * P * P, plane = (int64_t)geo.X * geo.Y * geo.Z;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvox; i += (int64_t)gridDim.x * blockDim.x) {
-        float a, b, c, ma, mb, mc;
-        if (P == 0) {
-            a = u[i]; b = v[i]; c = w[i];
-            ma = mu[i]; mb = mv[i]; mc = mw[i];
-        } else {
-            const int64_t n = i / per;                       // patch of this launch
-            int r = (int)(i - n * per);                      // voxel of the patch, z fastest
-            int pa = r / (P * P); r -= pa * P * P;
-            int pb = r / P, pcz = r - pb * P;
-            int64_t g = geo.g0 + n;                          // global patch: frame, then (i, j, k) with k fastest
-            const int pk = (int)(g % geo.nz); g /= geo.nz;
-            const int pj = (int)(g % geo.ny); g /= geo.ny;
-            const int pi = (int)(g % geo.nx);
-            const int64_t f = g / geo.nx;
-            if (geo.orient) fdn_rot_source(geo.orient, P, pa, pb, pcz);
-            const int x = pi * E + pa - 2, y = pj * E + pb - 2, z = pk * E + pcz - 2;
-            a = b = c = ma = mb = mc = 0.f;
-            if (x >= 0 && x < geo.X && y >= 0 && y < geo.Y && z >= 0 && z < geo.Z) {
-                const float* s = u + f * 6 * plane + ((int64_t)x * geo.Y + y) * geo.Z + z;
-                a = s[0]; b = s[plane]; c = s[2 * plane];
-                ma = s[3 * plane]; mb = s[4 * plane]; mc = s[5 * plane];
-            }
-            if (geo.orient) {
-                const int s0 = fdn_orient_src(geo.orient, 0), s1 = fdn_orient_src(geo.orient, 1), s2 = fdn_orient_src(geo.orient, 2);
-                const float a0 = a, b0 = b, c0 = c, ma0 = ma, mb0 = mb, mc0 = mc;
-                a = (s0 == 0 ? a0 : s0 == 1 ? b0 : c0) * fdn_orient_sign(geo.orient, 0);
-                b = (s1 == 0 ? a0 : s1 == 1 ? b0 : c0) * fdn_orient_sign(geo.orient, 1);
-                c = (s2 == 0 ? a0 : s2 == 1 ? b0 : c0) * fdn_orient_sign(geo.orient, 2);
-                ma = s0 == 0 ? ma0 : s0 == 1 ? mb0 : mc0;
-                mb = s1 == 0 ? ma0 : s1 == 1 ? mb0 : mc0;
-                mc = s2 == 0 ? ma0 : s2 == 1 ? mb0 : mc0;
-            }
+        const int64_t n = i / per;                       // patch of this launch
+        int r = (int)(i - n * per);                      // voxel of the patch, z fastest
+        int pa = r / (P * P); r -= pa * P * P;
+        int pb = r / P, pcz = r - pb * P;
+        int64_t g = geo.g0 + n;                          // global patch: frame, then (i, j, k) with k fastest
+        const int pk = (int)(g % geo.nz); g /= geo.nz;
+        const int pj = (int)(g % geo.ny); g /= geo.ny;
+        const int pi = (int)(g % geo.nx);
+        const int64_t f = g / geo.nx;
+        if (geo.orient) fdn_rot_source(geo.orient, P, pa, pb, pcz);
+        const int x = pi * E + pa - 2, y = pj * E + pb - 2, z = pk * E + pcz - 2;
+        float a = 0.f, b = 0.f, c = 0.f, ma = 0.f, mb = 0.f, mc = 0.f;
+        if (x >= 0 && x < geo.X && y >= 0 && y < geo.Y && z >= 0 && z < geo.Z) {
+            const float* s = frames + f * 6 * plane + ((int64_t)x * geo.Y + y) * geo.Z + z;
+            a = s[0]; b = s[plane]; c = s[2 * plane];
+            ma = s[3 * plane]; mb = s[4 * plane]; mc = s[5 * plane];
+        }
+        if (geo.orient) {
+            const int s0 = fdn_orient_src(geo.orient, 0), s1 = fdn_orient_src(geo.orient, 1), s2 = fdn_orient_src(geo.orient, 2);
+            const float a0 = a, b0 = b, c0 = c, ma0 = ma, mb0 = mb, mc0 = mc;
+            a = (s0 == 0 ? a0 : s0 == 1 ? b0 : c0) * fdn_orient_sign(geo.orient, 0);
+            b = (s1 == 0 ? a0 : s1 == 1 ? b0 : c0) * fdn_orient_sign(geo.orient, 1);
+            c = (s2 == 0 ? a0 : s2 == 1 ? b0 : c0) * fdn_orient_sign(geo.orient, 2);
+            ma = s0 == 0 ? ma0 : s0 == 1 ? mb0 : mc0;
+            mb = s1 == 0 ? ma0 : s1 == 1 ? mb0 : mc0;
+            mc = s2 == 0 ? ma0 : s2 == 1 ? mb0 : mc0;
         }
         const float speed = norm3(a, b, c);
         const float mag = norm3(ma, mb, mc);
@@ -364,16 +371,14 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Whole-volume evaluation (fdn_volume_metrics): a path of the three loss kernels selected by one by-value int, `vm` (0: the training
-// paths above and below, untouched; else VM_MODE(pass, pred_is_f64, per_frame_mask)).  The operands travel in the kernels' existing
-// parameters -- four bytes more per launch: the training call is bound by its launches -- and each kernel views them as a VolumeMetrics.  pred (F,3,X,Y,Z) fp32 or float64, truth (F,3,X,Y,Z), mask
-// (mask_frames,X,Y,Z); everything is summed in double.  part: per-block partials (F, gridDim.x, 26), every column written by
-// exactly one pass; loss_finalize_kernel adds them over the blocks in a fixed order.
-//   mask_sums_kernel  pass 1: columns 0-2 (sum m, sum nf, sum fl)
-//   loss_main_kernel  pass 1: columns 3-8 (q, corr, e_c^2)      pass 2: columns 9-10 (d: the pass that gathers the stencil neighbours)
+// Whole-volume evaluation (fdn_volume_metrics): three kernels of its own, each taking a VolumeMetrics by value.  pred (F,3,X,Y,Z) fp32
+// or float64, truth (F,3,X,Y,Z), mask (mask_frames,X,Y,Z); everything is summed in double.  part: per-block partials
+// (F, gridDim.x, 26), every column written by exactly one pass; volume_finalize_kernel adds them over the blocks in a fixed order.
+//   volume_mask_sums_kernel       columns 0-2 (sum m, sum nf, sum fl)
+//   volume_metrics_kernel pass 1: columns 3-8 (q, corr, e_c^2)      pass 2: columns 9-10 (d: the pass that gathers the stencil neighbours)
 //                     pass 3 + c: columns 11 + 5c .. 15 + 5c (the regression moments of component c over the fl voxels)
-// One pass holding all 26 double accumulators would take loss_main_kernel past 72 VGPRs and the training paths from seven waves per
-// SIMD to fewer; each column is accumulated by the same threads in the same order whatever the grouping.
+// 26 double accumulators are 52 VGPRs; a pass holds at most six of them, and each column is accumulated by the same threads in the
+// same order whatever the grouping.
 // ---------------------------------------------------------------------------------------------
 struct VolumeMetrics {
     const void* pred;
@@ -383,10 +388,6 @@ struct VolumeMetrics {
     double* out;
     int32_t pass, pred_is_f64, per_frame_mask, X, Y, Z;
 };
-#define VM_MODE(pass, f64, per_frame) ((pass) | ((f64) << 8) | ((per_frame) << 9))
-#define VM_PASS(vm) ((vm) & 0xff)
-#define VM_F64(vm) (((vm) >> 8) & 1)
-#define VM_PER_FRAME(vm) (((vm) >> 9) & 1)
 
 __device__ __forceinline__ double block_sum_d(double v, double* red) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -411,7 +412,8 @@ __device__ __forceinline__ double vm_axis_diff(const VolumeMetrics& a, int64_t b
     return (vm_pred(a, lo) - (double)a.truth[lo]) - (vm_pred(a, hi) - (double)a.truth[hi]);
 }
 
-__device__ __forceinline__ void volume_mask_sums(const VolumeMetrics& a, double* red) {
+__global__ __launch_bounds__(256) void volume_mask_sums_kernel(VolumeMetrics a) {
+    __shared__ double red[4];
     const int f = blockIdx.y;
     const int64_t V = (int64_t)a.X * a.Y * a.Z;
     const float* mask = a.mask + (a.per_frame_mask ? (int64_t)f * V : 0);
@@ -431,7 +433,8 @@ __device__ __forceinline__ void volume_mask_sums(const VolumeMetrics& a, double*
     }
 }
 
-__device__ __forceinline__ void volume_main(const VolumeMetrics& a, double* red) {
+__global__ __launch_bounds__(256) void volume_metrics_kernel(VolumeMetrics a) {
+    __shared__ double red[4];
     const int f = blockIdx.y;
     const int64_t YZ = (int64_t)a.Y * a.Z, V = (int64_t)a.X * YZ;
     const float* mask = a.mask + (a.per_frame_mask ? (int64_t)f * V : 0);
@@ -504,7 +507,7 @@ __device__ __forceinline__ void volume_main(const VolumeMetrics& a, double* red)
 }
 
 // one wave per frame, column by column: lane t adds the partials of blocks t, t + 64, ... in block order, then the shuffle tree
-__device__ __forceinline__ void volume_finalize(const VolumeMetrics& a, int nblk) {
+__global__ __launch_bounds__(64) void volume_finalize_kernel(VolumeMetrics a, int nblk) {
     const int f = blockIdx.x;
     const double* part = a.part + (size_t)f * nblk * 26;
     for (int col = 0; col < 26; ++col) {
@@ -515,14 +518,8 @@ __device__ __forceinline__ void volume_finalize(const VolumeMetrics& a, int nblk
     }
 }
 
-__global__ __launch_bounds__(256) void mask_sums_kernel(const float* __restrict__ mask, float* __restrict__ scratch, int64_t V,
-                                                         int vm) {
+__global__ __launch_bounds__(256) void mask_sums_kernel(const float* __restrict__ mask, float* __restrict__ scratch, int64_t V) {
     __shared__ float red[4];
-    __shared__ double redd[4];
-    if (vm) {                                                        // scratch: the doubles of fdn_volume_metrics; V < 2^31 voxels per frame
-        volume_mask_sums(VolumeMetrics{nullptr, nullptr, mask, (double*)scratch, nullptr, VM_PASS(vm), 0, VM_PER_FRAME(vm), (int)V, 1, 1}, redd);
-        return;
-    }
     const int n = blockIdx.y;
     float sm = 0.f, snf = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (int64_t)gridDim.x * blockDim.x) {
@@ -584,13 +581,8 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
                                                          const float* __restrict__ vh, const float* __restrict__ wh,
                                                          const float* __restrict__ mask, float* __restrict__ scratch,
                                                          float* __restrict__ dpred, int64_t V, int D, int H, int W, float div_w,
-                                                         int nparts, int vm, float nf_w, int out_act) {
+                                                         int nparts, float nf_w, int out_act) {
     __shared__ float red[4];
-    __shared__ double redd[4];
-    if (vm) {                                                        // pred: fp32 or float64; uh: truth; scratch: doubles; D,H,W = X,Y,Z
-        volume_main(VolumeMetrics{pred, uh, mask, (double*)scratch, nullptr, VM_PASS(vm), VM_F64(vm), VM_PER_FRAME(vm), D, H, W}, redd);
-        return;
-    }
     const int n = blockIdx.y;
     const float inv_f = 1.f / (scratch[n * 8 + 0] + 1.f);
     const float inv_nf = nf_w * (1.f / (scratch[n * 8 + 1] + 1.f));     // non_fluid_weight rides on the region's scalar: exact at 1
@@ -683,11 +675,7 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
 // nparts 3: out (N,4); nparts 5: out (N,5), column 4 = div_w * (sum m d / (sum m + 1) + nf_w * sum nf d / (sum nf + 1)); nf_w also weighs
 // the non-fluid part of column 0 (a multiplication by 1.f, exact, everywhere but in fdn_loss_metrics_act).
 __global__ __launch_bounds__(64) void loss_finalize_kernel(const float* __restrict__ scratch, float* __restrict__ out, int N, int nblk,
-                                                           int nparts, float div_w, int vm, float nf_w) {
-    if (vm) {                                                        // scratch, out: the doubles of fdn_volume_metrics
-        volume_finalize(VolumeMetrics{nullptr, nullptr, nullptr, (double*)scratch, (double*)out, VM_PASS(vm), 0, 0, 0, 0, 0}, nblk);
-        return;
-    }
+                                                           int nparts, float div_w, float nf_w) {
     const int n = blockIdx.x;
     const float* part = scratch + (size_t)N * 8 + (size_t)n * nblk * nparts;
     float sf = 0.f, sn = 0.f, sr = 0.f, sdf = 0.f, sdn = 0.f;
@@ -742,13 +730,6 @@ __device__ __forceinline__ void block_partial(float ss, float* __restrict__ out)
 // sumsq != null: block b also writes sum(w_new^2) over its kernel (non-bias) elements to sumsq[b] (fixed order: the
 // regulariser value of the NEXT step's loss, so fdn_l2_sumsq does not have to stream the parameters again).
 // lr_t_dev != null: the step size is lr_t_dev[0], read on the device (fdn_adam_step_dev: a captured launch must not bake it in).
-// accum != 0 (fdn_grad_accumulate): the sum of micro-batch gradient buffers as a path of this kernel selected by one by-value int --
-// w[i] = g[i] (ACCUM_FIRST) or w[i] + g[i] (ACCUM_ADD); m .. sumsq are not read.  Scalar accesses: w and g are bucket slices at any
-// float offset, and the 13.4 MB of cfg2 are not where the step's time is.
-// accum == GRAD_SUMSQ (fdn_grad_sumsq_partials: gradient clipping, tf.clip_by_global_norm): nothing is written but sumsq[b] = block b's
-// sum of g'^2, g' = g + l2s * w (kernels only) formed as the Adam path below forms it, over the elements with frozen[i] == 0 -- the
-// square of the norm Keras clips, TrainerController.py:73,223-225.  Here rather than in l2_sumsq_partials_kernel: this kernel's
-// parameter list already carries g, w, isk, frozen and the two halves of l2s, and the blocking is the same.
 // frozen != null (fdn_adam_step_masked: fine-tuning, one byte per parameter like isk): an element with frozen[i] != 0 keeps w, m and v --
 // g[i], m[i] and v[i] are neither loaded nor stored -- and still adds w[i]^2 to its block's sum when it is a kernel: the regulariser
 // value covers every kernel (TrainerController.py:129-141).  An element with frozen[i] == 0 takes the statements below unchanged.
@@ -758,36 +739,12 @@ __device__ __forceinline__ void block_partial(float ss, float* __restrict__ out)
 // ema[i] = mom * ema[i] + (1.f - mom) * wn in fp32, formed from the wn in the register right behind the store of w[i]; ema_init != 0
 // (the first step with an average): ema[i] is not loaded, the average starts at wi, the weight before the step.  A frozen element
 // stores the wi it loaded: the average of a frozen parameter is its weight.  w, m, v and sumsq get the bits of the call without ema.
-#define ACCUM_FIRST 1
-#define ACCUM_ADD 2
-#define GRAD_SUMSQ 3
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, const uint8_t* __restrict__ isk, int64_t n, float lr_t_host,
                                                    const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float l2s_host,
-                                                   const float* __restrict__ l2s_dev, float* __restrict__ sumsq, int accum,
+                                                   const float* __restrict__ l2s_dev, float* __restrict__ sumsq,
                                                    const uint8_t* __restrict__ frozen, const float* __restrict__ g_scale_dev,
                                                    float clip_value, float* __restrict__ ema, float ema_momentum, int ema_init) {
-    if (accum == GRAD_SUMSQ) {                                       // fdn_grad_sumsq_partials: w is only read
-        const float l2s = l2s_dev ? l2s_host * l2s_dev[0] : l2s_host;
-        float ss = 0.f;
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-            if (frozen && frozen[i]) continue;                       // g[i] is not loaded; the element adds +0
-            float gi = g[i];
-            if (isk[i]) gi += l2s * w[i];
-            ss += gi * gi;
-        }
-        block_partial(ss, sumsq);
-        return;
-    }
-    if (accum) {                                                     // fdn_grad_accumulate: w is the accumulator, g one micro-batch's gradients;
-        const bool first = accum == ACCUM_FIRST;                     // nothing else is read.  Uniform, ahead of the Adam path's first load
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-            const float gi = g[i];
-            if (first) w[i] = gi;                                    // a bit copy: the accumulator's old contents are never loaded
-            else w[i] = w[i] + gi;                                   // one IEEE fp32 add
-        }
-        return;
-    }
     const float lr_t = lr_t_dev ? lr_t_dev[0] : lr_t_host;
     const float l2s = l2s_dev ? l2s_host * l2s_dev[0] : l2s_host;
     const float g_scale = g_scale_dev ? g_scale_dev[0] : 1.f;
@@ -816,6 +773,34 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const 
     if (sumsq) block_partial(ss, sumsq);
 }
 
+// fdn_grad_accumulate: the sum of micro-batch gradient buffers, acc[i] = g[i] (first) or acc[i] + g[i].  Scalar accesses: acc and g are
+// bucket slices at any float offset, and the 13.4 MB of cfg2 are not where the step's time is.
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n, int first) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float gi = g[i];
+        if (first) acc[i] = gi;                                      // a bit copy: the accumulator's old contents are never loaded
+        else acc[i] = acc[i] + gi;                                   // one IEEE fp32 add
+    }
+}
+
+// fdn_grad_sumsq_partials (gradient clipping, tf.clip_by_global_norm): sumsq[b] = block b's sum of g'^2, g' = g + l2s * w (kernels only)
+// formed as adam_kernel forms it, over the elements with frozen[i] == 0 -- the square of the norm Keras clips,
+// TrainerController.py:73,223-225.  The blocking of adam_kernel's own partials (FDN_ADAM_PARTIALS blocks, block_partial).
+__global__ __launch_bounds__(256) void grad_sumsq_partials_kernel(const float* __restrict__ g, const float* __restrict__ w,
+                                                                  const uint8_t* __restrict__ isk, const uint8_t* __restrict__ frozen,
+                                                                  int64_t n, float l2s_host, const float* __restrict__ l2s_dev,
+                                                                  float* __restrict__ sumsq) {
+    const float l2s = l2s_dev ? l2s_host * l2s_dev[0] : l2s_host;
+    float ss = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (frozen && frozen[i]) continue;                           // g[i] is not loaded; the element adds +0
+        float gi = g[i];
+        if (isk[i]) gi += l2s * w[i];
+        ss += gi * gi;
+    }
+    block_partial(ss, sumsq);
+}
+
 // The same per-block sums the Adam kernel leaves behind (identical blocking: block b covers the elements b * 256 + t + k * grid * 256),
 // for the steps that have no Adam step before them (first step, load_weights): FDN_ADAM_PARTIALS blocks stream the parameters at the
 // rate of the chip instead of one block at 9 GB/s (l2_sumsq_kernel: 1.87 ms for the 13.4 MB of cfg2)
@@ -827,13 +812,8 @@ __global__ __launch_bounds__(256) void l2_sumsq_partials_kernel(const float* __r
     block_partial(ss, sumsq);
 }
 
-// out[0] = sum of n partials, one block, fixed order (deterministic).
-// clip_norm > 0 (fdn_clip_scale): the partials are those of fdn_grad_sumsq_partials and their sum S becomes out[0] = N = sqrtf(S), the
-// global norm, and out[1] = s = clip_norm / max(N, clip_norm), the factor of tf.clip_by_global_norm: exactly 1.0f whenever
-// N <= clip_norm (x / x), so an inactive clip changes no bit downstream.  TF writes clip_norm * min(1 / N, 1 / clip_norm): two roundings
-// instead of one, equal up to rounding.  N not finite (an inf or NaN gradient, or squares that overflow): s = NaN, which makes every
-// parameter the step updates NaN, as in TF.
-__global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restrict__ part, int n, float* __restrict__ out, float clip_norm) {
+// The sum of n partials by one block of 256 threads in a fixed order (deterministic); valid in thread 0.
+__device__ __forceinline__ float sum_partials(const float* __restrict__ part, int n) {
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += part[i];
@@ -841,15 +821,26 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restri
     for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
+    return threadIdx.x == 0 ? (red[0] + red[1]) + (red[2] + red[3]) : 0.f;
+}
+
+// fdn_sum_partials: out[0] = that sum.
+__global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
+    const float total = sum_partials(part, n);
+    if (threadIdx.x == 0) out[0] = total;
+}
+
+// fdn_clip_scale: the partials are those of fdn_grad_sumsq_partials and their sum S becomes out[0] = N = sqrtf(S), the global norm, and
+// out[1] = s = clip_norm / max(N, clip_norm), the factor of tf.clip_by_global_norm: exactly 1.0f whenever N <= clip_norm (x / x), so an
+// inactive clip changes no bit downstream.  TF writes clip_norm * min(1 / N, 1 / clip_norm): two roundings instead of one, equal up to
+// rounding.  N not finite (an inf or NaN gradient, or squares that overflow): s = NaN, which makes every parameter the step updates
+// NaN, as in TF.
+__global__ __launch_bounds__(256) void clip_scale_kernel(const float* __restrict__ part, int n, float* __restrict__ out, float clip_norm) {
+    const float total = sum_partials(part, n);
     if (threadIdx.x == 0) {
-        const float total = (red[0] + red[1]) + (red[2] + red[3]);
-        if (clip_norm > 0.f) {
-            const float norm = sqrtf(total);
-            out[0] = norm;
-            out[1] = __builtin_isfinite(norm) ? clip_norm / (norm > clip_norm ? norm : clip_norm) : __builtin_nanf("");
-        } else {
-            out[0] = total;
-        }
+        const float norm = sqrtf(total);
+        out[0] = norm;
+        out[1] = __builtin_isfinite(norm) ? clip_norm / (norm > clip_norm ? norm : clip_norm) : __builtin_nanf("");
     }
 }
 
@@ -872,7 +863,7 @@ static int input_features_t(const float* u, const float* v, const float* w, cons
                             T* phase, T* pc, int64_t nvox, void* stream) {
     FDN_REQUIRE(u && v && w && mu && mv && mw && phase && pc && nvox > 0, "fdn_input_features: NULL argument or nvox<=0");
     hipLaunchKernelGGL(input_features_kernel<T>, dim3(grid_for(nvox)), dim3(256), 0, (hipStream_t)stream, u, v, w, mu, mv, mw,
-                       phase, pc, nvox, InputGeom{});
+                       phase, pc, nvox);
     FDN_CHECK_LAUNCH("input_features_kernel");
     return FDN_OK;
 }
@@ -896,10 +887,9 @@ static int input_features_volume_t(const char* who, const float* frames, int F, 
     geo.orient = plane ? word : 0;
     geo.stride = strided ? stride : P - 4;
     geo.P = P; geo.X = X; geo.Y = Y; geo.Z = Z; geo.nx = nx; geo.ny = ny; geo.nz = nz; geo.g0 = g0;
-    hipLaunchKernelGGL(input_features_kernel<T>, dim3(grid_for(nvox)), dim3(256), 0, (hipStream_t)stream, frames,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, phase, pc, nvox, geo);      // the frames travel as `u`; v .. mw are not read
-    FDN_CHECK_LAUNCH("input_features_kernel");
+    hipLaunchKernelGGL(input_features_volume_kernel<T>, dim3(grid_for(nvox)), dim3(256), 0, (hipStream_t)stream, frames, phase, pc, nvox,
+                       geo);
+    FDN_CHECK_LAUNCH("input_features_volume_kernel");
     return FDN_OK;
 }
 extern "C" int fdn_input_features(const float* u, const float* v, const float* w, const float* mu, const float* mv,
@@ -1052,12 +1042,12 @@ static int loss_launch(const char* who, const float* pred, const float* uh, cons
     if (e != hipSuccess) { fdn_set_error("%s: memset: %s", who, hipGetErrorString(e)); return FDN_ERR_HIP; }
     const int gx = grid_for(V, FDN_LOSS_BLOCKS);
     // (16 blocks per sample: with 256 the 2 x 256 x N atomics on 2 N words took longer than reading the mask -- 29 us at cfg2)
-    hipLaunchKernelGGL(mask_sums_kernel, dim3(gx < 16 ? gx : 16, N), dim3(256), 0, s, mask, scratch, V, 0);
+    hipLaunchKernelGGL(mask_sums_kernel, dim3(gx < 16 ? gx : 16, N), dim3(256), 0, s, mask, scratch, V);
     FDN_CHECK_LAUNCH("mask_sums_kernel");
-    hipLaunchKernelGGL(loss_main_kernel, dim3(gx, N), dim3(256), 0, s, pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts, 0,
+    hipLaunchKernelGGL(loss_main_kernel, dim3(gx, N), dim3(256), 0, s, pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts,
                        nf_w, out_act);
     FDN_CHECK_LAUNCH("loss_main_kernel");
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(N), dim3(64), 0, s, (const float*)scratch, out, N, gx, nparts, div_w, 0, nf_w);
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(N), dim3(64), 0, s, (const float*)scratch, out, N, gx, nparts, div_w, nf_w);
     FDN_CHECK_LAUNCH("loss_finalize_kernel");
     return FDN_OK;
 }
@@ -1114,17 +1104,15 @@ extern "C" int fdn_volume_metrics(const void* pred, int pred_is_f64, const float
     FDN_REQUIRE(pred_is_f64 == 0 || pred_is_f64 == 1, "fdn_volume_metrics: pred_is_f64=%d must be 0 or 1", pred_is_f64);
     hipStream_t s = (hipStream_t)stream;
     const int gx = grid_for((int64_t)X * Y * Z, FDN_LOSS_BLOCKS);
-    const int f64 = pred_is_f64, per_frame = mask_frames != 1 ? 1 : 0;
-    hipLaunchKernelGGL(mask_sums_kernel, dim3(gx, F), dim3(256), 0, s, mask, (float*)scratch, (int64_t)X * Y * Z, VM_MODE(1, 0, per_frame));
-    FDN_CHECK_LAUNCH("mask_sums_kernel (volume metrics)");
-    for (int pass = 1; pass <= 5; ++pass) {                              // columns 3-8, 9-10, then the five moments of u, v, w
-        hipLaunchKernelGGL(loss_main_kernel, dim3(gx, F), dim3(256), 0, s, (const float*)pred, truth, (const float*)nullptr,
-                           (const float*)nullptr, mask, (float*)scratch, (float*)nullptr, (int64_t)X * Y * Z, X, Y, Z, 0.f, 0,
-                           VM_MODE(pass, f64, per_frame), 1.f, FDN_ACT_NONE);
-        FDN_CHECK_LAUNCH("loss_main_kernel (volume metrics)");
+    VolumeMetrics a{pred, truth, mask, scratch, out, 0, pred_is_f64, mask_frames != 1 ? 1 : 0, X, Y, Z};
+    hipLaunchKernelGGL(volume_mask_sums_kernel, dim3(gx, F), dim3(256), 0, s, a);
+    FDN_CHECK_LAUNCH("volume_mask_sums_kernel");
+    for (a.pass = 1; a.pass <= 5; ++a.pass) {                            // columns 3-8, 9-10, then the five moments of u, v, w
+        hipLaunchKernelGGL(volume_metrics_kernel, dim3(gx, F), dim3(256), 0, s, a);
+        FDN_CHECK_LAUNCH("volume_metrics_kernel");
     }
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(F), dim3(64), 0, s, (const float*)scratch, (float*)out, F, gx, 0, 0.f, VM_MODE(1, 0, 0), 1.f);
-    FDN_CHECK_LAUNCH("loss_finalize_kernel (volume metrics)");
+    hipLaunchKernelGGL(volume_finalize_kernel, dim3(F), dim3(64), 0, s, a, gx);
+    FDN_CHECK_LAUNCH("volume_finalize_kernel");
     return FDN_OK;
 }
 
@@ -1143,20 +1131,20 @@ extern "C" int fdn_l2_sumsq_partials(const float* w, const uint8_t* is_kernel, i
     return FDN_OK;
 }
 
-// adam_kernel's parameters by name (the kernel keeps its flat list): an entry point sets what its path reads, the rest stays "absent".
+// adam_kernel's parameters by name (the kernel keeps its flat list): an Adam entry point sets the options it has, the rest stay "absent".
 struct AdamOperands {
     float *w = nullptr, *m = nullptr, *v = nullptr, *sumsq = nullptr, *ema = nullptr;
     const float *g = nullptr, *lr_t_dev = nullptr, *l2_scale_dev = nullptr, *g_scale_dev = nullptr;
     const uint8_t *is_kernel = nullptr, *frozen = nullptr;
     int64_t n = 0;
     float lr_t = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f, l2_grad_scale = 0.f, clip_value = 0.f, ema_momentum = 0.f;
-    int accum = 0, ema_init = 0;
+    int ema_init = 0;
 };
 
 // The one place adam_kernel is launched from.
 static int launch_adam(const AdamOperands& a, int grid, hipStream_t stream, const char* what) {
     hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, stream, a.w, a.g, a.m, a.v, a.is_kernel, a.n, a.lr_t, a.lr_t_dev, a.b1, a.b2,
-                       a.eps, a.l2_grad_scale, a.l2_scale_dev, a.sumsq, a.accum, a.frozen, a.g_scale_dev, a.clip_value,
+                       a.eps, a.l2_grad_scale, a.l2_scale_dev, a.sumsq, a.frozen, a.g_scale_dev, a.clip_value,
                        a.ema, a.ema_momentum, a.ema_init);
     FDN_CHECK_LAUNCH(what);
     return FDN_OK;
@@ -1214,21 +1202,21 @@ extern "C" int fdn_grad_accumulate(float* acc, const float* g, int64_t n, int fi
     FDN_REQUIRE((uint64_t)n <= (UINTPTR_MAX - (a > b ? a : b)) / sizeof(float), "fdn_grad_accumulate: n=%lld floats run past the address space", (long long)n);
     FDN_REQUIRE((a > b ? a - b : b - a) >= bytes, "fdn_grad_accumulate: acc and g overlap (%lld bytes apart, n=%lld floats): an in-place call would double the buffer",
                 (long long)(a > b ? a - b : b - a), (long long)n);
-    AdamOperands op;
-    op.w = acc, op.g = g, op.n = n, op.accum = first ? ACCUM_FIRST : ACCUM_ADD;
-    return launch_adam(op, grid_for(n), (hipStream_t)stream, "adam_kernel (grad accumulate)");
+    hipLaunchKernelGGL(grad_accumulate_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, acc, g, n, first);
+    FDN_CHECK_LAUNCH("grad_accumulate_kernel");
+    return FDN_OK;
 }
 
 extern "C" int fdn_sum_partials(const float* partials, int n, float* out, void* stream) {
     FDN_REQUIRE(partials && out && n > 0, "fdn_sum_partials: bad argument");
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, out, 0.f);
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n, out);
     FDN_CHECK_LAUNCH("sum_partials_kernel");
     return FDN_OK;
 }
 
-// Gradient clipping (tf.keras.optimizers.Adam(global_clipnorm= / clipvalue=), TrainerController.py:73): three launches of kernels that
-// exist already -- the sum of squares of the step's gradient and the clipped step as paths of adam_kernel, norm and scale as a path of
-// sum_partials_kernel.  The scale stays on the device between the second and the third.
+// Gradient clipping (tf.keras.optimizers.Adam(global_clipnorm= / clipvalue=), TrainerController.py:73): three launches -- the sum of
+// squares of the step's gradient (grad_sumsq_partials_kernel), norm and scale (clip_scale_kernel), and the clipped step (adam_kernel).
+// The scale stays on the device between the second and the third.
 extern "C" int fdn_grad_sumsq_partials(const float* g, const float* w, const uint8_t* is_kernel, const uint8_t* frozen, int64_t n,
                                        float l2_grad_scale, const float* l2_scale_dev, float* partials, void* stream) {
     FDN_REQUIRE(g, "fdn_grad_sumsq_partials: g is NULL");
@@ -1236,10 +1224,10 @@ extern "C" int fdn_grad_sumsq_partials(const float* g, const float* w, const uin
     FDN_REQUIRE(is_kernel, "fdn_grad_sumsq_partials: is_kernel is NULL");
     FDN_REQUIRE(partials, "fdn_grad_sumsq_partials: partials is NULL");
     FDN_REQUIRE(n > 0, "fdn_grad_sumsq_partials: n=%lld must be positive", (long long)n);
-    AdamOperands a;
-    a.w = const_cast<float*>(w), a.g = g, a.is_kernel = is_kernel, a.n = n;          // (this path only reads w)
-    a.l2_grad_scale = l2_grad_scale, a.l2_scale_dev = l2_scale_dev, a.sumsq = partials, a.accum = GRAD_SUMSQ, a.frozen = frozen;
-    return launch_adam(a, FDN_ADAM_PARTIALS, (hipStream_t)stream, "adam_kernel (gradient sum of squares)");
+    hipLaunchKernelGGL(grad_sumsq_partials_kernel, dim3(FDN_ADAM_PARTIALS), dim3(256), 0, (hipStream_t)stream, g, w, is_kernel, frozen, n,
+                       l2_grad_scale, l2_scale_dev, partials);
+    FDN_CHECK_LAUNCH("grad_sumsq_partials_kernel");
+    return FDN_OK;
 }
 
 extern "C" int fdn_clip_scale(const float* partials, int n_partials, float clip_norm, float* out, void* stream) {
@@ -1247,8 +1235,8 @@ extern "C" int fdn_clip_scale(const float* partials, int n_partials, float clip_
     FDN_REQUIRE(out, "fdn_clip_scale: out is NULL");
     FDN_REQUIRE(n_partials > 0, "fdn_clip_scale: n_partials=%d must be positive", n_partials);
     FDN_REQUIRE(__builtin_isfinite(clip_norm) && clip_norm > 0.f, "fdn_clip_scale: clip_norm=%g must be finite and > 0", (double)clip_norm);
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, out, clip_norm);
-    FDN_CHECK_LAUNCH("sum_partials_kernel (clip scale)");
+    hipLaunchKernelGGL(clip_scale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, out, clip_norm);
+    FDN_CHECK_LAUNCH("clip_scale_kernel");
     return FDN_OK;
 }
 
@@ -1270,7 +1258,7 @@ extern "C" int fdn_adam_step_clipped(float* w, const float* g, float* m, float* 
     return launch_adam(a, adam_step_grid(n, sumsq_partials), (hipStream_t)stream, "adam_kernel (clipped)");
 }
 
-// Weight EMA (tf.keras.optimizers.Adam(use_ema=True, ema_momentum=)): the clipped step with the average as one more path of adam_kernel.
+// Weight EMA (tf.keras.optimizers.Adam(use_ema=True, ema_momentum=)): the clipped step with the average as one more option of adam_kernel.
 // The widest form: frozen, lr_t_dev, g_scale_dev and l2_scale_dev may be NULL, clip_value may be 0.
 extern "C" int fdn_adam_step_ema(float* w, const float* g, float* m, float* v, const uint8_t* is_kernel, const uint8_t* frozen, int64_t n,
                                  float lr_t, const float* lr_t_dev, float b1, float b2, float eps, float l2_grad_scale,

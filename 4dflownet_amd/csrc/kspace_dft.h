@@ -1,16 +1,16 @@
-// Low-res synthesis on the device (prepare_data/fft_downsampling.py:6-137): the stages of fdn_kspace_downsample, run as modes 5 and 6 of
-// gather_patches_kernel (patch_gather.hip).
+// Low-res synthesis on the device (prepare_data/fft_downsampling.py:6-137): the stage of fdn_kspace_downsample, the body of
+// kspace_stage_kernel<inverse> (kspace.hip).
 //
 // Per axis the reference's fftn -> fftshift -> centre crop -> fftshift is ONE truncated DFT: with half = N / 2, c the crop half-width and
 // M = 2c, output k' in 0..M-1 is frequency k = k' (k' < c) or k' - M (else), F[k'] = sum_n x[n] exp(-2 pi i ((k n) mod N) / N), and the
 // cropped ifftn is z[m] = (1/M) sum_k' F[k'] exp(+2 pi i ((k' m) mod M) / M).  The volumes are small (84 x 76 x 72 -> 42 x 38 x 36: 39 M
 // complex multiply-adds), so a stage is a plain VALU sum, one output element per thread and step, walking one axis of a (outer, N, inner)
 // array with the N (or M) unit roots in dynamic LDS: entry r = sincospif(2.f * r / N), the index (k n) mod N kept in integers.
-//   mode 5, forward:  first = 1 forms x = mag * mag_scale * exp(i pi vel / venc) on the way in (sincospif(vel / venc): the reduction by pi
-//                     is exact, |vel| > venc wraps as in the reference); last = 1 leaves one partial sum of |F|^2 per workgroup.
-//   mode 6, inverse:  first = 1 reads sigma = sqrtf(sum|F|^2 / count / snr_linear) on the device and adds sigma * g to Re F on the way in
-//                     (real noise on the complex spectrum, fft_downsampling.py:63-69); last = 1 writes |z| * ratio and
-//                     atan2(Im z, Re z) / pi * venc instead of z.
+//   forward:  first = 1 forms x = mag * mag_scale * exp(i pi vel / venc) on the way in (sincospif(vel / venc): the reduction by pi
+//             is exact, |vel| > venc wraps as in the reference); last = 1 leaves one partial sum of |F|^2 per workgroup.
+//   inverse:  first = 1 reads sigma = sqrtf(sum|F|^2 / count / snr_linear) on the device and adds sigma * g to Re F on the way in
+//             (real noise on the complex spectrum, fft_downsampling.py:63-69); last = 1 writes |z| * ratio and
+//             atan2(Im z, Re z) / pi * venc instead of z.
 // blockIdx.y is the volume of the batch; blockIdx.x strides over that volume's outputs.
 #pragma once
 #include "fdn_common.h"

@@ -298,7 +298,7 @@ int fdn_loss_metrics_act(const float* pred, const float* uh, const float* vh, co
  *   0,1,2: m, nf, fl    3,4: q m, q nf    5: corr fl    6,7,8: e_c^2 fl (c = u,v,w)    9,10: d m, d nf
  *   11+5c .. 15+5c: t_c fl, p_c fl, t_c^2 fl, p_c^2 fl, t_c p_c fl.
  * scratch: FDN_VOLUME_METRICS_SCRATCH_DOUBLES(F) caller-owned doubles of per-block partials, added in a fixed order (no atomics): two
- * calls give identical bits.  A path of the three loss kernels selected by a by-value argument; the main kernel runs once per group of
+ * calls give identical bits.  Three kernels of its own (volume_mask_sums, volume_metrics, volume_finalize); the main one runs once per group of
  * columns (3-8, 9-10, then the five moments of each component), and no column depends on that grouping.  At most FDN_LOSS_BLOCKS blocks per
  * frame.  Refused before the device is touched: NULL operands, non-positive extents, X*Y*Z > 2^31 - 1, mask_frames not in {1, F},
  * pred_is_f64 not in {0, 1}. */
@@ -321,7 +321,7 @@ int fdn_gather_patches(const void* desc, float* out, int B, int S, void* stream)
  * the stride tile it: nx,ny,nz patches per axis, tiler.PatchGenerator.plan).  Global patch g: frame f = g / (nx*ny*nz), then (i,j,k)
  * with k fastest; its voxel (a,b,c) reads source (i*E + a - 2, j*E + b - 2, k*E + c - 2), 0 outside [0,X)x[0,Y)x[0,Z).
  * The volume form of the input features: phase, pc (count,P,P,P,3) of patches g0 .. g0 + count - 1, equal bit for bit to
- * PatchGenerator.patchify followed by the plain entry point on those patches.  Same kernel (a by-value geometry selects the path).
+ * PatchGenerator.patchify followed by the plain entry point on those patches.  Its own kernel, input_features_volume_kernel (a by-value geometry).
  * Refused before the device is touched: NULL pointers, P <= 4, non-positive extents / counts, count <= 0, g0 < 0,
  * g0 + count > F*nx*ny*nz. */
 int fdn_input_features_volume(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
@@ -331,7 +331,7 @@ int fdn_input_features_volume(const float* frames, int F, int X, int Y, int Z, i
  * patch side), core voxel (a,b,c) of patch (f,i,j,k) and component m goes to vol[f][m][i*core + a][j*core + b][k*core + c] iff that
  * lies inside (Xo,Yo,Zo): the crop of the far pad.  Patches write disjoint voxels (no atomics; any chunking gives the same volume); a
  * patch wholly inside the cropped region writes nothing.  The values are copied unchanged: de-normalisation stays with the caller.
- * A path of the gather kernel selected by a runtime mode.  Refused before the device is touched: NULL pointers, S <= 2*side,
+ * Kernel: stitch_patches_kernel<false>.  Refused before the device is touched: NULL pointers, S <= 2*side,
  * count <= 0, g0 < 0, g0 + count > F*nx*ny*nz, an output extent <= 0 or > n*core. */
 int fdn_stitch_patches(const float* pred, float* vol, int F, int Xo, int Yo, int Zo, int S, int side, int nx, int ny, int nz,
                        int64_t g0, int count, void* stream);
@@ -341,13 +341,13 @@ int fdn_stitch_patches(const float* pred, float* vol, int F, int Xo, int Yo, int
  * threshold is kept; a threshold of 0 zeroes nothing, round_small_values=False) -- the bits of
  * `v = stitched.astype(float64) * venc; v[abs(v) < velocity_per_px] = 0` on the host.  Geometry, crop rule and refusals are those of
  * fdn_stitch_patches, plus a NULL frame_scale.  side = 0 is legal in both: cores packed by fdn_pack_patch_cores are stitched with S = core.
- * Another runtime mode of the gather kernel. */
+ * Kernel: stitch_patches_kernel<true>, the same element walk. */
 int fdn_stitch_patches_finish(const float* pred, double* vol, const double* frame_scale, int F, int Xo, int Yo, int Zo,
                               int S, int side, int nx, int ny, int nz, int64_t g0, int count, void* stream);
 /* The cores of predicted patches, contiguous: pred (count,S,S,S,3) fp32 -> cores (count,c,c,c,3), c = S - 2*side,
  * cores[n][a][b][k][m] = pred[n][side+a][side+b][side+k][m].  The unit a data-parallel rank sends to the rank that stitches (patch 24
  * at x2: 40^3 of 48^3 voxels, 1.73x less transport); stitching the cores with side = 0 equals stitching pred with `side`, and finishing
- * them (src/predictor.py:103-107) is fdn_stitch_patches_finish on the receiver.  A pure copy, a runtime mode of the gather kernel.
+ * them (src/predictor.py:103-107) is fdn_stitch_patches_finish on the receiver.  A pure copy (pack_patch_cores_kernel).
  * Refused before the device is touched: NULL pointers, side < 0, S <= 2*side, S > 512, count <= 0. */
 int fdn_pack_patch_cores(const float* pred, float* cores, int S, int side, int count, void* stream);
 
@@ -362,7 +362,7 @@ int fdn_pack_patch_cores(const float* pred, float* cores, int S, int side, int c
  * (zero outside the volume), THEN the six values are permuted and the velocities multiplied by their sign -- a padded zero under a
  * negative sign is -0.0 -- and the norms are taken of the permuted components in their new order.  phase, pc equal, bit for bit and sign
  * of zero included, PatchGenerator.patchify -> apply_rotation -> fdn_input_features on those patches.  Orientation (0,0) is
- * fdn_input_features_volume itself.  A path of the same kernel (the by-value geometry carries the orientation).  Refusals: those of
+ * fdn_input_features_volume itself.  The same kernel (the by-value geometry carries the orientation).  Refusals: those of
  * fdn_input_features_volume, and an orientation outside the set. */
 int fdn_input_features_volume_oriented(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
                                        int count, int plane, int k, float* phase, float* pc, void* stream);
@@ -371,7 +371,7 @@ int fdn_input_features_volume_oriented(const float* frames, int F, int X, int Y,
  * element of acc:  t = the element of q above (sign * pred at the rotated index and permuted component);  v = first ? t : acc + t;
  * acc = divisor > 1 ? v / (float)divisor : v.  Plain IEEE fp32 -- one add, and one correctly rounded divide on the call that carries the
  * count of orientations -- so numpy float32 reproduces it bit for bit; with first = 1 acc is not read.  (0,0), first = 1, divisor = 1 is a
- * copy.  The destination is walked (contiguous writes, no atomics); a runtime mode of the gather kernel.  Refused before the device is
+ * copy.  The destination is walked (contiguous writes, no atomics; unrotate_accumulate_kernel).  Refused before the device is
  * touched: NULL pointers, count <= 0, S <= 0 or S > 512, an orientation outside the set, first not 0 or 1, divisor < 1, pred and acc
  * ranges that overlap. */
 int fdn_unrotate_accumulate(const float* pred, float* acc, int count, int S, int plane, int k, int first, int divisor, void* stream);
@@ -382,7 +382,7 @@ int fdn_unrotate_accumulate(const float* pred, float* acc, int count, int S, int
  *
  * fdn_input_features_volume_oriented with the window advancing by `stride`: voxel (a,b,c) of patch (i,j,k) reads source
  * (i*stride + a - 2, j*stride + b - 2, k*stride + c - 2), zero outside the volume.  stride == P - 4 equals the oriented entry point bit
- * for bit (and with (plane,k) = (0,0) the plain one).  A path of the same kernel (the by-value geometry carries the stride).  Refusals:
+ * for bit (and with (plane,k) = (0,0) the plain one).  The same kernel (the by-value geometry carries the stride).  Refusals:
  * those of fdn_input_features_volume_oriented, and stride < 1 or stride > P - 4. */
 int fdn_input_features_volume_strided(const float* frames, int F, int X, int Y, int Z, int P, int nx, int ny, int nz, int64_t g0,
                                       int count, int stride, int plane, int k, float* phase, float* pc, void* stream);
@@ -397,14 +397,14 @@ int fdn_input_features_volume_strided(const float* frames, int F, int X, int Y, 
  * touch: no atomics, no two threads on one voxel, and after all patches of a volume the bits of acc do not depend on how [0, total) was
  * cut into calls, as long as the calls come in ascending g0; numpy float32 reproduces them exactly.  Voxels no patch of the call covers
  * are not written.  side = 0 with S = core blends cores packed by fdn_pack_patch_cores.  stride_hr == core is the disjoint stitch
- * (acc = 0 + p).  A runtime mode of the gather kernel.  Refused before the device is touched: what fdn_stitch_patches refuses (with the
+ * (acc = 0 + p).  Kernel: blend_patches_kernel.  Refused before the device is touched: what fdn_stitch_patches refuses (with the
  * extent limit (n-1)*stride_hr + core per axis: extents the counts do not cover), stride_hr < 1, stride_hr > core, 2*(core - stride_hr) > core. */
 int fdn_blend_patches(const float* pred, float* acc, int F, int Xo, int Yo, int Zo, int S, int side, int stride_hr, int nx, int ny, int nz,
                       int64_t g0, int count, void* stream);
 /* The predictor's post-processing (src/predictor.py:103-107, src/utils/ImageDataset.py:31) on an accumulated volume: acc (F,3,Xo,Yo,Zo) fp32
  * -> vol of the same shape in FLOAT64 with the device table frame_scale (F,2) of doubles {venc_f, threshold_f}: d = (double)acc * venc_f,
- * +0.0 where fabs(d) < threshold_f (strict) -- the rule of fdn_stitch_patches_finish, word for word.  Another runtime mode of the gather
- * kernel.  Refused before the device is touched: NULL pointers, non-positive F or extents. */
+ * +0.0 where fabs(d) < threshold_f (strict) -- the rule of fdn_stitch_patches_finish, word for word.  Kernel:
+ * finish_volume_kernel.  Refused before the device is touched: NULL pointers, non-positive F or extents. */
 int fdn_finish_volume(const float* acc, double* vol, const double* frame_scale, int F, int Xo, int Yo, int Zo, void* stream);
 
 /* Low-res synthesis (prepare_data/fft_downsampling.py:6-137, downsample_phase_img): nvol velocity volumes vel (nvol,X,Y,Z) that share one
@@ -422,7 +422,7 @@ int fdn_finish_volume(const float* acc, double* vol, const double* frame_scale, 
  *      u1 = ((x0 >> 9) + 0.5f) 2^-23, u2 = (x1 >> 8) 2^-24, g = sqrtf(-2 logf(u1)) cospif(2 u2)
  *   5. along X, Y, Z  z[m] = (1/M) sum_k' F[k'] exp(+2 pi i ((k' m) mod M) / M)
  *   6. out_mag = |z| * (2cx*2cy*2cz)/(X*Y*Z),  out_vel = atan2(Im z, Re z) / pi * venc
- * Six launches of the gather kernel (two further runtime modes; the N or M unit roots of a stage sit in dynamic LDS, entry r =
+ * Six launches of kspace_stage_kernel (three forward, three inverse; the N or M unit roots of a stage sit in dynamic LDS, entry r =
  * sincospif(2.f * r / N), the index (k n) mod N formed in integers) with complex fp32 intermediates in `workspace`
  * (fdn_kspace_downsample_workspace_bytes, 16-byte aligned, caller-owned), plus the one-block sums.  No host synchronisation, no memcpy.
  * sigma_out (nvol floats on the device) may be NULL.
@@ -458,7 +458,7 @@ int fdn_adam_step_dev(float* w, const float* g, float* m, float* v, const uint8_
                       const float* lr_t_dev, float b1, float b2, float eps, float l2_grad_scale,
                       const float* l2_scale_dev, float* sumsq_partials, void* stream);
 /* fdn_adam_step for fine-tuning (`layer.trainable = False`, TrainerController.py:223-225 update model.trainable_variables only):
- * frozen holds one byte per parameter like is_kernel.  A path of the same kernel, taken when frozen != NULL, on the grid of
+ * frozen holds one byte per parameter like is_kernel.  An option of the same kernel, taken when frozen != NULL, on the grid of
  * fdn_adam_step (FDN_ADAM_PARTIALS blocks when partials are requested).  lr_t_dev != NULL: the step size is lr_t_dev[0], read on the
  * device as in fdn_adam_step_dev (a captured launch); otherwise the by-value lr_t.
  *   frozen[i] == 0: the arithmetic of fdn_adam_step -- w, m and v come out bit-identical to fdn_adam_step[_dev] on the same operands.
@@ -475,7 +475,7 @@ int fdn_sum_partials(const float* partials, int n, float* out, void* stream);
  * first = 1 is a bit copy (no memset of acc is needed), first = 0 equals numpy's float32 acc + g bit for bit.
  * The sum of the micro-batch gradients of one optimiser step: TrainerController.py:223 (tape.gradient of the (B,)
  * loss vector = gradient of sum_b loss_b), :245-249 (L2 counted once per sample: the batch-size slot adds up too).
- * acc and g may sit at any float offset (gradient-bucket slices).  A path of the Adam kernel selected by a by-value argument.
+ * acc and g may sit at any float offset (gradient-bucket slices).  Kernel: grad_accumulate_kernel.
  * Refused before the device is touched: NULL acc or g, n <= 0, first not in {0, 1}, ranges that overlap (|acc - g| < n floats:
  * an in-place call would double a buffer silently). */
 int fdn_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream);
@@ -491,12 +491,12 @@ int fdn_l2_sumsq_partials(const float* w, const uint8_t* is_kernel, int64_t n, f
  *
  * fdn_grad_sumsq_partials: partials[b] (FDN_ADAM_PARTIALS floats) = block b's sum of g'_i^2 on the blocking of fdn_adam_step with
  * partials (block b takes the elements b * 256 + t + k * FDN_ADAM_PARTIALS * 256); no atomics, a fixed order, blocks beyond the data write 0.
- * Where frozen[i] != 0, g[i] is not read (a NaN there is harmless) and the element adds +0.  Nothing but partials is written.  A path of
- * the Adam kernel.  TrainerController.py:73,223-225.
+ * Where frozen[i] != 0, g[i] is not read (a NaN there is harmless) and the element adds +0.  Nothing but partials is written.  Kernel:
+ * grad_sumsq_partials_kernel.  TrainerController.py:73,223-225.
  * Refused before the device is touched, the message naming the argument: NULL g, w, is_kernel or partials, n <= 0. */
 int fdn_grad_sumsq_partials(const float* g, const float* w, const uint8_t* is_kernel, const uint8_t* frozen /* NULL ok */, int64_t n,
                             float l2_grad_scale, const float* l2_scale_dev /* NULL ok */, float* partials, void* stream);
-/* tf.clip_by_global_norm's factor from those partials, one block, fixed order (a path of the kernel behind fdn_sum_partials):
+/* tf.clip_by_global_norm's factor from those partials, one block, the fixed order of fdn_sum_partials (clip_scale_kernel):
  *     out[0] = N = sqrtf(sum of the n_partials partials) = sqrt(sum g'_i^2),     out[1] = s = clip_norm / max(N, clip_norm).
  * s is exactly 1.0f whenever N <= clip_norm: an inactive clip changes no bit.  TF writes clip_norm * min(1 / N, 1 / clip_norm), which
  * rounds twice where this rounds once; the two agree to rounding.  Non-finite rule: if N is not finite (an inf or NaN gradient, or
@@ -521,7 +521,7 @@ int fdn_adam_step_clipped(float* w, const float* g, float* m, float* v, const ui
                           float* sumsq_partials /* NULL ok */, void* stream);
 /* Weight EMA: what tf.keras.optimizers.Adam(use_ema=True, ema_momentum=mom) keeps beside the weights ([TF]-unpinned: TensorFlow is
  * absent, the recurrence below is the specification).  fdn_adam_step_clipped's operands -- the widest form: frozen, lr_t_dev,
- * l2_scale_dev and g_scale_dev may be NULL, clip_value may be 0 -- and the average ema (n floats), a path of the same kernel.  With
+ * l2_scale_dev and g_scale_dev may be NULL, clip_value may be 0 -- and the average ema (n floats), an option of the same kernel.  With
  * wi the weight the element held before the step and wn the weight the step stores, in fp32:
  *     ema_init == 0:    ema[i] = ema_momentum * ema[i] + (1.f - ema_momentum) * wn   (a_t = mom * a_{t-1} + (1 - mom) * w_t);
  *     ema_init != 0:    ema[i] = ema_momentum * wi + (1.f - ema_momentum) * wn       (the first step with an average: a_0 = w_0, the

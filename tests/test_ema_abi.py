@@ -37,7 +37,7 @@ def test_header_ctypes_table_and_both_libraries_hold_the_entry_point(fdn):
     build = import_module("4dflownet_amd.build")
     for path in (build.build_library(), build.build_library(test_hooks=True)):
         assert hasattr(ctypes.CDLL(path), NAME), path
-    assert fdn._lib.load().fdn_version() == 161 == fdn._lib.FDN_VERSION               # a path of an existing kernel, additive: the version stays
+    assert fdn._lib.load().fdn_version() == 161 == fdn._lib.FDN_VERSION               # an option of an existing kernel, additive: the version stays
 
 
 def test_entry_point_refuses_bad_arguments_before_it_touches_the_device(fdn):

@@ -1,4 +1,4 @@
-"""Low-res synthesis on the device (fdn_kspace_downsample, modes 5 and 6 of the gather kernel) against the float64 pipeline of
+"""Low-res synthesis on the device (fdn_kspace_downsample, kspace_stage_kernel) against the float64 pipeline of
 tests/_kspace_ref.py, which tests/test_kspace_host.py ties to fft_downsampling.downsample_phase_img.
 
 Results are compared in the complex plane -- z = mag_out / ratio * exp(i pi vel_out / venc), E = max|z_dev - z_ref64| / max|z_ref64| --

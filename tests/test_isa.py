@@ -98,10 +98,17 @@ PRODUCT_KERNELS = {
     "conv1x1_fwd_mfma_kernel<T>": "fdn_conv3d_fwd (64+64)->64 k1", "conv1x1_dgrad_mfma_kernel<T>": "fdn_conv1x1_dgrad", "wgrad_1x1_mfma_kernel<T>": "fdn_conv3d_wgrad k1",
     "head_fwd_kernel<T>": "fdn_conv3d_fwd 64->1", "head_dgrad_kernel<T>": "fdn_conv_cout1_dgrad_folded", "head_wgrad_kernel<T>": "fdn_conv3d_wgrad 64->1",
     "conv_cout1_dgrad_kernel": "fdn_conv3d_dgrad 64->1 (padded form)",
-    "bias_grad_kernel<T>": "fdn_bias_grad", "reduce_partials_kernel": "", "sum_partials_kernel": "",
+    "bias_grad_kernel<T>": "fdn_bias_grad", "reduce_partials_kernel": "", "sum_partials_kernel": "fdn_sum_partials", "clip_scale_kernel": "fdn_clip_scale",
     "upsample_fwd_kernel<T, true>": "fdn_upsample_trilinear_fwd (input rows staged through LDS)", "upsample_fwd_kernel<T, false>": "... rows too long for the LDS", "upsample_bwd_kernel<T, 2>": "fdn_upsample_trilinear_bwd (two low-res rows per block)", "upsample_bwd_kernel<T, 1>": "... rows too long for two in the LDS", "input_features_kernel<T>": "fdn_input_features",
-    "loss_main_kernel": "fdn_loss_metrics", "loss_finalize_kernel": "", "mask_sums_kernel": "", "l2_sumsq_kernel": "fdn_l2_sumsq", "l2_sumsq_partials_kernel": "fdn_l2_sumsq_partials", "adam_kernel": "fdn_adam_step",
-    "gather_patches_kernel": "fdn_gather_patches",
+    "input_features_volume_kernel<T>": "fdn_input_features_volume / _oriented / _strided (the window gather from resident frames)",
+    "loss_main_kernel": "fdn_loss_metrics / _div / _act", "loss_finalize_kernel": "", "mask_sums_kernel": "",
+    "volume_metrics_kernel": "fdn_volume_metrics", "volume_finalize_kernel": "", "volume_mask_sums_kernel": "",
+    "l2_sumsq_kernel": "fdn_l2_sumsq", "l2_sumsq_partials_kernel": "fdn_l2_sumsq_partials",
+    "adam_kernel": "fdn_adam_step / _dev / _masked / _clipped / _ema", "grad_accumulate_kernel": "fdn_grad_accumulate", "grad_sumsq_partials_kernel": "fdn_grad_sumsq_partials",
+    "gather_patches_kernel": "fdn_gather_patches", "stitch_patches_kernel<false>": "fdn_stitch_patches", "stitch_patches_kernel<true>": "fdn_stitch_patches_finish",
+    "pack_patch_cores_kernel": "fdn_pack_patch_cores", "unrotate_accumulate_kernel": "fdn_unrotate_accumulate", "blend_patches_kernel": "fdn_blend_patches",
+    "finish_volume_kernel": "fdn_finish_volume",
+    "kspace_stage_kernel<false>": "fdn_kspace_downsample (a forward stage)", "kspace_stage_kernel<true>": "... an inverse stage",
     # conv64_bf16_kernel<MT, MODE, MULTI>, conv64_bf16_fused_kernel<MT, MULTI> (MULTI: fdn_conv64_dgrad_fused_bf16_multi)
     "conv64_bf16_kernel<8, 2, false>": "bf16 mode: fdn_conv64_fwd_bf16", "conv64_bf16_fused_kernel<8, false>": "fdn_conv64_dgrad_fused_bf16 (inner box + shell slabs, one launch)",
     "conv64_bf16_fused_kernel<4, false>": "", "conv64_bf16_kernel<8, 1, false>": "", "conv64_bf16_kernel<8, 0, false>": "",
