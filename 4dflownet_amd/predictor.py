@@ -5,8 +5,10 @@ With torch.distributed initialised (BASELINE cfg5) the patch list is split conti
 runs its share through the same pipelined HIP forward loop and sends exactly its rows to rank 0, which stitches and writes.
 With the device tiler (predict_file(device_tiler=True)) the ranks send only the cores of their predictions, and rank 0
 stitches, de-normalises and zeroes them on the device (_predict_file_device)."""
+import functools
 import os
 import time
+import types
 
 import numpy as np
 import torch
@@ -33,47 +35,86 @@ def save_to_h5(output_filepath, col_name, dataset, compression=None):
     h5io.append_dataset(output_filepath, col_name, dataset, compression=compression)
 
 
-def _stage(network, batch_size, S):
-    """Two pinned float64 staging buffers + a copy stream, kept on the network between calls."""
-    key = (batch_size, S)
-    st = getattr(network, "_predict_stage", None)
-    if st is None or st[0] != key:
-        st = (key, [torch.empty((batch_size, S, S, S, 3), dtype=torch.float64).pin_memory() for _ in range(2)],
-              torch.cuda.Stream(device=network.device))
-        network._predict_stage = st
-    return st[1], st[2]
+class _PredictorState:
+    """What the predictor keeps on a network between calls: ONE copy stream, created on first use, and buffers by name -- pinned host ones
+    and device ones.  A name holds `count` equal tensors; they are re-allocated when a request no longer fits: another shape, or with
+    grow=True (flat storage, handed out as views) more elements than are held."""
+
+    def __init__(self, device):
+        self.device, self.stream, self.pinned_buffers, self.device_buffers = device, None, {}, {}
+
+    def copy_stream(self):
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.device)
+        return self.stream
+
+    def _buffers(self, held, name, shape, count, grow, alloc):
+        shape, n = tuple(shape), int(np.prod(shape))
+        bufs = held.get(name)
+        if bufs is None or (bufs[0].numel() < n if grow else tuple(bufs[0].shape) != shape):
+            bufs = held[name] = [alloc((n,) if grow else shape) for _ in range(count)]
+        return [b[:n].view(shape) for b in bufs] if grow else bufs
+
+    def pinned(self, name, shape, dtype, count=1, grow=False):
+        return self._buffers(self.pinned_buffers, name, shape, count, grow, lambda s: torch.empty(s, dtype=dtype).pin_memory())
+
+    def on_device(self, name, shape, dtype):
+        return self._buffers(self.device_buffers, name, shape, 1, False, lambda s: torch.empty(s, device=self.device, dtype=dtype))[0]
+
+
+def _state(network):
+    st = getattr(network, "_predictor_state", None)
+    if st is None:
+        st = network._predictor_state = _PredictorState(network.device)
+    return st
+
+
+class _CopyOut:
+    """Device results to the host behind the producer of the next one.  push() queues the copy of chunk k into pinned slot k & 1 on the
+    copy stream and then runs the host work of chunk k - 1 -- its copy has long finished, and its slot is not written again before the
+    next push --, so the loop costs the producer's time only; flush() runs the host work that is still owed."""
+
+    def __init__(self, network, stage):
+        self.stage, self.copy_stream = stage, _state(network).copy_stream()
+        self.main = torch.cuda.current_stream(network.device)
+        self.k, self.owed = 0, None                  # owed: (event, host view, on_host, device tensor kept alive)
+
+    def push(self, t, count, on_host):
+        """t: a device tensor whose first dimension is `count` <= the slots'; on_host(view) gets that many rows of the slot, as numpy."""
+        view = self.stage[self.k & 1][:count]
+        self.k += 1
+        self.copy_stream.wait_stream(self.main)
+        with torch.cuda.stream(self.copy_stream):
+            view.copy_(t, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.copy_stream)
+        t.record_stream(self.copy_stream)
+        self.flush()                                 # the previous chunk, while this one is copied and the next one produced
+        self.owed = (ev, view, on_host, t)
+
+    def flush(self):
+        if self.owed is not None:
+            ev, view, on_host, _keep = self.owed
+            self.owed = None
+            ev.synchronize()
+            on_host(view.numpy())
 
 
 def _drain_to_host(network, chunks, res, batch_size):
     """chunks: iterable of (first row, device tensor (cnt,S,S,S,3) fp32 or fp64) in production order.  Converts to float64 on the
-    device, moves every chunk to a pinned staging buffer on a copy stream while the producer of the NEXT chunk runs, and copies it
-    into `res` in that shadow: the loop costs the producer's time only."""
+    device (main stream) and moves every chunk into its rows of `res` through _CopyOut."""
     S = res.shape[1]
-    stage, copy_stream = _stage(network, batch_size, S)
-    main = torch.cuda.current_stream(network.device)
-    inflight = [None, None]                      # per staging slot: (event, first row, row count, device tensor kept alive)
+    pipe = _CopyOut(network, _state(network).pinned("rows", (batch_size, S, S, S, 3), torch.float64, count=2))
 
-    def drain(slot):
-        if inflight[slot] is not None:
-            ev, r0, cnt, _keep = inflight[slot]
-            ev.synchronize()
-            res[r0:r0 + cnt] = stage[slot][:cnt].numpy()
-            inflight[slot] = None
+    def into(r0):
+        def on_host(rows):
+            res[r0:r0 + len(rows)] = rows
+        return on_host
 
-    for k, (r0, out) in enumerate(chunks):
+    for r0, out in chunks:
         out64 = out.double()
-        cnt = out64.shape[0]
-        slot = k & 1
-        drain(slot)                              # the copy issued two chunks ago has long finished; frees the staging slot
-        copy_stream.wait_stream(main)
-        with torch.cuda.stream(copy_stream):
-            stage[slot][:cnt].copy_(out64, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(copy_stream)
-        out64.record_stream(copy_stream)
-        inflight[slot] = (ev, r0, cnt, out64)
-        drain(slot ^ 1)                          # the previous chunk's rows, while this one is produced
-    drain(0); drain(1)
+        pipe.push(out64, out64.shape[0], into(r0))
+    pipe.flush()
     return res
 
 
@@ -102,15 +143,51 @@ def shard_bounds(n, world):
     return [min(r * per, n) for r in range(world + 1)]
 
 
+def _send_rows(network, t):
+    """A rank's shard -- one fp32 device buffer of predictions or packed cores -- to rank 0: one grouped RCCL send of the device buffer,
+    or through pinned host memory under gloo."""
+    import torch.distributed as dist
+    if parallel._host_staged():
+        host, = _state(network).pinned("transport", tuple(t.shape), torch.float32, grow=True)
+        host.copy_(t, non_blocking=True)
+        torch.cuda.current_stream(network.device).synchronize()
+        dist.send(host, dst=0)
+        return
+    for q in dist.batch_isend_irecv([dist.P2POp(dist.isend, t, 0)]):
+        q.wait()
+
+
+def _recv_rows(network, shapes):
+    """Rank 0: the shards of the peers {rank: shape} -- shapes that differ in the number of rows alone -- as ONE fp32 device tensor, rank after
+    rank, ordered on the current stream.  One grouped RCCL launch for all peers; under gloo each shard arrives in pinned host memory and
+    is uploaded."""
+    import torch.distributed as dist
+    dev = torch.device(network.device)
+    ranks = sorted(shapes)
+    rows = torch.empty((sum(shapes[r][0] for r in ranks),) + tuple(shapes[ranks[0]][1:]), device=dev, dtype=torch.float32)
+    parts = dict(zip(ranks, rows.split([shapes[r][0] for r in ranks])))
+    if parallel._host_staged():
+        for r, part in parts.items():
+            host, = _state(network).pinned("transport", shapes[r], torch.float32, grow=True)
+            dist.recv(host, src=r)
+            part.copy_(host, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()          # the one staging buffer is reused for the next peer
+        return rows
+    for q in dist.batch_isend_irecv([dist.P2POp(dist.irecv, part, r) for r, part in parts.items()]):     # one grouped RCCL launch
+        q.wait()                                                  # makes the current stream wait for the transfers; no host sync
+    return rows
+
+
 def predict_patches(network, velocities, magnitudes, batch_size):
     """The batched predict loop of predictor.py:79-94 (results accumulate in float64 like np.zeros + np.append there).
 
     Data-parallel (BASELINE cfg5): the patch list is sharded contiguously over the ranks, every rank runs the same pipelined loop
     on its shard, and rank 0 -- the only rank that stitches and writes -- receives exactly the rows each rank owns (no padding, no
     copy to ranks that do not need it).  Returns the (n,S,S,S,3) float64 array on rank 0 and None on the other ranks.
-      nccl (= RCCL): fp32 predictions travel device-to-device; rank 0 then converts to float64 on the device and drains through the
-      pinned staging buffers.
-      gloo (CPU tests, two ranks on one device): every rank drains its own shard to the host and sends the float64 rows."""
+      On the device the fp32 predictions of every peer travel as one buffer (_send_rows / _recv_rows: device-to-device under nccl = RCCL,
+      through pinned host memory under gloo, two ranks on one device); rank 0 then converts them to float64 on the device and drains
+      them through the pinned staging buffers like its own.
+      CPU stand-in network (tests, gloo): every rank fills float64 host rows and sends those."""
     n = len(velocities[0])
     world, rank = parallel.world_size(), parallel.rank()
     if world == 1:
@@ -120,33 +197,27 @@ def predict_patches(network, velocities, magnitudes, batch_size):
     bounds = shard_bounds(n, world)
     lo, hi = bounds[rank], bounds[rank + 1]
     dev = torch.device(network.device)
-    if dev.type == "cuda" and not parallel._host_staged():
+    if dev.type == "cuda":
         if rank == 0:
-            full = torch.empty((n, S, S, S, 3), device=dev, dtype=torch.float32)
             res = np.empty((n, S, S, S, 3), dtype=np.float64)
             _drain_to_host(network, _forward_chunks(network, velocities, magnitudes, batch_size, lo, hi), res, batch_size)
             # receives are posted AFTER the own shard (a pending RCCL receive is a kernel spinning on a few CUs); the peers finish
             # their equal shards at about the same time, so only the transfer itself (1.3 MB per patch over xGMI) is exposed
-            ops_ = [dist.P2POp(dist.irecv, full[bounds[r]:bounds[r + 1]], r) for r in range(1, world) if bounds[r + 1] > bounds[r]]
-            for q in (dist.batch_isend_irecv(ops_) if ops_ else []):     # one grouped RCCL launch for all peers
-                q.wait()                              # makes the current stream wait for the transfers; no host sync
+            peers = {r: (bounds[r + 1] - bounds[r], S, S, S, 3) for r in range(1, world) if bounds[r + 1] > bounds[r]}
+            rest = _recv_rows(network, peers) if peers else None         # rows [hi, n): an empty shard is not waited for
             step = max(batch_size, 1)
-            _drain_to_host(network, ((s, full[s:min(s + step, n)]) for s in range(hi, n, step)), res, batch_size)
+            _drain_to_host(network, ((s, rest[s - hi:min(s + step, n) - hi]) for s in range(hi, n, step)), res, batch_size)
             return res
         if hi > lo:
             mine = torch.empty((hi - lo, S, S, S, 3), device=dev, dtype=torch.float32)
             for _ in _forward_chunks(network, velocities, magnitudes, batch_size, lo, hi, keep=mine):
                 pass
-            for q in dist.batch_isend_irecv([dist.P2POp(dist.isend, mine, 0)]):
-                q.wait()
+            _send_rows(network, mine)
         return None
-    # host transport
-    if dev.type == "cuda":
-        mine = _predict_pipelined(network, velocities, magnitudes, batch_size, lo, hi)
-    else:                                             # CPU stand-in network (tests): same loop without the staging machinery
-        mine = np.empty((hi - lo, S, S, S, 3), dtype=np.float64)
-        for r0, out in _forward_chunks(network, velocities, magnitudes, batch_size, lo, hi, base=lo):
-            mine[r0:r0 + out.shape[0]] = out.detach().cpu().numpy().astype(np.float64)
+    # CPU stand-in network (tests): the same loop and host rows, without streams or pinned memory
+    mine = np.empty((hi - lo, S, S, S, 3), dtype=np.float64)
+    for r0, out in _forward_chunks(network, velocities, magnitudes, batch_size, lo, hi, base=lo):
+        mine[r0:r0 + out.shape[0]] = out.detach().cpu().numpy().astype(np.float64)
     if rank == 0:
         res = np.empty((n, S, S, S, 3), dtype=np.float64)
         res[lo:hi] = mine
@@ -177,16 +248,6 @@ def _orientations(self_ensemble):
     return None if orientations is None or tuple(orientations) == ((0, 0),) else orientations
 
 
-def _ensemble_acc(network, batch_size, S):
-    """The (batch_size,S,S,S,3) fp32 accumulator of the self-ensemble, kept on the network between calls (the pattern of _stage)."""
-    key = (batch_size, S)
-    st = getattr(network, "_predict_ensemble", None)
-    if st is None or st[0] != key:
-        st = (key, torch.empty((batch_size, S, S, S, 3), device=network.device, dtype=torch.float32))
-        network._predict_ensemble = st
-    return st[1]
-
-
 def _predict_batch(network, frames, patch_size, counts, g0, count, batch_size, orientations, stride=None):
     """The predictions (count,S,S,S,3) fp32 of global patches [g0, g0 + count) of resident frames.  orientations (a tuple of (plane, k),
     or None): for each one in order the features are formed in the rotated frame (ops.input_features_volume(orientation=)), the network
@@ -197,13 +258,27 @@ def _predict_batch(network, frames, patch_size, counts, g0, count, batch_size, o
     if orientations is None:
         phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, count, **window)
         return network.forward_features(phase, pc)
-    acc = _ensemble_acc(network, batch_size, patch_size * network.res_increase)[:count]
+    S = patch_size * network.res_increase
+    acc = _state(network).on_device("ensemble", (batch_size, S, S, S, 3), torch.float32)[:count]     # kept on the network between calls
     last = len(orientations) - 1
     for j, o in enumerate(orientations):
         phase, pc = network.ops.input_features_volume(frames, patch_size, counts, g0, count, orientation=o, **window)
         network.ops.unrotate_accumulate(network.forward_features(phase, pc), acc, o, first=j == 0,
                                         divisor=len(orientations) if j == last else 1)
     return acc
+
+
+def _volume_plan(who, network, frames, patch_size, self_ensemble, blend):
+    """What predict_volume and predict_cores (`who`, for the messages) open with: the options checked -- blend first, before the network or
+    the frames are touched --, the frames on the device and the window plan.  Returns (blend, orientations, frames, pgen, counts, extents)."""
+    blend = check_blend(blend, patch_size, who)
+    orientations = _orientations(self_ensemble)
+    frames = network._to_dev(frames)
+    if frames.dim() != 5 or frames.shape[1] != 6:
+        raise ValueError("%s: frames must be (F,6,X,Y,Z), got %s" % (who, tuple(frames.shape)))
+    pgen = PatchGenerator(patch_size, network.res_increase, blend)
+    counts, _, extents = pgen.plan(tuple(frames.shape[2:]))
+    return blend, orientations, frames, pgen, counts, extents
 
 
 def predict_volume(network, frames, patch_size, batch_size, out=None, frame_scale=None, patch_range=None, self_ensemble=None, blend=0):
@@ -227,15 +302,9 @@ def predict_volume(network, frames, patch_size, batch_size, out=None, frame_scal
     batch_size.  Without frame_scale the accumulator is the result: a fresh zeroed tensor, or `out`, which the caller zeroed and which
     is ADDED to -- this is how patch_range parts, run in ascending order, compose to the whole.  With frame_scale the accumulator is
     internal and the float64 output is finished from it at the end (ops.finish_volume): it holds the patches of patch_range alone."""
-    blend = check_blend(blend, patch_size, "predict_volume")
-    orientations = _orientations(self_ensemble)
-    frames = network._to_dev(frames)
-    if frames.dim() != 5 or frames.shape[1] != 6:
-        raise ValueError("predict_volume: frames must be (F,6,X,Y,Z), got %s" % (tuple(frames.shape),))
+    blend, orientations, frames, pgen, counts, extents = _volume_plan("predict_volume", network, frames, patch_size, self_ensemble, blend)
     R = network.res_increase
     F = frames.shape[0]
-    pgen = PatchGenerator(patch_size, R, blend)
-    counts, _, extents = pgen.plan(tuple(frames.shape[2:]))
     scale = None if frame_scale is None else _frame_scale_tensor(frame_scale, F, frames.device)
     dtype = torch.float32 if scale is None else torch.float64
     if out is None:
@@ -249,14 +318,13 @@ def predict_volume(network, frames, patch_size, batch_size, out=None, frame_scal
         raise ValueError("predict_volume: patch_range (%d, %d) outside [0, %d]" % (lo, hi, total))
     if blend:
         acc = out if scale is None else torch.zeros((F, 3) + extents, device=frames.device, dtype=torch.float32)
-        for g0 in range(lo, hi, batch_size):
-            pred = _predict_batch(network, frames, patch_size, counts, g0, min(batch_size, hi - g0), batch_size, orientations, pgen.stride)
-            network.ops.blend_patches(pred, acc, 2 * R, pgen.stride * R, counts, g0)
-        return out if scale is None else network.ops.finish_volume(acc, scale, out=out)
+        place = lambda pred, g0: network.ops.blend_patches(pred, acc, 2 * R, pgen.stride * R, counts, g0)
+    else:
+        place = lambda pred, g0: network.ops.stitch_patches(pred, out, 2 * R, counts, g0, frame_scale=scale)
     for g0 in range(lo, hi, batch_size):
-        pred = _predict_batch(network, frames, patch_size, counts, g0, min(batch_size, hi - g0), batch_size, orientations)
-        network.ops.stitch_patches(pred, out, 2 * R, counts, g0, frame_scale=scale)
-    return out
+        place(_predict_batch(network, frames, patch_size, counts, g0, min(batch_size, hi - g0), batch_size, orientations,
+                             pgen.stride if blend else None), g0)
+    return network.ops.finish_volume(acc, scale, out=out) if blend and scale is not None else out
 
 
 def shard_frame_span(lo, hi, per_frame):
@@ -275,14 +343,8 @@ def predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=0
     orientations is formed before the cores are packed, so what travels and what the receiver does are the same.
     blend: as in predict_volume -- the patches are those of the overlapping window; the receiver blends the cores (ops.blend_patches with
     side 0 at g0 = lo) instead of stitching them."""
-    blend = check_blend(blend, patch_size, "predict_cores")
-    orientations = _orientations(self_ensemble)
-    frames = network._to_dev(frames)
-    if frames.dim() != 5 or frames.shape[1] != 6:
-        raise ValueError("predict_cores: frames must be (F,6,X,Y,Z), got %s" % (tuple(frames.shape),))
+    blend, orientations, frames, pgen, counts, _ = _volume_plan("predict_cores", network, frames, patch_size, self_ensemble, blend)
     R = network.res_increase
-    pgen = PatchGenerator(patch_size, R, blend)
-    counts, _, _ = pgen.plan(tuple(frames.shape[2:]))
     per_frame = counts[0] * counts[1] * counts[2]
     lo, hi, base = int(lo), int(hi), int(first_frame) * per_frame
     if not base <= lo <= hi <= base + frames.shape[0] * per_frame:
@@ -298,66 +360,124 @@ def predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=0
     return cores
 
 
+def _write_row(output_filepath, dataset, volume, meta, res_increase, round_small_values, finished=False):
+    """One row of the output file from its stitched prediction.  volume: the three (X,Y,Z) components, normalised (fp32 or float64) -- or,
+    finished=True, float64 in a staging buffer, de-normalised and zeroed on the device already: they are copied out and no arithmetic is
+    done.  meta: the row's (venc, velocity_per_px, dx).  Appends u, v, w (+ dx / res_increase) and returns the three (1,X,Y,Z) float64
+    volumes written."""
+    venc, velocity_per_px, dx = meta
+    vols, cols = [], []
+    for i in range(3):
+        if finished:
+            v = volume[i].copy()                                       # the staging buffer is reused
+        else:
+            v = np.asarray(volume[i], dtype=np.float64) * venc         # de-normalise (:103)
+            if round_small_values:
+                v[np.abs(v) < velocity_per_px] = 0                     # (:104-107)
+        v = np.expand_dims(v, axis=0)
+        vols.append(v)
+        cols.append((dataset.velocity_colnames[i], v))
+    if dx is not None:
+        cols.append((dataset.dx_colname, np.expand_dims(dx / res_increase, axis=0)))
+    h5io.append_datasets(output_filepath, cols, compression='gzip')   # u, v, w (+ dx/R): one pass over the file
+    return tuple(vols)
+
+
 DEVICE_TILER_GROUP_BYTES = 1 << 30        # frames + stitched output of one group of rows (predict_file(device_tiler=True))
 
 
-def _volume_stage(network, shape, dtype=torch.float64):
-    """Two pinned buffers for stitched groups + a copy stream, kept on the network between calls (the pattern of _stage); one pair per
-    dtype -- float64 for finished groups, fp32 with FDN_DEVICE_FINISH=0 -- so that switching the finish does not re-pin."""
-    stages = getattr(network, "_predict_vol_stages", None)
-    if stages is None:
-        stages = network._predict_vol_stages = {}
-    st = stages.get(dtype)
-    if st is None or st[0] != tuple(shape):
-        stream = next(iter(stages.values()))[2] if stages else torch.cuda.Stream(device=network.device)
-        st = (tuple(shape), [torch.empty(tuple(shape), dtype=dtype).pin_memory() for _ in range(2)], stream)
-        stages[dtype] = st
-    network._predict_vol_stage = st
-    return st[1], st[2]
+def _plan_groups(job, frames_per_group):
+    """The groups of _predict_file_device, added to its `job`: fpg rows per group (frames_per_group, or what fits
+    DEVICE_TILER_GROUP_BYTES), the window plan of one frame and the side of a packed core."""
+    job.lr_shape = job.dataset.get_volume_shape(job.input_filepath)
+    R, blend, device_finish = job.R, job.blend, job.device_finish
+    if frames_per_group is None:                                       # depends on the file alone: all ranks walk the same groups
+        # the six fp32 inputs, the stitched output (float64 when finished here) and, under blend, the fp32 accumulator beside it
+        per_frame = int(np.prod(job.lr_shape)) * (24 + ((36 if blend else 24) if device_finish else 12) * R ** 3)
+        frames_per_group = max(1, DEVICE_TILER_GROUP_BYTES // per_frame)
+    job.fpg = max(1, min(int(frames_per_group), job.nr_rows))
+    job.pgen = PatchGenerator(job.patch_size, R, blend)
+    job.counts, _, _ = job.pgen.plan(job.lr_shape)
+    job.per_frame_patches = job.counts[0] * job.counts[1] * job.counts[2]
+    job.core = (job.patch_size - 4) * R
 
 
-def _pinned_cores(network, shape):
-    """A pinned fp32 host buffer of `shape` for the host-staged transport of packed cores (gloo), kept on the network and grown on demand."""
-    n = int(np.prod(shape))
-    buf = getattr(network, "_predict_cores_stage", None)
-    if buf is None or buf.numel() < n:
-        buf = torch.empty(n, dtype=torch.float32).pin_memory()
-        network._predict_cores_stage = buf
-    return buf[:n].view(shape)
+def _load_rows(job, rows):
+    """Rows `rows` of the input file: the (len(rows),6,X,Y,Z) fp32 frames predict_volume takes and each row's (venc, velocity_per_px, dx)."""
+    dataset = job.dataset
+    frames = np.empty((len(rows), 6) + job.lr_shape, dtype=np.float32)
+    meta = []
+    for f, nrow in enumerate(rows):
+        dataset.load_vectorfield(job.input_filepath, nrow)
+        for c, a in enumerate((dataset.u, dataset.v, dataset.w, dataset.mag_u, dataset.mag_v, dataset.mag_w)):
+            frames[f, c] = a
+        meta.append((dataset.venc, dataset.velocity_per_px, dataset.dx))
+    return frames, meta
 
 
-def _send_cores(network, cores):
-    """A rank's packed cores to rank 0: one grouped RCCL send of the device buffer, or through pinned host memory under gloo."""
-    import torch.distributed as dist
-    if parallel._host_staged():
-        host = _pinned_cores(network, tuple(cores.shape))
-        host.copy_(cores, non_blocking=True)
-        torch.cuda.current_stream(network.device).synchronize()
-        dist.send(host, dst=0)
-        return
-    for q in dist.batch_isend_irecv([dist.P2POp(dist.isend, cores, 0)]):
-        q.wait()
+def _device_peer_loop(network, job):
+    """Rank r > 0 of _predict_file_device: per group the rows its shard touches, predict_cores, one buffer of cores to rank 0."""
+    world, rank = parallel.world_size(), parallel.rank()
+    for r0 in range(0, job.nr_rows, job.fpg):
+        nrows = min(job.fpg, job.nr_rows - r0)
+        bounds = shard_bounds(nrows * job.per_frame_patches, world)
+        lo, hi = bounds[rank], bounds[rank + 1]
+        if hi > lo:                                                    # an empty shard neither sends nor is waited for
+            f0, f1 = shard_frame_span(lo, hi, job.per_frame_patches)
+            frames, _ = _load_rows(job, list(range(r0 + f0, r0 + f1)))
+            _send_rows(network, predict_cores(network, frames, job.patch_size, job.batch_size, lo, hi, first_frame=f0,
+                                              self_ensemble=job.orientations, blend=job.blend))
 
 
-def _recv_cores(network, shapes):
-    """Rank 0: the packed cores of the peers {rank: shape} as device tensors {rank: tensor}, ordered on the current stream.  One grouped
-    RCCL launch for all peers; under gloo each buffer arrives in pinned host memory and is uploaded."""
-    import torch.distributed as dist
-    dev = torch.device(network.device)
-    got = {}
-    if parallel._host_staged():
-        for r, shape in shapes.items():
-            host = _pinned_cores(network, shape)
-            dist.recv(host, src=r)
-            got[r] = host.to(dev, non_blocking=True)
-            torch.cuda.current_stream(dev).synchronize()          # the one staging buffer is reused for the next peer
-        return got
-    for r, shape in shapes.items():
-        got[r] = torch.empty(shape, device=dev, dtype=torch.float32)
-    ops_ = [dist.P2POp(dist.irecv, t, r) for r, t in got.items()]
-    for q in (dist.batch_isend_irecv(ops_) if ops_ else []):
-        q.wait()                                                  # makes the current stream wait for the transfers; no host sync
-    return got
+def _write_group(job, rows, meta, t0, written, host):
+    """The host work of one group that has arrived in pinned memory (host: (len(rows),3,X*R,Y*R,Z*R)): its rows to the file and to `written`."""
+    if job.verbose:
+        print("Processed rows %d-%d/%d: %d patches%s in %.2f secs." % (
+            rows[0] + 1, rows[-1] + 1, job.nr_rows, len(rows) * job.per_frame_patches,
+            "" if job.orientations is None else " x %d orientations" % len(job.orientations), time.time() - t0))
+    for f, m in enumerate(meta):
+        written.append(_write_row(job.output_filepath, job.dataset, host[f], m, job.R, job.round_small_values, finished=job.device_finish))
+
+
+def _device_root_loop(network, job):
+    """Rank 0 of _predict_file_device: per group its own shard through predict_volume, the peers' cores placed behind it, on_group, and the
+    copy-out whose host work (_write_group) runs behind the next group's compute.  Returns the volumes written."""
+    world, R, blend, counts = parallel.world_size(), job.R, job.blend, job.counts
+    written, pipe = [], None
+    if job.output_filepath is not None:
+        # one pair of pinned buffers per dtype -- float64 for finished groups, fp32 with FDN_DEVICE_FINISH=0 --: switching does not re-pin
+        dtype = torch.float64 if job.device_finish else torch.float32
+        out_shape = (job.fpg, 3) + tuple(n * R for n in job.lr_shape)
+        pipe = _CopyOut(network, _state(network).pinned(("groups", dtype), out_shape, dtype, count=2))
+    for r0 in range(0, job.nr_rows, job.fpg):
+        rows = list(range(r0, min(r0 + job.fpg, job.nr_rows)))
+        frames, meta = _load_rows(job, rows)
+        t0 = time.time()
+        scale = None
+        if job.device_finish:                                          # the doubles the host finish multiplies and compares with
+            scale = _frame_scale_tensor([(venc, vpp if job.round_small_values else 0.0) for venc, vpp, _ in meta], len(rows), network.device)
+        bounds = shard_bounds(len(rows) * job.per_frame_patches, world)
+        vol = predict_volume(network, frames, job.patch_size, job.batch_size, frame_scale=None if blend else scale,
+                             patch_range=(bounds[0], bounds[1]), self_ensemble=job.orientations, blend=blend)
+        peers = {r: (bounds[r + 1] - bounds[r], job.core, job.core, job.core, 3) for r in range(1, world) if bounds[r + 1] > bounds[r]}
+        if peers:                                                      # posted after the own shard (see predict_patches)
+            got = _recv_rows(network, peers)                           # patches [bounds[1], ...), rank after rank
+            for r in sorted(peers):
+                cores = got[bounds[r] - bounds[1]:bounds[r + 1] - bounds[1]]
+                if blend:
+                    network.ops.blend_patches(cores, vol, 0, job.pgen.stride * R, counts, bounds[r])
+                else:
+                    network.ops.stitch_patches(cores, vol, 0, counts, bounds[r], frame_scale=scale)
+        if blend and scale is not None:                                # the accumulator is complete: de-normalise and zero (:103-107)
+            vol = network.ops.finish_volume(vol, scale)
+        if job.on_group is not None:
+            job.on_group(rows, vol)
+        if pipe is not None:
+            pipe.push(vol, len(rows), functools.partial(_write_group, job, rows, meta, t0, written))
+    if pipe is not None:
+        pipe.flush()
+    return written
+
 
 
 def _predict_file_device(network, input_filepath, output_filepath, patch_size, res_increase, batch_size, round_small_values, verbose,
@@ -378,116 +498,20 @@ def _predict_file_device(network, input_filepath, output_filepath, patch_size, r
     and finishes the accumulator into the float64 group (ops.finish_volume); the byte budget counts the accumulator."""
     blend = check_blend(blend, patch_size, "predict_file")
     orientations = _orientations(self_ensemble)
-    world, rank = parallel.world_size(), parallel.rank()
     if device_finish is None:
         device_finish = os.environ.get("FDN_DEVICE_FINISH", "1") not in ("", "0")
     dataset = ImageDataset()
     nr_rows = dataset.get_dataset_len(input_filepath)
-    written = []
     if nr_rows == 0:
-        return written
-    lr_shape = dataset.get_volume_shape(input_filepath)
-    R = res_increase
-    if frames_per_group is None:                                       # depends on the file alone: all ranks walk the same groups
-        # the six fp32 inputs, the stitched output (float64 when finished here) and, under blend, the fp32 accumulator beside it
-        per_frame = int(np.prod(lr_shape)) * (24 + ((36 if blend else 24) if device_finish else 12) * R ** 3)
-        frames_per_group = max(1, DEVICE_TILER_GROUP_BYTES // per_frame)
-    fpg = max(1, min(int(frames_per_group), nr_rows))
-    pgen = PatchGenerator(patch_size, R, blend)
-    counts, _, _ = pgen.plan(lr_shape)
-    per_frame_patches = counts[0] * counts[1] * counts[2]
-    core = (patch_size - 4) * R
-
-    def load(rows):
-        frames = np.empty((len(rows), 6) + lr_shape, dtype=np.float32)
-        meta = []
-        for f, nrow in enumerate(rows):
-            dataset.load_vectorfield(input_filepath, nrow)
-            for c, a in enumerate((dataset.u, dataset.v, dataset.w, dataset.mag_u, dataset.mag_v, dataset.mag_w)):
-                frames[f, c] = a
-            meta.append((dataset.venc, dataset.velocity_per_px, dataset.dx))
-        return frames, meta
-
-    if rank > 0:
-        for r0 in range(0, nr_rows, fpg):
-            nrows = min(fpg, nr_rows - r0)
-            bounds = shard_bounds(nrows * per_frame_patches, world)
-            lo, hi = bounds[rank], bounds[rank + 1]
-            if hi > lo:                                                # an empty shard neither sends nor is waited for
-                f0, f1 = shard_frame_span(lo, hi, per_frame_patches)
-                frames, _ = load(list(range(r0 + f0, r0 + f1)))
-                _send_cores(network, predict_cores(network, frames, patch_size, batch_size, lo, hi, first_frame=f0,
-                                                   self_ensemble=orientations, blend=blend))
-        return written
-
-    write = output_filepath is not None
-    if write:
-        out_shape = (fpg, 3) + tuple(n * R for n in lr_shape)
-        stage, copy_stream = _volume_stage(network, out_shape, torch.float64 if device_finish else torch.float32)
-        main = torch.cuda.current_stream(network.device)
-
-    def finish(job):
-        ev, slot, rows, meta, t0, _keep = job
-        ev.synchronize()
-        host = stage[slot].numpy()
-        if verbose:
-            print("Processed rows %d-%d/%d: %d patches%s in %.2f secs." % (
-                rows[0] + 1, rows[-1] + 1, nr_rows, len(rows) * per_frame_patches,
-                "" if orientations is None else " x %d orientations" % len(orientations), time.time() - t0))
-        for f, (venc, vpp, dx) in enumerate(meta):
-            vols, cols = [], []
-            for i in range(3):
-                if device_finish:
-                    v = host[f, i].copy()                              # finished on the device; the staging buffer is reused
-                else:
-                    v = host[f, i].astype(np.float64) * venc           # de-normalise (:103)
-                    if round_small_values:
-                        v[np.abs(v) < vpp] = 0                         # (:104-107)
-                v = np.expand_dims(v, axis=0)
-                vols.append(v)
-                cols.append((dataset.velocity_colnames[i], v))
-            if dx is not None:
-                cols.append((dataset.dx_colname, np.expand_dims(dx / res_increase, axis=0)))
-            h5io.append_datasets(output_filepath, cols, compression='gzip')
-            written.append(tuple(vols))
-
-    pending = None
-    for k, r0 in enumerate(range(0, nr_rows, fpg)):
-        rows = list(range(r0, min(r0 + fpg, nr_rows)))
-        frames, meta = load(rows)
-        t0 = time.time()
-        scale = None
-        if device_finish:                                              # the doubles the host finish multiplies and compares with
-            scale = _frame_scale_tensor([(venc, vpp if round_small_values else 0.0) for venc, vpp, _ in meta], len(rows), network.device)
-        bounds = shard_bounds(len(rows) * per_frame_patches, world)
-        vol = predict_volume(network, frames, patch_size, batch_size, frame_scale=None if blend else scale,
-                             patch_range=(bounds[0], bounds[1]), self_ensemble=orientations, blend=blend)
-        peers = {r: (bounds[r + 1] - bounds[r], core, core, core, 3) for r in range(1, world) if bounds[r + 1] > bounds[r]}
-        if peers:                                                      # posted after the own shard (see predict_patches)
-            for r, cores in sorted(_recv_cores(network, peers).items()):
-                if blend:
-                    network.ops.blend_patches(cores, vol, 0, pgen.stride * R, counts, bounds[r])
-                else:
-                    network.ops.stitch_patches(cores, vol, 0, counts, bounds[r], frame_scale=scale)
-        if blend and scale is not None:                                # the accumulator is complete: de-normalise and zero (:103-107)
-            vol = network.ops.finish_volume(vol, scale)
-        if on_group is not None:
-            on_group(rows, vol)
-        if not write:
-            continue
-        slot = k & 1                                                   # its previous user (group k - 2) was finished one turn ago
-        copy_stream.wait_stream(main)
-        with torch.cuda.stream(copy_stream):
-            stage[slot][:len(rows)].copy_(vol, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(copy_stream)
-        vol.record_stream(copy_stream)
-        if pending is not None:
-            finish(pending)                                            # host work of group k - 1 behind the compute of group k
-        pending = (ev, slot, rows, meta, t0, vol)
-    if pending is not None:
-        finish(pending)
-    return written
+        return []
+    job = types.SimpleNamespace(dataset=dataset, nr_rows=nr_rows, input_filepath=input_filepath, output_filepath=output_filepath,
+                                patch_size=patch_size, R=res_increase, batch_size=batch_size, round_small_values=round_small_values,
+                                verbose=verbose, on_group=on_group, device_finish=device_finish, orientations=orientations, blend=blend)
+    _plan_groups(job, frames_per_group)
+    if parallel.rank() > 0:
+        _device_peer_loop(network, job)
+        return []
+    return _device_root_loop(network, job)
 
 
 def predict_file(network, input_filepath, output_filepath, patch_size, res_increase, batch_size=8,
@@ -524,19 +548,9 @@ def predict_file(network, input_filepath, output_filepath, patch_size, res_incre
             continue                              # rank 0 holds the gathered patches: it alone stitches and writes
         if verbose:
             print("Processed row %d/%d: %d patches in %.2f secs." % (nrow + 1, nr_rows, len(results), time.time() - t0))
-        vols, cols = [], []
-        for i in range(3):
-            v = pgen._patchup_with_overlap(results[:, :, :, :, i], pgen.nr_x, pgen.nr_y, pgen.nr_z)
-            v = v * dataset.venc                                   # de-normalise (:103)
-            if round_small_values:
-                v[np.abs(v) < dataset.velocity_per_px] = 0        # (:104-107)
-            v = np.expand_dims(v, axis=0)
-            vols.append(v)
-            cols.append((dataset.velocity_colnames[i], v))
-        if dataset.dx is not None:
-            cols.append((dataset.dx_colname, np.expand_dims(dataset.dx / res_increase, axis=0)))
-        h5io.append_datasets(output_filepath, cols, compression='gzip')     # u, v, w (+ dx/R): one pass over the file
-        written.append(tuple(vols))
+        stitched = [pgen._patchup_with_overlap(results[:, :, :, :, i], pgen.nr_x, pgen.nr_y, pgen.nr_z) for i in range(3)]
+        written.append(_write_row(output_filepath, dataset, stitched, (dataset.venc, dataset.velocity_per_px, dataset.dx), res_increase,
+                                  round_small_values))
     return written
 
 
@@ -656,18 +670,25 @@ def evaluate_file(network, input_filepath, hr_filepath, patch_size, res_increase
     return (metrics, sums) if return_sums else metrics
 
 
+def _start(who, blend, patch_size, res_increase, low_resblock, hi_resblock, dtype, output_activation, model_path, output_dir):
+    """What main and evaluate_main (`who`) open with: blend checked before anything else, the process group from the environment, the
+    network with its weights, and the output directory (made by rank 0).  Returns the network."""
+    check_blend(blend, patch_size, who)
+    parallel.init_from_env()
+    network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype, output_activation=output_activation)
+    network.load_weights(model_path)
+    if not os.path.isdir(output_dir) and parallel.rank() == 0:
+        os.makedirs(output_dir)
+    return network
+
+
 def main(data_dir='../data', filename='example_data.h5', output_dir="../result", output_filename='example_result.h5',
          model_path="../models/4DFlowNet/4DFlowNet.h5", patch_size=24, res_increase=2, batch_size=8,
          round_small_values=True, low_resblock=8, hi_resblock=4, dtype="float32", device_tiler=False, frames_per_group=None,
          self_ensemble=None, blend=0, output_activation=None):
     """Same hard-coded surface as predictor.py:31-47 (+ dtype, + the device tiler switch, self_ensemble and blend of predict_file,
     + output_activation of prepare_network)."""
-    check_blend(blend, patch_size, "main")
-    parallel.init_from_env()
-    network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype, output_activation=output_activation)
-    network.load_weights(model_path)
-    if not os.path.isdir(output_dir) and parallel.rank() == 0:
-        os.makedirs(output_dir)
+    network = _start("main", blend, patch_size, res_increase, low_resblock, hi_resblock, dtype, output_activation, model_path, output_dir)
     predict_file(network, '{}/{}'.format(data_dir, filename), '{}/{}'.format(output_dir, output_filename), patch_size,
                  res_increase, batch_size, round_small_values, device_tiler=device_tiler, frames_per_group=frames_per_group,
                  self_ensemble=self_ensemble, blend=blend)
@@ -681,12 +702,8 @@ def evaluate_main(data_dir='../data', filename='example_data.h5', hr_filename='e
                   frames_per_group=None, self_ensemble=None, blend=0, output_activation=None):
     """The surface of main() for scoring a checkpoint: + hr_filename, the ground truth beside `filename`, and csv_filename; the
     prediction itself is written only with output_filename."""
-    check_blend(blend, patch_size, "evaluate_main")
-    parallel.init_from_env()
-    network = prepare_network(patch_size, res_increase, low_resblock, hi_resblock, dtype=dtype, output_activation=output_activation)
-    network.load_weights(model_path)
-    if not os.path.isdir(output_dir) and parallel.rank() == 0:
-        os.makedirs(output_dir)
+    network = _start("evaluate_main", blend, patch_size, res_increase, low_resblock, hi_resblock, dtype, output_activation, model_path,
+                     output_dir)
     evaluate_file(network, '{}/{}'.format(data_dir, filename), '{}/{}'.format(data_dir, hr_filename), patch_size, res_increase, batch_size,
                   round_small_values, output_filepath=None if output_filename is None else '{}/{}'.format(output_dir, output_filename),
                   csv_path='{}/{}'.format(output_dir, csv_filename) if parallel.rank() == 0 else None, frames_per_group=frames_per_group,

@@ -194,7 +194,7 @@ def test_predict_file_with_the_device_tiler_equals_the_host_path_on_the_same_bat
         got3 = predictor.predict_file(net, src, str(tmp_path / "env.h5"), P, R, batch_size=B, verbose=False, frames_per_group=1)
     finally:
         del os.environ["FDN_DEVICE_TILER"]
-    assert getattr(net, "_predict_vol_stage")[0] == (1, 3, 24, 40, 10)          # the device path ran
+    assert tuple(net._predictor_state.pinned_buffers["groups", torch.float64][0].shape) == (1, 3, 24, 40, 10)   # the device path ran
     _same_volumes(got3, host)
     a, b = h5io.read_all(str(tmp_path / "env.h5")), h5io.read_all(str(tmp_path / "host.h5"))
     assert sorted(a) == sorted(b) and all(a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes() for k in a)

@@ -242,8 +242,9 @@ def test_predict_volume_equals_the_composed_path_on_the_same_batches(which):
     assert vol.dtype == torch.float32 and tuple(vol.shape) == want.shape == (F, 3, 18, 12, 10)
     assert se.same_bits(vol.cpu().numpy(), want)
     assert np.abs(want).max() > 0 and not np.isnan(want).any()
-    assert tuple(net._predict_ensemble[1].shape) == (BATCH, 16, 16, 16, 3)          # one accumulator, kept on the network
-    kept = net._predict_ensemble[1].data_ptr()
+    held = net._predictor_state.device_buffers
+    assert tuple(held["ensemble"][0].shape) == (BATCH, 16, 16, 16, 3)               # one accumulator, kept on the network
+    kept = held["ensemble"][0].data_ptr()
     # finished: thresholds at the medians of the de-normalised frames zero about half of the voxels
     vencs = (1.5, 0.75)
     scale = [(v, float(np.median(np.abs(want[f].astype(np.float64) * v)))) for f, v in enumerate(vencs)]
@@ -252,7 +253,7 @@ def test_predict_volume_equals_the_composed_path_on_the_same_batches(which):
     assert 0.3 < zeroed < 0.7, zeroed
     fin = predictor.predict_volume(net, frames, P_NET, BATCH, frame_scale=scale, self_ensemble=option)
     assert fin.dtype == torch.float64 and se.same_bits(fin.cpu().numpy(), fin_want)
-    assert net._predict_ensemble[1].data_ptr() == kept
+    assert held["ensemble"][0].data_ptr() == kept
     if which == "subset":                                                           # the ensemble is not the plain prediction
         plain = predictor.predict_volume(net, frames, P_NET, BATCH)
         assert not se.same_bits(plain.cpu().numpy(), want)
@@ -261,13 +262,12 @@ def test_predict_volume_equals_the_composed_path_on_the_same_batches(which):
 def test_identity_alone_and_off_take_the_plain_path():
     frames = _frames()
     net = _net()
-    if hasattr(net, "_predict_ensemble"):
-        del net._predict_ensemble
+    predictor._state(net).device_buffers.pop("ensemble", None)
     plain = predictor.predict_volume(net, frames, P_NET, BATCH).cpu().numpy()
     for option in (None, False, [(0, 0)], ((0, 0),)):
         got = predictor.predict_volume(net, frames, P_NET, BATCH, self_ensemble=option)
         assert se.same_bits(got.cpu().numpy(), plain), option
-    assert not hasattr(net, "_predict_ensemble")                                    # no accumulator: the plain loop ran
+    assert "ensemble" not in predictor._state(net).device_buffers                   # no accumulator: the plain loop ran
     _, want, _ = _reference(frames, [(0, 0)])                                       # and the composed path with one orientation agrees
     assert se.same_bits(plain, want)
     with pytest.raises(ValueError, match="self_ensemble"):
