@@ -472,6 +472,8 @@ __device__ __forceinline__ void conv64_wino2d_body(const Wino2Args& p, const int
         if constexpr (SPLIT) {
             // one step = (kd, xw): 32 cin x 6 terms x 2 M-blocks = 12 MFMAs of 16 cycles, fed by 3 weight pieces (16 B per lane each, L1/L2;
             // requested a step ahead into the other half of US) and 3 x 2 cell pieces (ds_read_b128; each re-requested right behind its last use)
+            // (This body is the test build's A/B twin only.  It adds all six terms to ONE accumulator, which the bf16 pipe answers with a bias
+            // of -5e-9 sum|x||w|; the product kernel, conv64_wino2d_pc_kernel.h, sums the five small terms on their own.)
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc) ldv(pc, 0);
 #pragma unroll 1

@@ -114,7 +114,7 @@ int fdn_pack_conv64_weights_batch(const float* w_base, const int64_t* w_offsets,
  * fdn_pack_conv64_weights_batch_streams is fdn_pack_conv64_weights_batch restricted to the named streams of the forward
  * and of the dgrad packs (the others keep whatever they held: a caller that narrows the set must re-pack before a
  * grid that needs more).  cfg2 reads F(4,3)xF(4,3) forward and F(4,3)xF(4,3) + 1-D Winograd (shell faces) in dgrad: 270 of
- * the 522 x 4096 floats per layer.  The per-step re-pack after the optimizer, TrainerController.py:225. */
+ * the 846 x 4096 floats per layer.  The per-step re-pack after the optimizer, TrainerController.py:225. */
 #define FDN_PACK_STREAM_DIRECT 1
 #define FDN_PACK_STREAM_WINO_W 2
 #define FDN_PACK_STREAM_WINO_H2 4
