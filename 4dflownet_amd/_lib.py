@@ -46,6 +46,7 @@ SIGNATURES = {
     "fdn_loss_metrics": (c_i, [c_fp] * 8 + [c_i, c_i64, c_fp]),
     "fdn_loss_metrics_div": (c_i, [c_fp] * 5 + [c_f] + [c_fp] * 3 + [c_i] * 4 + [c_fp]),
     "fdn_loss_metrics_act": (c_i, [c_fp] * 5 + [c_f, c_f, c_i] + [c_fp] * 3 + [c_i] * 4 + [c_fp]),
+    "fdn_loss_metrics_kind": (c_i, [c_fp] * 5 + [c_i, c_f, c_f, c_f, c_i] + [c_fp] * 3 + [c_i] * 4 + [c_fp]),
     "fdn_volume_metrics": (c_i, [c_fp, c_i, c_fp, c_fp, c_i, c_fp, c_fp] + [c_i] * 4 + [c_fp]),
     "fdn_gather_patches": (c_i, [c_fp, c_fp, c_i, c_i, c_fp]),
     "fdn_input_features_volume": (c_i, [c_fp] + [c_i] * 8 + [c_i64, c_i, c_fp, c_fp, c_fp]),

@@ -570,22 +570,49 @@ __device__ __forceinline__ void tanh_grad_store(const float* yb, int64_t i, floa
     d[2] = gw * fmaf(-yw, yw, 1.f);
 }
 
-// div_w == 0: the masked MSE alone, exactly the arithmetic and block -> voxel mapping of the plain loss.  div_w > 0 (fdn_loss_metrics_div):
+// The penalty rho of the data term and its derivative psi, per component of the residual d (fdn_loss_metrics_kind).  KIND is a
+// compile-time parameter of loss_body: FDN_LOSS_MSE is the arithmetic the loss always had (rho = d^2 summed as one fma chain, psi's 2 in
+// the voxel weight), the others sum theirs in pen_sum.  kp: delta (Huber) or epsilon (Charbonnier), kp2 = kp * kp.
+// IEEE sqrtf and division (hipcc's default for fp32): correctly rounded, which the tests' rounding count relies on.  psi(0) is exactly 0
+// for every kind (MAE: tf.abs' gradient; Huber: 0 lies in the inner branch; Charbonnier: 0 / eps, and 0 where eps^2 underflowed to 0).
+template <int KIND>
+__device__ __forceinline__ float pen_psi(float d, float kp, float kp2) {
+    if (KIND == FDN_LOSS_MAE) return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    if (KIND == FDN_LOSS_HUBER) return fabsf(d) <= kp ? d : copysignf(kp, d);
+    if (KIND == FDN_LOSS_CHARBONNIER) { const float s = sqrtf(fmaf(d, d, kp2)); return s > 0.f ? d / s : 0.f; }
+    return d;                                                       // MSE: the factor 2 rides on the voxel weight
+}
+template <int KIND>
+__device__ __forceinline__ float pen_sum(float du, float dv, float dw, float mse, float kp, float kp2) {
+    if (KIND == FDN_LOSS_MAE) return fabsf(du) + fabsf(dv) + fabsf(dw);
+    if (KIND == FDN_LOSS_HUBER) {
+        // with t = clamp(d, -delta, delta): rho = t (d - t / 2), d^2 / 2 inside and delta (|d| - delta / 2) outside without a branch; summed
+        // as the MSE's fma chain, so where every |d| <= delta the sum is the MSE's scaled by a power of two: half of it, bit for bit.
+        // (psi is the same t; taking it from here instead of pen_psi's select costs the shared kernel a spill)
+        const float tu = fminf(fmaxf(du, -kp), kp), tv = fminf(fmaxf(dv, -kp), kp), tw = fminf(fmaxf(dw, -kp), kp);
+        return fmaf(tw, fmaf(-0.5f, tw, dw), fmaf(tv, fmaf(-0.5f, tv, dv), tu * fmaf(-0.5f, tu, du)));
+    }
+    if (KIND == FDN_LOSS_CHARBONNIER) return sqrtf(fmaf(du, du, kp2)) + sqrtf(fmaf(dv, dv, kp2)) + sqrtf(fmaf(dw, dw, kp2));
+    return mse;
+}
+
+// div_w == 0: the masked data term alone, exactly the arithmetic and block -> voxel mapping of the plain loss.  div_w > 0 (fdn_loss_metrics_div):
 // the same pass also gathers each channel's stencil neighbours (e at +-1, +-2 and m at +-1 along its axis; L1 / L2 hits), adds the
 // divergence part of dpred and writes two more per-block partials (sum m d, sum nf d; the weight is applied in loss_finalize_kernel).
 // nparts: partials per block, 3 (plain) or 5.  (The branch's gathers in flight take the kernel from 26 to 68 VGPRs: seven waves per
 // SIMD instead of eight; capping it at 64 spills.)  nf_w (fdn_loss_metrics_act): the non-fluid region's weight, folded into inv_nf, so it
-// reaches the region's part of dpred -- MSE and divergence -- through the existing arithmetic; the sums stay unweighted and
-// loss_finalize_kernel applies it.
-__global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict__ pred, const float* __restrict__ uh,
-                                                         const float* __restrict__ vh, const float* __restrict__ wh,
-                                                         const float* __restrict__ mask, float* __restrict__ scratch,
-                                                         float* __restrict__ dpred, int64_t V, int D, int H, int W, float div_w,
-                                                         int nparts, float nf_w, int out_act) {
-    __shared__ float red[4];
+// reaches the region's part of dpred -- data term and divergence -- through the existing arithmetic; the sums stay unweighted and
+// loss_finalize_kernel applies it.  The divergence term is squared for every KIND: it works on the raw residuals.
+template <int KIND>
+__device__ __forceinline__ void loss_body(const float* __restrict__ pred, const float* __restrict__ uh, const float* __restrict__ vh,
+                                          const float* __restrict__ wh, const float* __restrict__ mask, float* __restrict__ scratch,
+                                          float* __restrict__ dpred, int64_t V, int D, int H, int W, float div_w, int nparts, float nf_w,
+                                          int out_act, float kp, float* red) {
+    constexpr bool MSE = KIND == FDN_LOSS_MSE;
     const int n = blockIdx.y;
     const float inv_f = 1.f / (scratch[n * 8 + 0] + 1.f);
     const float inv_nf = nf_w * (1.f / (scratch[n * 8 + 1] + 1.f));     // non_fluid_weight rides on the region's scalar: exact at 1
+    const float kp2 = kp * kp;
     if (div_w != 0.f) {
         const float two_w = 2.f * div_w;
         const int64_t HW = (int64_t)H * W;
@@ -597,8 +624,9 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
             const float m = mask[g];
             const float nf = m < 0.5f ? 1.f : 0.f;
             const float mse = du * du + dv * dv + dw * dw;
-            sf += mse * m;
-            snf += mse * nf;
+            const float e = pen_sum<KIND>(du, dv, dw, mse, kp, kp2);
+            sf += e * m;
+            snf += e * nf;
             const float diff = sqrtf(mse);
             const float actual = sqrtf(tu * tu + tv * tv + tw * tw);
             float rel = diff / (actual + 1e-5f);
@@ -610,8 +638,8 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
             const unsigned q = iv / (unsigned)W;
             const int pw = (int)(iv - q * (unsigned)W), ph = (int)(q % (unsigned)H), pd = (int)(q / (unsigned)H);
             const float c0 = m * inv_f + nf * inv_nf;
-            const float wgt = 2.f * c0;
-            float gu = du * wgt, gv = dv * wgt, gw = dw * wgt;
+            const float wgt = MSE ? 2.f * c0 : c0;
+            float gu = pen_psi<KIND>(du, kp, kp2) * wgt, gv = pen_psi<KIND>(dv, kp, kp2) * wgt, gw = pen_psi<KIND>(dw, kp, kp2) * wgt;
             const float au = div_axis(pred, uh, mask, g, 0, pd, D, HW, du, c0, inv_f, inv_nf, two_w, &gu);
             const float av = div_axis(pred, vh, mask, g, 1, ph, H, W, dv, c0, inv_f, inv_nf, two_w, &gv);
             const float aw = div_axis(pred, wh, mask, g, 2, pw, W, 1, dw, c0, inv_f, inv_nf, two_w, &gw);
@@ -642,8 +670,9 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
         const float m = mask[g];
         const float nf = m < 0.5f ? 1.f : 0.f;
         const float mse = du * du + dv * dv + dw * dw;
-        sf += mse * m;
-        snf += mse * nf;
+        const float e = pen_sum<KIND>(du, dv, dw, mse, kp, kp2);
+        sf += e * m;
+        snf += e * nf;
         // relative error (loss_utils.py:64-103); rintf == round-half-to-even == tf.round
         const float diff = sqrtf(mse);
         const float actual = sqrtf(tu * tu + tv * tv + tw * tw);
@@ -653,9 +682,11 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
         corr = rintf(corr * 1e4f) / 1e4f;
         if (m == 1.0f) srel += corr;
         if (dpred) {
-            const float wgt = 2.f * (m * inv_f + nf * inv_nf);
-            if (out_act == FDN_ACT_TANH) tanh_grad_store(pred, g * 3, dpred + g * 3, du * wgt, dv * wgt, dw * wgt);
-            else { dpred[g * 3] = du * wgt; dpred[g * 3 + 1] = dv * wgt; dpred[g * 3 + 2] = dw * wgt; }
+            const float c0 = m * inv_f + nf * inv_nf;
+            const float wgt = MSE ? 2.f * c0 : c0;
+            const float gu = pen_psi<KIND>(du, kp, kp2) * wgt, gv = pen_psi<KIND>(dv, kp, kp2) * wgt, gw = pen_psi<KIND>(dw, kp, kp2) * wgt;
+            if (out_act == FDN_ACT_TANH) tanh_grad_store(pred, g * 3, dpred + g * 3, gu, gv, gw);
+            else { dpred[g * 3] = gu; dpred[g * 3 + 1] = gv; dpred[g * 3 + 2] = gw; }
         }
     }
     const float a = block_sum(sf, red);
@@ -668,6 +699,28 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float* __restrict_
         part[0] = a; part[1] = b; part[2] = c;
         if (nparts == 5) { part[3] = 0.f; part[4] = 0.f; }
     }
+}
+
+// One kernel symbol for every kind (tests/test_isa.py pins the product library's kernel set): the block picks its instantiation of
+// loss_body once, on a wave-uniform scalar, before the voxel loop; no loop holds a switch on the kind.  kind == FDN_LOSS_MSE (what
+// fdn_loss_metrics / _div / _act pass) runs the instantiation that is the loss as it always was.  A kernel's register allocation is that
+// of its hungriest path -- Charbonnier's divergence branch, 78 VGPRs left alone, which would cost every kind the seventh wave -- so the
+// kernel asks for seven waves per SIMD: 72 VGPRs, no spills (DESIGN 5.4a'' has the table per instantiation).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void loss_main_kernel(const float* __restrict__ pred, const float* __restrict__ uh,
+                                                         const float* __restrict__ vh, const float* __restrict__ wh,
+                                                         const float* __restrict__ mask, float* __restrict__ scratch,
+                                                         float* __restrict__ dpred, int64_t V, int D, int H, int W, float div_w,
+                                                         int nparts, float nf_w, int out_act, int kind, float kp) {
+    __shared__ float red[4];
+    if (kind == FDN_LOSS_MSE) {                   // the shipped loss first: its code follows the prologue, as it always did
+        loss_body<FDN_LOSS_MSE>(pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts, nf_w, out_act, 0.f, red);
+        return;
+    }
+    int other = kind;
+    asm volatile("" : "+s"(other));               // a second scalar: the compiler does not fold the test above into one four-way switch
+    if (other == FDN_LOSS_MAE) loss_body<FDN_LOSS_MAE>(pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts, nf_w, out_act, 0.f, red);
+    else if (other == FDN_LOSS_HUBER) loss_body<FDN_LOSS_HUBER>(pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts, nf_w, out_act, kp, red);
+    else loss_body<FDN_LOSS_CHARBONNIER>(pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts, nf_w, out_act, kp, red);
 }
 
 // one wave per sample: lane t sums the partials of blocks t, t + 64, ..., then a shuffle tree -- a fixed order, so the reported loss /
@@ -1036,7 +1089,7 @@ extern "C" int fdn_upsample_trilinear_bwd_bf16(const uint16_t* dy, const uint16_
 // the three launches of both loss entry points; nparts 3: out (N,4) (fdn_loss_metrics), 5: out (N,5) (fdn_loss_metrics_div)
 static int loss_launch(const char* who, const float* pred, const float* uh, const float* vh, const float* wh, const float* mask, float* out,
                        float* dpred, float* scratch, int N, int64_t V, int D, int H, int W, float div_w, int nparts, void* stream,
-                       float nf_w = 1.f, int out_act = FDN_ACT_NONE) {
+                       float nf_w = 1.f, int out_act = FDN_ACT_NONE, int kind = FDN_LOSS_MSE, float kind_param = 0.f) {
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(scratch, 0, (size_t)N * 8 * sizeof(float), s);
     if (e != hipSuccess) { fdn_set_error("%s: memset: %s", who, hipGetErrorString(e)); return FDN_ERR_HIP; }
@@ -1045,7 +1098,7 @@ static int loss_launch(const char* who, const float* pred, const float* uh, cons
     hipLaunchKernelGGL(mask_sums_kernel, dim3(gx < 16 ? gx : 16, N), dim3(256), 0, s, mask, scratch, V);
     FDN_CHECK_LAUNCH("mask_sums_kernel");
     hipLaunchKernelGGL(loss_main_kernel, dim3(gx, N), dim3(256), 0, s, pred, uh, vh, wh, mask, scratch, dpred, V, D, H, W, div_w, nparts,
-                       nf_w, out_act);
+                       nf_w, out_act, kind, kind_param);
     FDN_CHECK_LAUNCH("loss_main_kernel");
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(N), dim3(64), 0, s, (const float*)scratch, out, N, gx, nparts, div_w, nf_w);
     FDN_CHECK_LAUNCH("loss_finalize_kernel");
@@ -1088,6 +1141,33 @@ extern "C" int fdn_loss_metrics_act(const float* pred, const float* uh, const fl
     }
     return loss_launch("fdn_loss_metrics_act", pred, uh, vh, wh, mask, out, dpred, scratch, N, (int64_t)D * H * W, D, H, W, div_weight, 5,
                        stream, non_fluid_weight, out_act);
+}
+
+// the data term under another penalty (FDN_LOSS_*): fdn_loss_metrics_act's checks, launches and buffers; FDN_LOSS_MSE is that call
+extern "C" int fdn_loss_metrics_kind(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask, int kind,
+                                     float kind_param, float div_weight, float non_fluid_weight, int out_act, float* out, float* dpred,
+                                     float* scratch, int N, int D, int H, int W, void* stream) {
+    FDN_REQUIRE(pred && uh && vh && wh && mask && out && scratch, "fdn_loss_metrics_kind: NULL operand");
+    FDN_REQUIRE(kind == FDN_LOSS_MSE || kind == FDN_LOSS_MAE || kind == FDN_LOSS_HUBER || kind == FDN_LOSS_CHARBONNIER,
+                "fdn_loss_metrics_kind: kind %d is not a loss (FDN_LOSS_MSE, _MAE, _HUBER or _CHARBONNIER)", kind);
+    if (kind == FDN_LOSS_HUBER || kind == FDN_LOSS_CHARBONNIER)
+        FDN_REQUIRE(__builtin_isfinite(kind_param) && kind_param > 0.f, "fdn_loss_metrics_kind: %s %g must be finite and > 0",
+                    kind == FDN_LOSS_HUBER ? "the Huber delta" : "the Charbonnier epsilon", (double)kind_param);
+    else
+        FDN_REQUIRE(kind_param == 0.f, "fdn_loss_metrics_kind: %s takes no parameter, kind_param %g must be 0",
+                    kind == FDN_LOSS_MSE ? "FDN_LOSS_MSE" : "FDN_LOSS_MAE", (double)kind_param);
+    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_loss_metrics_kind: extents N=%d D=%d H=%d W=%d must be positive", N, D, H, W);
+    FDN_REQUIRE((int64_t)D * H * W <= (int64_t)INT32_MAX, "fdn_loss_metrics_kind: %d x %d x %d voxels per sample exceed 2^31 - 1", D, H, W);
+    FDN_REQUIRE(__builtin_isfinite(div_weight) && div_weight >= 0.f, "fdn_loss_metrics_kind: div_weight %g must be finite and >= 0",
+                (double)div_weight);
+    FDN_REQUIRE(__builtin_isfinite(non_fluid_weight) && non_fluid_weight >= 0.f,
+                "fdn_loss_metrics_kind: non_fluid_weight %g must be finite and >= 0", (double)non_fluid_weight);
+    if (out_act != FDN_ACT_NONE && out_act != FDN_ACT_TANH) {
+        fdn_set_error("fdn_loss_metrics_kind: out_act %d is not an activation of the heads (FDN_ACT_NONE or FDN_ACT_TANH)", out_act);
+        return FDN_ERR_UNSUPPORTED;
+    }
+    return loss_launch("fdn_loss_metrics_kind", pred, uh, vh, wh, mask, out, dpred, scratch, N, (int64_t)D * H * W, D, H, W, div_weight, 5,
+                       stream, non_fluid_weight, out_act, kind, kind_param);
 }
 
 extern "C" int fdn_volume_metrics(const void* pred, int pred_is_f64, const float* truth, const float* mask, int mask_frames,

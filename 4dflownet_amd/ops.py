@@ -5,7 +5,9 @@ Tensors must be fp32, contiguous and on a ROCm device; anything else raises (no 
 import ctypes
 import functools
 import math
+import numbers
 import operator
+import struct
 
 import numpy as np
 import torch
@@ -610,19 +612,58 @@ def upsample_trilinear_bwd(dy, R, y_prev=None, act=ACT_NONE, alpha=LEAKY_ALPHA, 
     return _upsample_trilinear_bwd("fdn_upsample_trilinear_bwd", ACT_DTYPE, dy, R, y_prev, act, alpha, out)
 
 
+LOSS_KINDS = {'mse': 0, 'mae': 1, 'huber': 2, 'charbonnier': 3}       # FDN_LOSS_MSE .. FDN_LOSS_CHARBONNIER
+LOSS_PARAM_DEFAULTS = {'huber': 1.0, 'charbonnier': 1e-3}             # delta (tf.keras.losses.Huber's default), epsilon
+
+
+def checked_loss_kind(kind, kind_param, who="loss_metrics", error=None):
+    """(name, FDN_LOSS_* code, parameter as the float the entry point takes) of a penalty of the data term, validated without a tensor.
+    'mse' and 'mae' take no parameter (None or 0); 'huber' takes delta and 'charbonnier' epsilon, finite and > 0 also once rounded to
+    fp32, None = the default (1.0 / 1e-3)."""
+    error = error or FdnError
+    if not isinstance(kind, str) or kind not in LOSS_KINDS:
+        raise error("%s: the loss must be one of %s, got %r" % (who, ", ".join(repr(k) for k in LOSS_KINDS), kind))
+    if kind not in LOSS_PARAM_DEFAULTS:
+        if kind_param is not None and not (isinstance(kind_param, numbers.Real) and not isinstance(kind_param, bool) and kind_param == 0):
+            raise error("%s: the %r loss takes no parameter, got %r" % (who, kind, kind_param))
+        return kind, LOSS_KINDS[kind], 0.0
+    what = "delta" if kind == 'huber' else "epsilon"
+    if kind_param is None:
+        kind_param = LOSS_PARAM_DEFAULTS[kind]
+    try:
+        pf = float(kind_param)
+        if isinstance(kind_param, bool):
+            raise TypeError
+        p32 = struct.unpack("f", struct.pack("f", pf))[0] if math.isfinite(pf) else pf
+    except (TypeError, ValueError, OverflowError):
+        raise error("%s: %s of the %r loss must be a finite number > 0, got %r" % (who, what, kind, kind_param)) from None
+    if not (math.isfinite(p32) and p32 > 0):
+        raise error("%s: %s of the %r loss must be a finite number > 0 (in fp32), got %r" % (who, what, kind, kind_param))
+    return kind, LOSS_KINDS[kind], pf
+
+
 def loss_metrics(pred, uh, vh, wh, mask, want_grad=True, out=None, dpred=None, scratch=None, div_weight=0.0, non_fluid_weight=1.0,
-                 out_act=ACT_NONE):
+                 out_act=ACT_NONE, kind='mse', kind_param=None):
     """Returns out (N,4) = [mse-loss, rel-err %, sum mask, sum nonfluid] and dpred (N,...,3) or None.
     div_weight != 0 (pred (N,D,H,W,3)): fdn_loss_metrics_div, out (N,5) with the weighted divergence loss div_b in column 4 and its
     gradient in dpred (the sample's loss is out[:, 0] + out[:, 4]).  div_weight == 0 is exactly the plain call.
     non_fluid_weight != 1 or out_act == ACT_TANH (pred (N,D,H,W,3)): fdn_loss_metrics_act, out (N,5): the non-fluid part of the MSE and of
     the divergence term weighted, and dpred the gradient w.r.t. the heads' PRE-activations (times 1 - pred^2 under ACT_TANH) -- what
-    FlowNetModel.backward takes.  At the defaults the calls are exactly the ones above."""
+    FlowNetModel.backward takes.  At the defaults the calls are exactly the ones above.
+    kind: the penalty rho of the data term, summed over the three components of the residual d = pred - truth: 'mse' d^2 (the reference's
+    calculate_mse; the calls above, untouched), 'mae' |d|, 'huber' d^2 / 2 up to |d| = kind_param = delta and delta (|d| - delta / 2)
+    beyond (default 1.0; on velocities normalised to [-1, 1] that is MSE / 2 almost everywhere, so choose a smaller delta),
+    'charbonnier' sqrt(d^2 + eps^2), kind_param = eps (default 1e-3).  Other than 'mse' (pred (N,D,H,W,3)): fdn_loss_metrics_kind, out
+    (N,5) with the data term in column 0; the divergence term stays squared, the metric and the counts do not depend on the kind."""
+    kind, kind_code, kind_param = checked_loss_kind(kind, kind_param)
     non_fluid_weight = float(non_fluid_weight)
     if not (math.isfinite(non_fluid_weight) and non_fluid_weight >= 0):
         raise FdnError("loss_metrics: non_fluid_weight must be a finite number >= 0, got %r" % (non_fluid_weight,))
     if out_act not in (ACT_NONE, ACT_TANH):
         raise FdnError("loss_metrics: out_act must be ACT_NONE or ACT_TANH, got %r" % (out_act,))
+    if kind != 'mse':
+        return _loss_metrics_div(pred, uh, vh, wh, mask, float(div_weight), want_grad, out, dpred, scratch, non_fluid_weight, out_act,
+                                 (kind_code, kind_param))
     if non_fluid_weight != 1.0 or out_act != ACT_NONE:
         return _loss_metrics_div(pred, uh, vh, wh, mask, float(div_weight), want_grad, out, dpred, scratch, non_fluid_weight, out_act)
     N = pred.shape[0]
@@ -641,8 +682,9 @@ def loss_metrics(pred, uh, vh, wh, mask, want_grad=True, out=None, dpred=None, s
     return out, (dpred if want_grad else None)
 
 
-def _loss_metrics_div(pred, uh, vh, wh, mask, div_weight, want_grad, out, dpred, scratch, non_fluid_weight=None, out_act=ACT_NONE):
-    """fdn_loss_metrics_div, or (non_fluid_weight given) fdn_loss_metrics_act: same operands, same buffers."""
+def _loss_metrics_div(pred, uh, vh, wh, mask, div_weight, want_grad, out, dpred, scratch, non_fluid_weight=None, out_act=ACT_NONE, kind=None):
+    """fdn_loss_metrics_div, (non_fluid_weight given) fdn_loss_metrics_act or (kind = (code, parameter) given too) fdn_loss_metrics_kind:
+    same operands, same buffers."""
     if pred.dim() != 5 or pred.shape[-1] != 3:
         raise FdnError("loss_metrics: the divergence term needs pred of shape (N,D,H,W,3), got %s" % (tuple(pred.shape),))
     N, D, H, W = pred.shape[:4]
@@ -658,6 +700,12 @@ def _loss_metrics_div(pred, uh, vh, wh, mask, div_weight, want_grad, out, dpred,
         dpred = torch.empty_like(pred)
     if out.numel() < N * 5 or scratch.numel() < N * (8 + 5 * 256) or (want_grad and dpred.numel() != pred.numel()):
         raise FdnError("loss_metrics: out needs (N,5), scratch N*(8 + 5*256) floats and dpred pred's shape")
+    if kind is not None:
+        check(_lib.load().fdn_loss_metrics_kind(_p(pred), _p(uh), _p(vh), _p(wh), _p(mask), kind[0], kind[1], div_weight, non_fluid_weight,
+                                                int(out_act), _p(out), _p(dpred, allow_none=True) if want_grad else None, _p(scratch),
+                                                N, D, H, W, _stream()),
+              "fdn_loss_metrics_kind")
+        return out, (dpred if want_grad else None)
     if non_fluid_weight is not None:
         check(_lib.load().fdn_loss_metrics_act(_p(pred), _p(uh), _p(vh), _p(wh), _p(mask), div_weight, non_fluid_weight, int(out_act), _p(out),
                                                _p(dpred, allow_none=True) if want_grad else None, _p(scratch), N, D, H, W, _stream()),

@@ -124,11 +124,13 @@ class _Optimizer:
 
 
 class TrainerController:
+    loss, loss_param = 'mse', None     # the data term's penalty: instance attributes, read on every step (see __init__)
+
     def __init__(self, patch_size, res_increase, initial_learning_rate=1e-4, quicksave_enable=True,
                  network_name='4DFlowNet', low_resblock=8, hi_resblock=4, device=None, seed=0, dtype='float32',
                  bucketed_allreduce=None, conv_algo=None, div_weight=0, accum_steps=1, trainable=None, global_clipnorm=None,
                  clipvalue=None, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, ema_validation=False,
-                 output_activation=None, non_fluid_weight=1):
+                 output_activation=None, non_fluid_weight=1, loss='mse', loss_param=None):
         """Reference arguments: TrainerController.py:18.  Extra (keyword-only in spirit): device, seed (Glorot draw), dtype
         (activation storage, 'float32' | 'bfloat16'), bucketed_allreduce (data parallel only: True = one asynchronous SUM
         all-reduce per gradient bucket started inside backward -- the default --, False = ONE all-reduce of the whole buffer
@@ -163,7 +165,14 @@ class TrainerController:
         network, 'tanh' = the bounded heads its first published weights were trained with; see FlowNetModel), non_fluid_weight
         ("Weighting for non fluid region", TrainerController.py:24: a finite number >= 0 on the non-fluid part of the MSE and of the
         divergence term; 1 = the reference's shipped loss, 0 = a fluid-only loss.  Like div_weight the attribute is read on every
-        step)."""
+        step), loss / loss_param (the penalty of the data term, per component of pred - truth: 'mse' = the reference's calculate_mse,
+        'mae' |d|, 'huber' with loss_param = delta (None = 1.0, tf.keras.losses.Huber's default; on velocities normalised to [-1, 1]
+        that is MSE / 2 almost everywhere, so choose a smaller delta), 'charbonnier' sqrt(d^2 + eps^2) with loss_param = eps (None =
+        1e-3); 'mse' and 'mae' take no parameter.  The divergence term stays squared and the relative-error metric does not depend on
+        the choice.  The names of loss_metrics and the columns of loss.csv stay the reference's: train_mse / val_mse hold the data term
+        under the chosen penalty, and val_loss, the model-selection metric, is in the chosen loss's units, so values of runs with
+        different losses do not compare.  Whether any of them improves accuracy over 'mse' is unmeasured.  Both attributes are read on
+        every step: train_step, test_step and quicksave follow a later assignment)."""
         self.use_ema = use_ema
         self.ema_momentum = ema_momentum
         self.ema_overwrite_frequency = ema_overwrite_frequency
@@ -189,6 +198,9 @@ class TrainerController:
         self._accum_has = False        # the accumulator holds a contribution of the running group (an empty shard contributes nothing)
         self.non_fluid_weight = non_fluid_weight   # TrainerController.py:24
         self._checked_non_fluid_weight()
+        self.loss = loss
+        self.loss_param = loss_param
+        self._checked_loss()
         self.res_increase = res_increase
         self.patch_size = patch_size
         self.QUICKSAVE_ENABLED = quicksave_enable
@@ -258,6 +270,11 @@ class TrainerController:
             raise ValueError("non_fluid_weight must be a finite number >= 0, got %r" % (w,))
         return wf
 
+    def _checked_loss(self):
+        """(name, parameter or None) of the data term's penalty as the attributes stand, validated: ops.checked_loss_kind."""
+        kind, _, param = ops.checked_loss_kind(self.loss, self.loss_param, who="TrainerController: loss / loss_param", error=ValueError)
+        return kind, (param if kind in ops.LOSS_PARAM_DEFAULTS else None)
+
     def _checked_accum_steps(self):
         k = self.accum_steps
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
@@ -273,12 +290,15 @@ class TrainerController:
         return _ema_arguments(self.use_ema, self.ema_momentum, self.ema_overwrite_frequency, self.ema_validation)
 
     def _loss_call(self, hires, predictions, mask, want_grad):
-        """The loss pass of every step and of quicksave: div_weight and non_fluid_weight as the attributes stand now, the activation the
-        model's heads ended in -- so dpred is the gradient w.r.t. their pre-activations, what model.backward takes.  At the defaults
-        (1, linear) ops.loss_metrics makes the calls it always made.  Returns (out, dpred, div_weight)."""
+        """The loss pass of every step and of quicksave: div_weight, non_fluid_weight and loss / loss_param as the attributes stand now,
+        the activation the model's heads ended in -- so dpred is the gradient w.r.t. their pre-activations, what model.backward takes.
+        At the defaults (1, linear, 'mse') ops.loss_metrics is called as it always was and makes the calls it always made.  Returns
+        (out, dpred, div_weight)."""
         div_weight = self._checked_div_weight()
+        kind, param = self._checked_loss()
+        more = {} if kind == 'mse' else {'kind': kind, 'kind_param': param}
         out, dpred = ops.loss_metrics(predictions, hires[0], hires[1], hires[2], mask, want_grad=want_grad, div_weight=div_weight,
-                                      non_fluid_weight=self._checked_non_fluid_weight(), out_act=self.model.out_act)
+                                      non_fluid_weight=self._checked_non_fluid_weight(), out_act=self.model.out_act, **more)
         return out, dpred, div_weight
 
     def calculate_and_update_metrics(self, hires, predictions, mask, metric_set, want_grad):
@@ -557,6 +577,9 @@ class TrainerController:
         self._log('Divergence weight: %s\n' % self.div_weight)
         if self._checked_non_fluid_weight() != 1:
             self._log('Non fluid weight: %s\n' % self.non_fluid_weight)
+        kind, param = self._checked_loss()
+        if kind != 'mse':
+            self._log('Loss: %s%s\n' % (kind, '' if param is None else ' (%s=%s)' % ('delta' if kind == 'huber' else 'epsilon', param)))
         if self.model.output_activation != 'linear':
             self._log('Output activation: %s\n' % self.model.output_activation)
         clipnorm, clipvalue = self._checked_clip()

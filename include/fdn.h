@@ -285,6 +285,29 @@ int fdn_loss_metrics_act(const float* pred, const float* uh, const float* vh, co
                          float non_fluid_weight, int out_act, float* out, float* dpred, float* scratch, int N, int D, int H, int W,
                          void* stream);
 
+/* fdn_loss_metrics_act with a choice of the data term's penalty.  Per component of the residual d = pred_c - truth_c:
+ *   FDN_LOSS_MSE          rho = d^2                                                   psi = 2 d     (TrainerController.calculate_mse)
+ *   FDN_LOSS_MAE          rho = |d|                                                   psi = sign(d), psi(0) = 0 (tf.abs' gradient)
+ *   FDN_LOSS_HUBER        rho = d^2 / 2 if |d| <= delta, else delta (|d| - delta / 2) psi = d, else delta sign(d)   (tf.keras.losses.Huber)
+ *   FDN_LOSS_CHARBONNIER  rho = sqrt(d^2 + eps^2)                                     psi = d / sqrt(d^2 + eps^2)
+ * kind_param: delta (Huber) or eps (Charbonnier), finite and > 0; 0 for MSE and MAE, which have none.  On velocities normalised to
+ * [-1, 1] a delta of 1 (Keras' default) makes Huber half the MSE almost everywhere: choose a smaller one.
+ * Per voxel e = sum_c rho(d_c), and e takes the place of e^2 in fdn_loss_metrics_act's column 0:
+ *   out[0] = sum(mask e) / (sum(mask) + 1) + non_fluid_weight * sum(nf e) / (sum(nf) + 1).
+ * The divergence term (out[4]) keeps its squared form for every kind; the relative-error column and the two counts do not depend on
+ * the kind.  dpred = d(sum_b (out[0] + out[4])) / d(head pre-activations) with psi in the data term's part, exactly 0 where d is 0
+ * (and div_weight is 0).  Same operands, out (N,5) layout, scratch size (FDN_LOSS_DIV_SCRATCH_FLOATS(N)), launches and determinism as
+ * fdn_loss_metrics_act; kind == FDN_LOSS_MSE is that call, bit for bit.  Refused before the device is touched: NULL operands, an
+ * unknown kind, a delta / eps that is not finite or <= 0, a non-zero kind_param for MSE / MAE, and everything fdn_loss_metrics_act
+ * refuses. */
+#define FDN_LOSS_MSE 0
+#define FDN_LOSS_MAE 1
+#define FDN_LOSS_HUBER 2
+#define FDN_LOSS_CHARBONNIER 3
+int fdn_loss_metrics_kind(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask, int kind,
+                          float kind_param, float div_weight, float non_fluid_weight, int out_act, float* out, float* dpred,
+                          float* scratch, int N, int D, int H, int W, void* stream);
+
 /* Whole-volume evaluation of a stitched prediction against the high-resolution truth: 26 sums per frame, from which the host derives the
  * reference's loss and metric (src/Network/TrainerController.py:96-107, src/Network/loss_utils.py:64-101), the divergence term, RMSE
  * and the regression line of prediction on truth.  pred (F,3,X,Y,Z) planar, fp32 (pred_is_f64 = 0) or float64 (1) -- what

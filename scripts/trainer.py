@@ -62,6 +62,11 @@ if __name__ == "__main__":
     div_weight = 0
     non_fluid_weight = 1
     output_activation = None
+    # penalty of the data term: 'mse' (the reference's calculate_mse) | 'mae' | 'huber' (loss_param = delta, None = 1.0; on velocities
+    # normalised to [-1, 1] choose a smaller one) | 'charbonnier' (loss_param = epsilon, None = 1e-3).  The divergence term stays squared;
+    # train_mse / val_mse and val_loss are then in the chosen loss's units.  Whether one of them beats 'mse' is unmeasured.
+    loss = 'mse'
+    loss_param = None
 
     parallel.init_from_env()
     trainset = data.load_indexes(training_file)
@@ -79,7 +84,8 @@ if __name__ == "__main__":
     print("4DFlowNet Patch %d, lr %s, batch %d" % (patch_size, initial_learning_rate, batch_size))
     network = trainer.TrainerController(patch_size, res_increase, initial_learning_rate, QUICKSAVE, network_name,
                                         low_resblock, hi_resblock, accum_steps=accum_steps, trainable=trainable, div_weight=div_weight,
-                                        non_fluid_weight=non_fluid_weight, output_activation=output_activation)
+                                        non_fluid_weight=non_fluid_weight, output_activation=output_activation, loss=loss,
+                                        loss_param=loss_param)
     network.init_model_dir()
     if restore and trainable is not None:
         print("Fine-tuning from the weights of %s..." % model_file)
