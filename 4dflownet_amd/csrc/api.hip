@@ -10,6 +10,7 @@
 #include <type_traits>
 #include <utility>
 #include "fdn_common.h"
+#include "wgrad64_plan.h"
 
 static thread_local char g_err[512] = "";
 
@@ -397,20 +398,37 @@ extern "C" int fdn_conv_cout1_dgrad_folded_bf16(const float* dz, const float* w,
 }
 
 // ---- weight gradients ----
-// The 64->64 kernel of a storage type.  fp32: Winograd F(3,4) along W (wgrad64_wino.hip), half the multiplies of the direct kernel,
-// which FDN_ALGO_DIRECT selects -- the workspace serves either; bf16: one kernel
-static int wgrad64_launch(const float* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H, int W, int algo, hipStream_t s) {
-    return (fdn_wgrad64_force_direct || algo == FDN_ALGO_DIRECT) ? fdn_wgrad64_launch(x, dz, dw, ws, ws_bytes, N, D, H, W, s)
-                                                                 : fdn_wgrad64_wino_launch(x, dz, dw, ws, ws_bytes, N, D, H, W, s, algo);
+// The 64->64 layers: fdn_wgrad64_plan (wgrad64_plan.h) decides kernels, chunks, splits and workspace; here the plan is walked.
+static FdnWgrad64Hooks wgrad64_hooks() {
+    FdnWgrad64Hooks hk;
+    hk.force_direct = fdn_wgrad64_force_direct; hk.wino_nodep = fdn_wgrad64_wino_nodep_hook(); hk.bf16_variant = fdn_wgrad64_bf16_variant_hook();
+    return hk;
 }
-static int wgrad64_launch(const uint16_t* x, const uint16_t* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H, int W, int, hipStream_t s) {
-    return fdn_wgrad64_bf16_launch(x, dz, dw, ws, ws_bytes, N, D, H, W, s);
+static int wgrad64_step_launch(const FdnWgrad64Step& st, const float* const* x, const float* const* dz, float* const* dw, void* ws, size_t ws_bytes,
+                               int N, int D, int H, int W, hipStream_t s) {
+    return st.route == FDN_WG_DIRECT ? fdn_wgrad64_launch(st, x[0], dz[0], dw[0], ws, ws_bytes, N, D, H, W, s)
+                                     : fdn_wgrad64_wino_launch(st, x, dz, dw, ws, ws_bytes, N, D, H, W, s);
 }
+static int wgrad64_step_launch(const FdnWgrad64Step& st, const uint16_t* const* x, const uint16_t* const* dz, float* const* dw, void* ws,
+                               size_t ws_bytes, int N, int D, int H, int W, hipStream_t s) {
+    return fdn_wgrad64_bf16_launch(st, x, dz, dw, ws, ws_bytes, N, D, H, W, s);
+}
+// every step of a plan in order, each reusing the workspace behind the one before (stream order); x, dz, dw: the tables of all layers
+template <typename T>
+static int wgrad64_walk(const char* who, const FdnWgrad64Plan& plan, const T* const* x, const T* const* dz, float* const* dw, void* ws,
+                        size_t ws_bytes, int N, int D, int H, int W, hipStream_t s) {
+    FDN_REQUIRE(plan.addr32_ok, "wgrad64: x of %dx%dx%dx%dx64 floats exceeds the 32-bit buffer addressing", N, D, H, W);
+    for (const FdnWgrad64Step& st : plan.steps) {
+        if (st.count == 1) FDN_REQUIRE(x[st.first] && dz[st.first] && dw[st.first], "%s: NULL pointer for layer %d", who, st.first);
+        if (int rc = wgrad64_step_launch(st, x + st.first, dz + st.first, dw + st.first, ws, ws_bytes, N, D, H, W, s)) return rc;
+    }
+    return FDN_OK;
+}
+
 template <typename T>
 static size_t conv3d_wgrad_workspace_bytes(int N, int D, int H, int W, int Cin, int Cout, int K) {
     if (!(Cin == 64 && Cout == 64 && K == 3)) return fdn_small_wgrad_workspace_bytes(Cin, Cout, K);
-    if constexpr (kBf16<T>) return fdn_wgrad64_bf16_workspace_bytes(N, D, H, W);
-    else return std::max(fdn_wgrad64_workspace_bytes(N, D, H, W), fdn_wgrad64_wino_workspace_bytes(N, D, H, W));
+    return fdn_wgrad64_bound(kBf16<T>, N, D, H, W);
 }
 extern "C" size_t fdn_conv3d_wgrad_workspace_bytes(int N, int D, int H, int W, int Cin, int Cout, int K) {
     return conv3d_wgrad_workspace_bytes<float>(N, D, H, W, Cin, Cout, K);
@@ -444,7 +462,7 @@ static int conv3d_wgrad(const char* who, const T* x, const T* x2, const void* dz
     }
     if (Cin == 64 && Cout == 64 && K == 3) {
         FDN_REQUIRE(lddz == 64 && dz_coff == 0, "%s: 64->64 path reads dense dz rows", who);
-        rc = wgrad64_launch(x, dzt, dw, workspace, workspace_bytes, N, D, H, W, algo, s);
+        rc = wgrad64_walk<T>(who, fdn_wgrad64_plan(kBf16<T>, 1, N, D, H, W, algo, wgrad64_hooks()), &x, &dzt, &dw, workspace, workspace_bytes, N, D, H, W, s);
     } else if (Cin == 3 && Cout == 64 && K == 3) {
         FDN_REQUIRE(lddz == 64 && dz_coff == 0, "%s(3->64): dense dz rows", who);
         rc = fdn_wgrad_cin3_launch<T>(x, dzt, dw, workspace, workspace_bytes, N, D, H, W, s);
@@ -470,33 +488,14 @@ extern "C" int fdn_conv3d_wgrad_bf16(const uint16_t* x, const uint16_t* x2, cons
                                   FDN_ALGO_AUTO, stream);
 }
 
-// Weight gradients of n_layers 64->64 3x3x3 layers that share one grid, in ONE launch (+ one reduction launch) where the kernel allows
-// it, else layer by layer through conv3d_wgrad.  fp32: W % 4 == 0, even D, FDN_ALGO_AUTO / _WINO_H2; the batched kernel gives every
-// layer 64 / n_layers splits of the voxel sum where the single-layer launch uses 63: equal to fp32 rounding, not bit for bit.  bf16:
-// fdn_wgrad64_bf16_batch_ok.
-static bool wgrad_batchable(int n_layers, int D, int W, int algo) {
-    return !fdn_wgrad64_force_direct && (W & 3) == 0 && fdn_wgrad64_wino_batch_ok(n_layers, D, algo);
-}
-template <typename T>
-static size_t conv3d_wgrad_batch_workspace_bytes(int n_layers, int N, int D, int H, int W) {
-    if (n_layers <= 0 || N <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t one = conv3d_wgrad_workspace_bytes<T>(N, D, H, W, 64, 64, 3);
-    size_t all = 0;
-    if constexpr (kBf16<T>) {
-        if (fdn_wgrad64_bf16_batch_ok(n_layers, N, D, H, W)) all = fdn_wgrad64_bf16_batch_workspace_bytes(n_layers, N, D, H, W);
-    } else if (wgrad_batchable(n_layers, D, W, FDN_ALGO_AUTO)) {
-        for (int c = 2; c <= n_layers; ++c) {          // (the batch may go out in chunks of fewer layers with more splits each: conv3d_wgrad_batch)
-            const size_t b = fdn_wgrad64_wino_batch_workspace_bytes(c, N, D, H, W);
-            if (b > all) all = b;
-        }
-    }
-    return all > one ? all : one;
-}
+// Weight gradients of n_layers 64->64 3x3x3 layers that share one grid: in batched launches (+ one reduction launch each) where the plan
+// allows it, else layer by layer.  The batched fp32 kernel gives every layer 64 / layers splits of the voxel sum where the single-layer
+// launch uses 64: equal to fp32 rounding, not bit for bit.
 extern "C" size_t fdn_conv3d_wgrad_batch_workspace_bytes(int n_layers, int N, int D, int H, int W) {
-    return conv3d_wgrad_batch_workspace_bytes<float>(n_layers, N, D, H, W);
+    return fdn_wgrad64_batch_bound(false, n_layers, N, D, H, W, wgrad64_hooks());
 }
 extern "C" size_t fdn_conv3d_wgrad_bf16_batch_workspace_bytes(int n_layers, int N, int D, int H, int W) {
-    return conv3d_wgrad_batch_workspace_bytes<uint16_t>(n_layers, N, D, H, W);
+    return fdn_wgrad64_batch_bound(true, n_layers, N, D, H, W, wgrad64_hooks());
 }
 
 template <typename T>
@@ -505,38 +504,14 @@ static int conv3d_wgrad_batch(const char* who, const T* const* x, const T* const
     FDN_REQUIRE(x && dz && dw && n_layers > 0, "%s: NULL table or n_layers <= 0", who);
     FDN_REQUIRE(algo >= FDN_ALGO_AUTO && algo <= FDN_ALGO_LAST, "%s: bad algo %d", who, algo);
     FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "%s: bad dims", who);
-    const size_t need = conv3d_wgrad_batch_workspace_bytes<T>(n_layers, N, D, H, W);
+    const size_t need = fdn_wgrad64_batch_bound(kBf16<T>, n_layers, N, D, H, W, wgrad64_hooks());
     if (workspace_bytes < need || !workspace) {
         fdn_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
         return FDN_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    auto single = [&](int i) {
-        return conv3d_wgrad<T>(who, x[i], nullptr, dz[i], dw[i], nullptr, workspace, workspace_bytes, N, D, H, W, 64, 64, 3, 64, 0, algo, stream);
-    };
-    bool batched;
-    if constexpr (kBf16<T>) batched = fdn_wgrad64_bf16_batch_ok(n_layers, N, D, H, W);
-    else batched = wgrad_batchable(n_layers, D, W, algo);
-    if (!batched) {
-        for (int i = 0; i < n_layers; ++i) {
-            FDN_REQUIRE(x[i] && dz[i] && dw[i], "%s: NULL pointer for layer %d", who, i);
-            if (int rc = single(i)) return rc;
-        }
-    } else if constexpr (kBf16<T>) {
-        if (int rc = fdn_wgrad64_bf16_batch_launch(x, dz, dw, n_layers, workspace, workspace_bytes, N, D, H, W, s)) return rc;
-    } else {
-        // The batched kernel gives every layer 64 / n splits x 4 coordinates: n = 11 fills 220 of the 256 CUs.  Such a batch goes out in
-        // chunks that fill the chip (>= 63 of 64 split slots: 1, 2, 3, 4, 7, 8, 9, 16 layers), a batch at >= 15/16 as it is.
-        auto fill64 = [](int c) { return (64 / c) * c; };
-        for (int i0 = 0; i0 < n_layers;) {
-            const int rem = n_layers - i0;
-            int c = rem;
-            if (fill64(rem) < 60) { c = rem - 1; while (c > 1 && fill64(c) < 63) --c; }
-            if (c >= 2) { if (int rc = fdn_wgrad64_wino_batch_launch(x + i0, dz + i0, dw + i0, c, workspace, workspace_bytes, N, D, H, W, s)) return rc; }
-            else if (int rc = single(i0)) return rc;
-            i0 += c;
-        }
-    }
+    const FdnWgrad64Plan plan = fdn_wgrad64_plan(kBf16<T>, n_layers, N, D, H, W, algo, wgrad64_hooks());
+    if (int rc = wgrad64_walk<T>(who, plan, x, dz, dw, workspace, workspace_bytes, N, D, H, W, s)) return rc;
     if (dbias)                           // (stream-ordered behind the reduction: the workspace is free again)
         for (int i = 0; i < n_layers; ++i)
             if (dbias[i])
@@ -552,3 +527,22 @@ extern "C" int fdn_conv3d_wgrad_bf16_batch(const uint16_t* const* x, const uint1
     return conv3d_wgrad_batch<uint16_t>("fdn_conv3d_wgrad_bf16_batch", x, dz, dw, dbias, n_layers, workspace, workspace_bytes, N, D, H, W,
                                         FDN_ALGO_AUTO, stream);
 }
+
+#ifdef FDN_TEST_HOOKS
+// The plan of a call as text, one line per step and a last line with the plan's workspace_bytes, under the hooks as they are set; needs no
+// device.  Returns the length of the text; it is written (NUL-terminated) when n exceeds that length.
+extern "C" int fdn_debug_wgrad64_plan(int bf16, int n_layers, int N, int D, int H, int W, int algo, char* buf, size_t n) {
+    const FdnWgrad64Plan plan = fdn_wgrad64_plan(bf16 != 0, n_layers, N, D, H, W, algo, wgrad64_hooks());
+    std::string text;
+    char line[256];
+    for (const FdnWgrad64Step& st : plan.steps) {
+        snprintf(line, sizeof(line), "route=%s first=%d count=%d splits=%d planes=%d grid=%d tiles=%d nseg=%d seg_len=%d partial_bytes=%zu\n",
+                 fdn_wgrad64_route_name(st.route), st.first, st.count, st.splits, st.planes, st.grid, st.tiles, st.nseg, st.seg_len, st.partial_bytes);
+        text += line;
+    }
+    snprintf(line, sizeof(line), "workspace_bytes=%zu addr32_ok=%d\n", plan.workspace_bytes, (int)plan.addr32_ok);
+    text += line;
+    if (buf && n > text.size()) memcpy(buf, text.c_str(), text.size() + 1);
+    return (int)text.size();
+}
+#endif

@@ -324,17 +324,14 @@ inline unsigned fdn_fold_halo_border_blocks(int N, int D, int H, int W, int vecs
     const int64_t nb = ((int64_t)N * per_n * vecs + 255) / 256;
     return (unsigned)(nb < 1 ? 1 : (nb > 4096 ? 4096 : nb));
 }
-int fdn_wgrad64_launch(const float* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H,
+// The 64->64 weight gradient: fdn_wgrad64_plan (wgrad64_plan.h) decides route, chunks, splits and workspace; each launcher issues one
+// step of it.  x, dz, dw of the table forms: the step's st.count layers.  _hook: the test build's switch of that translation unit
+struct FdnWgrad64Step;
+int fdn_wgrad64_launch(const FdnWgrad64Step& st, const float* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H,
                        int W, hipStream_t s);
-size_t fdn_wgrad64_workspace_bytes(int N, int D, int H, int W);
-int fdn_wgrad64_wino_launch(const float* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H,
-                            int W, hipStream_t s, int algo = FDN_ALGO_AUTO);
-size_t fdn_wgrad64_wino_workspace_bytes(int N, int D, int H, int W);
-// several 64->64 layers of one grid in ONE launch (wgrad64_wino.hip); _ok: applicable (else the caller loops over fdn_wgrad64_wino_launch)
-bool fdn_wgrad64_wino_batch_ok(int n_layers, int D, int algo);
-size_t fdn_wgrad64_wino_batch_workspace_bytes(int n_layers, int N, int D, int H, int W);
-int fdn_wgrad64_wino_batch_launch(const float* const* x, const float* const* dz, float* const* dw, int n_layers, void* ws, size_t ws_bytes,
-                                  int N, int D, int H, int W, hipStream_t s);
+int fdn_wgrad64_wino_launch(const FdnWgrad64Step& st, const float* const* x, const float* const* dz, float* const* dw, void* ws, size_t ws_bytes,
+                            int N, int D, int H, int W, hipStream_t s);
+int fdn_wgrad64_wino_nodep_hook();
 int fdn_wgrad64_reduce_launch(const float* partial, float* dw, int S, hipStream_t s);
 
 // bf16 activation path (conv64_bf16.hip)
@@ -342,11 +339,6 @@ int fdn_conv64_bf16_launch(const FdnConv64BfCall& c);
 int fdn_fold_halo_border_launch(const float* s0, const float* s1, const float* s2, int nsrc, const uint16_t* skip,
                                 const uint16_t* yprev, int act, float alpha, uint16_t* out, int N, int D, int H, int W,
                                 hipStream_t s);
-size_t fdn_wgrad64_bf16_workspace_bytes(int N, int D, int H, int W);
-int fdn_wgrad64_bf16_launch(const uint16_t* x, const uint16_t* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H,
-                            int W, hipStream_t s);
-// several 64->64 layers of one grid per launch (wgrad64_bf16.hip)
-bool fdn_wgrad64_bf16_batch_ok(int n_layers, int N, int D, int H, int W);
-size_t fdn_wgrad64_bf16_batch_workspace_bytes(int n_layers, int N, int D, int H, int W);
-int fdn_wgrad64_bf16_batch_launch(const uint16_t* const* x, const uint16_t* const* dz, float* const* dw, int n_layers, void* ws, size_t ws_bytes,
-                                  int N, int D, int H, int W, hipStream_t s);
+int fdn_wgrad64_bf16_launch(const FdnWgrad64Step& st, const uint16_t* const* x, const uint16_t* const* dz, float* const* dw, void* ws,
+                            size_t ws_bytes, int N, int D, int H, int W, hipStream_t s);
+int fdn_wgrad64_bf16_variant_hook();

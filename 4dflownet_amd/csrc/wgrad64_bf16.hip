@@ -19,6 +19,7 @@
 //     cover all 64 banks (conflict-free transposing reads); every k-step offset is a multiple of 4 rows, so the per-lane
 //     addresses are computed once and the steps are immediates.
 #include "fdn_common.h"
+#include "wgrad64_plan.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -42,7 +43,9 @@ FDN_HOOK_VAR(int, fdn_wgrad64bf_dbg, 0);
 FDN_HOOK_VAR(int, fdn_wgrad64bf_variant, 0);      // test build: 1 = the register-staged kernel (two planes per tile) for every size
 
 namespace {
-constexpr int TD = 2, TH = 8, TW = 8;
+using fdn_wg::TD;
+using fdn_wg::TH;
+using fdn_wg::TW;                        // tile: 2 x 8 x 8 voxels (wgrad64_plan.h)
 constexpr int XH = TH + 2, XW = TW + 2;
 constexpr int XROWS = TD * XH * XW;      // 200
 constexpr int ZROWS = TD * TH * TW;      // 128
@@ -478,7 +481,6 @@ __global__ __launch_bounds__(256, 2) void wgrad64_bf16_dma_kernel(Wgrad64BfArgs 
 // gets S = 168 / layers splits (a multiple of 8), so the launch still fills the chip about once, but a workgroup walks layers-times
 // more tiles of ITS layer between prologue and output stage and the partial sums (and the one batched reduction) shrink by that factor.
 // At the cfg4 low-res grid (4 x 32^3) a layer alone on the chip leaves a walk 12 one-plane tiles.
-constexpr int kWgBfBatchMax = 8;
 struct Wgrad64BfBatch {
     Wgrad64BfArgs a;                     // x / dz / partial of layer 0; everything else common to the layers
     const uint16_t* x[kWgBfBatchMax];
@@ -517,120 +519,58 @@ __global__ __launch_bounds__(256) void wgrad64_reduce_batch_kernel(const float* 
     if (qtr == 0) ((f32x4*)t.dw[blockIdx.y])[e4] = (v + red[0][col]) + (red[1][col] + red[2][col]);
 }
 
-namespace {
-int wgrad64bf_splits(int N, int D, int H, int W) {
-    // (counted in two-plane tiles for both kernels: the one-plane kernel then has >= 4 tiles per walk)
-    const long long ntiles = (long long)N * ((D + TD - 1) / TD) * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
-    long long S = 168;                 // 3*168 = 504 workgroups ~ 2 per CU; a multiple of 8 (one walk set per XCD)
-    while (S > 8 && ntiles / 2 < S) S -= 8;
-    return (int)S;
-}
-}  // namespace
+int fdn_wgrad64_bf16_variant_hook() { return fdn_wgrad64bf_variant; }
 
-size_t fdn_wgrad64_bf16_workspace_bytes(int N, int D, int H, int W) {
-    return (size_t)wgrad64bf_splits(N, D, H, W) * 27 * 4096 * sizeof(float);
-}
-
-int fdn_wgrad64_bf16_launch(const uint16_t* x, const uint16_t* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H,
-                            int W, hipStream_t s) {
-    Wgrad64BfArgs a;
-    a.x = x; a.dz = dz; a.partial = (float*)ws;
-    a.N = N; a.D = D; a.H = H; a.W = W;
-    a.S = wgrad64bf_splits(N, D, H, W);
-    a.dbg = fdn_wgrad64bf_dbg;
-    if (ws_bytes < (size_t)a.S * 27 * 4096 * sizeof(float)) {
+// The FDN_WG_BF16_DMA / _BF16_REG / _BF16_BATCH step of a plan (wgrad64_plan.h): x, dz, dw are the tables of the step's st.count layers.
+// _BF16_BATCH: the layers in ONE launch + one reduction, S = 168 / layers splits each
+int fdn_wgrad64_bf16_launch(const FdnWgrad64Step& st, const uint16_t* const* x, const uint16_t* const* dz, float* const* dw, void* ws,
+                            size_t ws_bytes, int N, int D, int H, int W, hipStream_t s) {
+    const bool batch = st.route == FDN_WG_BF16_BATCH, dma = st.route != FDN_WG_BF16_REG;
+    if (batch) FDN_REQUIRE(ws_bytes >= st.partial_bytes, "wgrad64_bf16 (batched): workspace too small");
+    else if (ws_bytes < st.partial_bytes) {
         fdn_set_error("wgrad64_bf16: workspace too small");
         return FDN_ERR_WORKSPACE;
     }
-    a.nth = (H + TH - 1) / TH; a.ntw = (W + TW - 1) / TW;
-    // the LDS-DMA kernel addresses x / dz through 32-bit buffer offsets; tensors of 4 GB and more keep the register-staged kernel
-    const long long bytes = (long long)N * D * H * W * 128;
-    if (bytes < (1ll << 32) - 4096 && !fdn_wgrad64bf_variant) {
-        a.bytes = (unsigned)bytes;
-        a.ntd = D;
-        a.ntiles = N * a.ntd * a.nth * a.ntw;
-        // depth segments: long enough for the plane reuse between the taps (<= 32 planes), short enough that every walk of
-        // every XCD gets >= ~4 units
-        int want = (int)((long long)a.ntiles / ((long long)a.S * 4));
-        want = want < 1 ? 1 : (want > 32 ? 32 : want);
-        a.nseg = (D + want - 1) / want;
-        a.seg_len = (D + a.nseg - 1) / a.nseg;
-        a.nseg = (D + a.seg_len - 1) / a.seg_len;
-        FDN_PLAN("fam=wgrad_bf16_dma op=wgrad dt=bf16 N=%d D=%d H=%d W=%d splits=%d nseg=%d grid=%d tiles=%d cus=%d", N, D, H, W, a.S, a.nseg, 3 * a.S,
+    Wgrad64BfBatch b;
+    WgBfDwTable t;
+    for (int i = 0; i < st.count; ++i) {
+        FDN_REQUIRE(x[i] && dz[i] && dw[i], "wgrad64_bf16 (batched): NULL pointer for layer %d", st.first + i);
+        b.x[i] = x[i]; b.dz[i] = dz[i]; t.dw[i] = dw[i];
+    }
+    for (int i = st.count; i < kWgBfBatchMax; ++i) { b.x[i] = nullptr; b.dz[i] = nullptr; t.dw[i] = nullptr; }
+    Wgrad64BfArgs& a = b.a;
+    a.x = x[0]; a.dz = dz[0]; a.partial = (float*)ws;
+    a.N = N; a.D = D; a.H = H; a.W = W;
+    a.S = st.splits;
+    a.dbg = fdn_wgrad64bf_dbg;
+    a.nth = fdn_wg::cdiv(H, TH); a.ntw = fdn_wg::cdiv(W, TW);
+    a.bytes = dma ? (unsigned)((long long)N * D * H * W * 128) : 0;       // (the LDS-DMA route: < 4 GB)
+    a.ntd = dma ? D : fdn_wg::cdiv(D, TD);
+    a.ntiles = st.tiles;
+    a.nseg = st.nseg; a.seg_len = st.seg_len;
+    if (batch) {
+        if (int rc = fdn_func_max_lds((const void*)wgrad64_bf16_dma_batch_kernel, DLDS_BYTES, "wgrad64_bf16_batch")) return rc;
+        FDN_PLAN("fam=wgrad_bf16_batch op=wgrad dt=bf16 N=%d D=%d H=%d W=%d layers=%d splits=%d nseg=%d grid=%d tiles=%d cus=%d", N, D, H, W, st.count,
+                 a.S, a.nseg, st.grid, a.ntiles, fdn_plan_cus());
+        hipLaunchKernelGGL(wgrad64_bf16_dma_batch_kernel, dim3(st.grid), dim3(256), DLDS_BYTES, s, b);
+        FDN_CHECK_LAUNCH("wgrad64_bf16_dma_batch_kernel");
+        hipLaunchKernelGGL(wgrad64_reduce_batch_kernel, dim3(27 * 1024 / 64, st.count), dim3(256), 0, s, (const float*)ws, t, a.S);
+        FDN_CHECK_LAUNCH("wgrad64_reduce_batch_kernel");
+        return FDN_OK;
+    }
+    if (dma) {
+        FDN_PLAN("fam=wgrad_bf16_dma op=wgrad dt=bf16 N=%d D=%d H=%d W=%d splits=%d nseg=%d grid=%d tiles=%d cus=%d", N, D, H, W, a.S, a.nseg, st.grid,
                  a.ntiles, fdn_plan_cus());
         if (int rc = fdn_func_max_lds((const void*)wgrad64_bf16_dma_kernel, DLDS_BYTES, "wgrad64_bf16")) return rc;
-        hipLaunchKernelGGL(wgrad64_bf16_dma_kernel, dim3(3 * a.S), dim3(256), DLDS_BYTES, s, a);
+        hipLaunchKernelGGL(wgrad64_bf16_dma_kernel, dim3(st.grid), dim3(256), DLDS_BYTES, s, a);
         FDN_CHECK_LAUNCH("wgrad64_bf16_dma_kernel");
     } else {
-        a.bytes = 0;
-        a.ntd = (D + TD - 1) / TD;
-        a.ntiles = N * a.ntd * a.nth * a.ntw;
-        FDN_PLAN("fam=wgrad_bf16_reg op=wgrad dt=bf16 N=%d D=%d H=%d W=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, a.S, 3 * a.S, a.ntiles, fdn_plan_cus());
-        hipLaunchKernelGGL(wgrad64_bf16_kernel, dim3(3 * a.S), dim3(256), LDS_BYTES, s, a);
+        FDN_PLAN("fam=wgrad_bf16_reg op=wgrad dt=bf16 N=%d D=%d H=%d W=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, a.S, st.grid, a.ntiles, fdn_plan_cus());
+        hipLaunchKernelGGL(wgrad64_bf16_kernel, dim3(st.grid), dim3(256), LDS_BYTES, s, a);
         FDN_CHECK_LAUNCH("wgrad64_bf16_kernel");
     }
-    hipLaunchKernelGGL(wgrad64_reduce_kernel, dim3(27 * 1024 / 64), dim3(256), 0, s, (const float*)ws, dw, a.S);
+    hipLaunchKernelGGL(wgrad64_reduce_kernel, dim3(27 * 1024 / 64), dim3(256), 0, s, (const float*)ws, dw[0], a.S);
     FDN_CHECK_LAUNCH("wgrad64_reduce_kernel");
-    return FDN_OK;
-}
-
-// ---- several layers of one grid: chunks of <= 7 layers, each ONE launch + one reduction (3 S layers ~ 504 workgroups) ----
-static int wgrad64bf_batch_splits(int chunk) { int S = (168 / chunk) & ~7; return S < 8 ? 8 : S; }
-bool fdn_wgrad64_bf16_batch_ok(int n_layers, int N, int D, int H, int W) {
-    const long long tiles1 = (long long)N * D * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);       // one-plane tiles of a layer
-    return n_layers >= 2 && (long long)N * D * H * W * 128 < (1ll << 32) - 4096 && !fdn_wgrad64bf_variant && tiles1 >= 4 * 80;     // every walk of every chunk size gets >= 4 tiles
-}
-size_t fdn_wgrad64_bf16_batch_workspace_bytes(int n_layers, int N, int D, int H, int W) {
-    const size_t one = fdn_wgrad64_bf16_workspace_bytes(N, D, H, W);
-    size_t all = 0;
-    for (int chunk = 2; chunk <= 7 && chunk <= n_layers; ++chunk) {
-        const size_t b = (size_t)chunk * wgrad64bf_batch_splits(chunk) * 27 * 4096 * sizeof(float);
-        if (b > all) all = b;
-    }
-    return all > one ? all : one;
-}
-int fdn_wgrad64_bf16_batch_launch(const uint16_t* const* x, const uint16_t* const* dz, float* const* dw, int n_layers, void* ws, size_t ws_bytes,
-                                  int N, int D, int H, int W, hipStream_t s) {
-    FDN_REQUIRE(fdn_wgrad64_bf16_batch_ok(n_layers, N, D, H, W), "wgrad64_bf16 (batched): %d layers of %dx%dx%dx%d are not batchable", n_layers, N, D, H, W);
-    FDN_REQUIRE(ws_bytes >= fdn_wgrad64_bf16_batch_workspace_bytes(n_layers, N, D, H, W), "wgrad64_bf16 (batched): workspace too small");
-    if (int rc = fdn_func_max_lds((const void*)wgrad64_bf16_dma_batch_kernel, DLDS_BYTES, "wgrad64_bf16_batch")) return rc;
-    for (int first = 0; first < n_layers;) {
-        int chunk = n_layers - first;
-        if (chunk > 7) chunk = (chunk == 8) ? 4 : 7;           // (8 = 4 + 4 rather than 7 + 1)
-        if (chunk == 1) {                                       // a lone layer: the single-layer launch
-            if (int rc = fdn_wgrad64_bf16_launch(x[first], dz[first], dw[first], ws, ws_bytes, N, D, H, W, s)) return rc;
-            first += 1;
-            continue;
-        }
-        Wgrad64BfBatch b;
-        WgBfDwTable t;
-        for (int i = 0; i < chunk; ++i) {
-            FDN_REQUIRE(x[first + i] && dz[first + i] && dw[first + i], "wgrad64_bf16 (batched): NULL pointer for layer %d", first + i);
-            b.x[i] = x[first + i]; b.dz[i] = dz[first + i]; t.dw[i] = dw[first + i];
-        }
-        for (int i = chunk; i < kWgBfBatchMax; ++i) { b.x[i] = nullptr; b.dz[i] = nullptr; t.dw[i] = nullptr; }
-        Wgrad64BfArgs& a = b.a;
-        a.x = b.x[0]; a.dz = b.dz[0]; a.partial = (float*)ws;
-        a.N = N; a.D = D; a.H = H; a.W = W;
-        a.S = wgrad64bf_batch_splits(chunk);
-        a.dbg = fdn_wgrad64bf_dbg;
-        a.nth = (H + TH - 1) / TH; a.ntw = (W + TW - 1) / TW;
-        a.bytes = (unsigned)((long long)N * D * H * W * 128);
-        a.ntd = D;
-        a.ntiles = N * a.ntd * a.nth * a.ntw;
-        int want = (int)((long long)a.ntiles / ((long long)a.S * 4));
-        want = want < 1 ? 1 : (want > 32 ? 32 : want);
-        a.nseg = (D + want - 1) / want;
-        a.seg_len = (D + a.nseg - 1) / a.nseg;
-        a.nseg = (D + a.seg_len - 1) / a.seg_len;
-        FDN_PLAN("fam=wgrad_bf16_batch op=wgrad dt=bf16 N=%d D=%d H=%d W=%d layers=%d splits=%d nseg=%d grid=%d tiles=%d cus=%d", N, D, H, W, chunk,
-                 a.S, a.nseg, 3 * a.S * chunk, a.ntiles, fdn_plan_cus());
-        hipLaunchKernelGGL(wgrad64_bf16_dma_batch_kernel, dim3(3 * a.S * chunk), dim3(256), DLDS_BYTES, s, b);
-        FDN_CHECK_LAUNCH("wgrad64_bf16_dma_batch_kernel");
-        hipLaunchKernelGGL(wgrad64_reduce_batch_kernel, dim3(27 * 1024 / 64, chunk), dim3(256), 0, s, (const float*)ws, t, a.S);
-        FDN_CHECK_LAUNCH("wgrad64_reduce_batch_kernel");
-        first += chunk;
-    }
     return FDN_OK;
 }
 

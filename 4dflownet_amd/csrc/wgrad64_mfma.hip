@@ -15,6 +15,7 @@
 //   x is re-read by the 3 depth-tap groups through L2; per tile a wave issues 9*TH*TW/2 MFMAs
 //   (64 cyc each) against 10 LDS reads per k-step, so the matrix pipe is the bottleneck by construction.
 #include "fdn_common.h"
+#include "wgrad64_plan.h"
 
 struct Wgrad64Args {
     const float* x;
@@ -234,16 +235,8 @@ __global__ __launch_bounds__(256) void wgrad64_reduce_kernel(const float* __rest
     if (qtr == 0) ((f32x4*)dw)[e4] = (t + red[0][col]) + (red[1][col] + red[2][col]);
 }
 
-namespace {
-constexpr int kTH = 4, kTW = 8;          // pipelined kernel: tiles of 1 x 4 x 8 voxels
-int wgrad64_splits(int N, int D, int H, int W) {
-    const long long ntiles = (long long)N * D * ((H + kTH - 1) / kTH) * ((W + kTW - 1) / kTW);
-    // 3 tap groups x S workgroups; two workgroups fit a CU -> aim for ~512 resident, at least 8 tiles each
-    long long S = 170;                 // 3*170 = 510 workgroups ~ 2 per CU
-    if (ntiles / 8 < S) S = ntiles / 8 > 0 ? ntiles / 8 : 1;
-    return (int)S;
-}
-}  // namespace
+using fdn_wg::kTH;
+using fdn_wg::kTW;          // pipelined kernel: tiles of 1 x 4 x 8 voxels
 
 // dw = sum over S of partial[S][27][64][64] (shared with the Winograd kernel, whose workgroups write the same layout)
 int fdn_wgrad64_reduce_launch(const float* partial, float* dw, int S, hipStream_t s) {
@@ -252,26 +245,21 @@ int fdn_wgrad64_reduce_launch(const float* partial, float* dw, int S, hipStream_
     return FDN_OK;
 }
 
-size_t fdn_wgrad64_workspace_bytes(int N, int D, int H, int W) {
-    return (size_t)wgrad64_splits(N, D, H, W) * 27 * 4096 * sizeof(float);
-}
-
-int fdn_wgrad64_launch(const float* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H,
+// the FDN_WG_DIRECT step of a plan (wgrad64_plan.h)
+int fdn_wgrad64_launch(const FdnWgrad64Step& st, const float* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H,
                        int W, hipStream_t s) {
+    FDN_REQUIRE(ws_bytes >= st.partial_bytes, "wgrad64: workspace too small");
     Wgrad64Args a;
     a.x = x; a.dz = dz; a.partial = (float*)ws;
     a.N = N; a.D = D; a.H = H; a.W = W;
-    a.ntd = D; a.nth = (H + kTH - 1) / kTH; a.ntw = (W + kTW - 1) / kTW;
-    a.ntiles = N * a.ntd * a.nth * a.ntw;
-    a.S = wgrad64_splits(N, D, H, W);
-    FDN_REQUIRE((long long)N * D * H * W * 256 < (1ll << 32), "wgrad64: x of %dx%dx%dx%dx64 floats exceeds the 32-bit buffer addressing", N, D, H, W);
-    a.bytes = (unsigned)((long long)N * D * H * W * 256);
-    FDN_PLAN("fam=wgrad_direct op=wgrad dt=f32 N=%d D=%d H=%d W=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, a.S, 3 * a.S, a.ntiles, fdn_plan_cus());
+    a.ntd = D; a.nth = fdn_wg::cdiv(H, kTH); a.ntw = fdn_wg::cdiv(W, kTW);
+    a.ntiles = st.tiles;
+    a.S = st.splits;
+    a.bytes = (unsigned)((long long)N * D * H * W * 256);           // (< 4 GB: the plan's addr32_ok)
+    FDN_PLAN("fam=wgrad_direct op=wgrad dt=f32 N=%d D=%d H=%d W=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, a.S, st.grid, a.ntiles, fdn_plan_cus());
     const size_t lds = (size_t)3 * ((kTH + 2) * (kTW + 2) + kTH * kTW) * 256;
     if (int rc = fdn_func_max_lds((const void*)wgrad64_pipe_kernel<kTH, kTW>, (int)lds, "wgrad64")) return rc;
     hipLaunchKernelGGL((wgrad64_pipe_kernel<kTH, kTW>), dim3(a.S, 3), dim3(256), lds, s, a);
     FDN_CHECK_LAUNCH("wgrad64_pipe_kernel");
-    hipLaunchKernelGGL(wgrad64_reduce_kernel, dim3(27 * 1024 / 64), dim3(256), 0, s, (const float*)ws, dw, a.S);
-    FDN_CHECK_LAUNCH("wgrad64_reduce_kernel");
-    return FDN_OK;
+    return fdn_wgrad64_reduce_launch((const float*)ws, dw, a.S, s);
 }

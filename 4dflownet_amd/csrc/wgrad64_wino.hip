@@ -34,6 +34,7 @@
 // kernel has none to spare), dz's second plane in two extra registers.  The depth output transform runs in the reduction kernel
 // (wgrad64_reduce_dep_kernel), which sums the S x 4 partials with the G^T weights.
 #include "fdn_common.h"
+#include "wgrad64_plan.h"
 #include <type_traits>
 
 namespace {
@@ -51,7 +52,9 @@ struct WgWinoArgs {
 
 FDN_HOOK_VAR(int, fdn_wgrad64_wino_dbg, 0);
 
-constexpr int WTH = 6, WTG = 2, WTW = 4 * WTG;          // tile: 1 x 6 x 8 voxels
+using fdn_wg::WTH;
+using fdn_wg::WTG;
+using fdn_wg::WTW;                                      // tile: 1 x 6 x 8 voxels (wgrad64_plan.h)
 constexpr int GROWB = 1536;                             // bytes per (line, group): 2 parities x (64 ch x 2 floats + 64 ch x 1 float)
 constexpr int VBYTES = (WTH + 2) * WTG * GROWB;         // transformed x: 8 halo lines
 constexpr int ZBYTES = WTH * WTG * GROWB;               // transformed dz
@@ -434,7 +437,6 @@ __global__ __launch_bounds__(512, 1) void wgrad64_wino_kernel(WgWinoArgs p) {
 // layer gets S = 64 / layers splits, so the launch still fills the chip once, but a workgroup walks layers-times more tiles of ITS layer
 // between the prologue and the output transform, and the partial sums it writes (and the reduction reads) shrink by the same factor.
 // At the cfg2 low-res grid (8 x 24^3: 4.6 tiles per workgroup when a layer has the chip to itself) that is where the time goes.
-constexpr int kWgBatchMax = 32;
 struct WgWinoBatch {
     WgWinoArgs a;                        // x / dz / partial unused; everything else common to the layers
     const float* x[kWgBatchMax];
@@ -454,15 +456,6 @@ __global__ __launch_bounds__(512, 1) void wgrad64_wino_batch_kernel(WgWinoBatch 
     p.x = b.x[layer]; p.dz = b.dz[layer];
     p.partial = b.a.partial + (size_t)layer * b.a.S * (NP * 9) * 4096;
     wgrad64_wino_body<DEP>(p, qg - layer * per, smem);
-}
-
-// DEP: (D / 2) depth units and 4 workgroups per split
-bool wgrad64_wino_dep_ok(int D) { return D >= 2 && (D & 1) == 0; }
-int wgrad64_wino_splits(int N, int D, int H, int W, bool dep) {
-    const long long ntiles = (long long)N * (dep ? D / 2 : D) * ((H + WTH - 1) / WTH) * ((W + WTW - 1) / WTW);
-    long long S = dep ? 64 : 85;       // 4 * 64 = 256 / 3 * 85 = 255 workgroups: one (8 waves, 126-150 KB of LDS) per CU
-    if (ntiles < S) S = ntiles > 0 ? ntiles : 1;
-    return (int)S;
 }
 
 // dw[a][k] = sum_s sum_xd G^T[a][xd] partial[s][xd][k]  (k over the 9 (b,t) taps x 64 x 64), G^T = (1,1/2,1/2,0) (0,1/2,-1/2,0) (0,1/2,1/2,1).
@@ -503,90 +496,49 @@ extern "C" int fdn_debug_set_wgrad64_wino_dbg(int bits) { fdn_wgrad64_wino_dbg =
 
 FDN_HOOK_VAR(int, fdn_wgrad64_wino_nodep, 0);          // test build: 1 = never the depth transform (the round-2 kernel)
 
-size_t fdn_wgrad64_wino_workspace_bytes(int N, int D, int H, int W) {
-    const size_t a = (size_t)wgrad64_wino_splits(N, D, H, W, false) * 27, b = wgrad64_wino_dep_ok(D) ? (size_t)wgrad64_wino_splits(N, D, H, W, true) * 36 : 0;
-    return (a > b ? a : b) * 4096 * sizeof(float);
-}
+int fdn_wgrad64_wino_nodep_hook() { return fdn_wgrad64_wino_nodep; }
 
-int fdn_wgrad64_wino_launch(const float* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H,
-                            int W, hipStream_t s, int algo) {
-    // F(3,2) along D on top of F(3,4) along W whenever D is even (FDN_ALGO_WINO_W keeps the W-only kernel selectable)
-    const bool dep = wgrad64_wino_dep_ok(D) && algo != FDN_ALGO_WINO_W && !fdn_wgrad64_wino_nodep;
-    WgWinoArgs a;
-    a.x = x; a.dz = dz; a.partial = (float*)ws;
-    a.N = N; a.D = D; a.H = H; a.W = W;
-    a.DT = dep ? D / 2 : D;
-    a.nth = (H + WTH - 1) / WTH; a.ntw = (W + WTW - 1) / WTW;
-    a.ntiles = N * a.DT * a.nth * a.ntw;
-    a.S = wgrad64_wino_splits(N, D, H, W, dep);
-    FDN_REQUIRE((long long)N * D * H * W * 256 < (1ll << 32), "wgrad64: x of %dx%dx%dx%dx64 floats exceeds the 32-bit buffer addressing", N, D, H, W);
-    FDN_REQUIRE(ws_bytes >= (size_t)a.S * (dep ? 36 : 27) * 4096 * sizeof(float), "wgrad64 (winograd): workspace too small");
-    a.bytes = (unsigned)((long long)N * D * H * W * 256);
-    a.dbg = fdn_wgrad64_wino_dbg;
-    FDN_PLAN("fam=wgrad_wino op=wgrad dt=f32 N=%d D=%d H=%d W=%d dep=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, dep, a.S, (dep ? 4 : 3) * a.S,
-             a.ntiles, fdn_plan_cus());
-    if (dep) {
-        const size_t lds = (size_t)3 * WBUFB + XSCRATCH + ZSCRATCH;
-        if (int rc = fdn_func_max_lds((const void*)wgrad64_wino_kernel<true>, (int)lds, "wgrad64_wino")) return rc;
-        hipLaunchKernelGGL(wgrad64_wino_kernel<true>, dim3(4 * a.S), dim3(512), lds, s, a);
-        FDN_CHECK_LAUNCH("wgrad64_wino_kernel");
-        WgDwTable t;
-        t.dw[0] = dw;
-        hipLaunchKernelGGL(wgrad64_reduce_dep_kernel, dim3(9 * 1024 / 64), dim3(64 * kRedParts), 0, s, (const float*)ws, t, a.S);
-        FDN_CHECK_LAUNCH("wgrad64_reduce_dep_kernel");
-        return FDN_OK;
-    }
-    const size_t lds = (size_t)3 * WBUFB;
-    if (int rc = fdn_func_max_lds((const void*)wgrad64_wino_kernel<false>, (int)lds, "wgrad64_wino")) return rc;
-    hipLaunchKernelGGL(wgrad64_wino_kernel<false>, dim3(3 * a.S), dim3(512), lds, s, a);
-    FDN_CHECK_LAUNCH("wgrad64_wino_kernel");
-    return fdn_wgrad64_reduce_launch((const float*)ws, dw, a.S, s);
-}
-
-// ---- several layers of one grid in ONE launch (+ one reduction launch) ----
-// Applicable when the depth-transformed kernel is (D even, FDN_ALGO_AUTO) and the layers' partial sums fit 32-bit tile counts;
-// fdn_conv3d_wgrad_batch (api.hip) falls back to per-layer launches otherwise.
-bool fdn_wgrad64_wino_batch_ok(int n_layers, int D, int algo) {
-    return n_layers >= 2 && n_layers <= kWgBatchMax && wgrad64_wino_dep_ok(D) && algo != FDN_ALGO_WINO_W && algo != FDN_ALGO_DIRECT && !fdn_wgrad64_wino_nodep;
-}
-static int wgrad64_wino_batch_splits(int n_layers, int N, int D, int H, int W) {
-    const long long ntiles = (long long)N * (D / 2) * ((H + WTH - 1) / WTH) * ((W + WTW - 1) / WTW);
-    long long S = 64 / n_layers;         // 4 S n_layers <= 256 workgroups: one per CU, the chip filled once
-    if (S < 1) S = 1;
-    if (ntiles < S) S = ntiles > 0 ? ntiles : 1;
-    return (int)S;
-}
-size_t fdn_wgrad64_wino_batch_workspace_bytes(int n_layers, int N, int D, int H, int W) {
-    return (size_t)n_layers * wgrad64_wino_batch_splits(n_layers, N, D, H, W) * 36 * 4096 * sizeof(float);
-}
-int fdn_wgrad64_wino_batch_launch(const float* const* x, const float* const* dz, float* const* dw, int n_layers, void* ws, size_t ws_bytes,
-                                  int N, int D, int H, int W, hipStream_t s) {
-    FDN_REQUIRE(fdn_wgrad64_wino_batch_ok(n_layers, D, FDN_ALGO_AUTO), "wgrad64 (batched): %d layers at depth %d are not batchable", n_layers, D);
-    FDN_REQUIRE((long long)N * D * H * W * 256 < (1ll << 32), "wgrad64: x of %dx%dx%dx%dx64 floats exceeds the 32-bit buffer addressing", N, D, H, W);
+// The FDN_WG_WINO_W / _WINO_DEP / _WINO_BATCH step of a plan (wgrad64_plan.h): x, dz, dw are the tables of the step's st.count layers.
+// _WINO_BATCH: the layers in ONE launch (+ one reduction launch), S = 64 / layers splits each
+int fdn_wgrad64_wino_launch(const FdnWgrad64Step& st, const float* const* x, const float* const* dz, float* const* dw, void* ws, size_t ws_bytes,
+                            int N, int D, int H, int W, hipStream_t s) {
+    const bool dep = st.route != FDN_WG_WINO_W, batch = st.route == FDN_WG_WINO_BATCH;
     WgWinoBatch b;
     WgDwTable t;
-    b.nl = n_layers;
-    for (int i = 0; i < n_layers; ++i) {
+    b.nl = st.count;
+    for (int i = 0; i < st.count; ++i) {
         FDN_REQUIRE(x[i] && dz[i] && dw[i], "wgrad64 (batched): NULL pointer for layer %d", i);
         b.x[i] = x[i]; b.dz[i] = dz[i]; t.dw[i] = dw[i];
     }
     WgWinoArgs& a = b.a;
-    a.x = nullptr; a.dz = nullptr; a.partial = (float*)ws;
+    a.x = batch ? nullptr : x[0]; a.dz = batch ? nullptr : dz[0]; a.partial = (float*)ws;
     a.N = N; a.D = D; a.H = H; a.W = W;
-    a.DT = D / 2;
-    a.nth = (H + WTH - 1) / WTH; a.ntw = (W + WTW - 1) / WTW;
-    a.ntiles = N * a.DT * a.nth * a.ntw;
-    a.S = wgrad64_wino_batch_splits(n_layers, N, D, H, W);
-    FDN_REQUIRE(ws_bytes >= fdn_wgrad64_wino_batch_workspace_bytes(n_layers, N, D, H, W), "wgrad64 (batched): workspace too small");
-    a.bytes = (unsigned)((long long)N * D * H * W * 256);
+    a.DT = dep ? D / 2 : D;
+    a.nth = fdn_wg::cdiv(H, WTH); a.ntw = fdn_wg::cdiv(W, WTW);
+    a.ntiles = st.tiles;
+    a.S = st.splits;
+    if (batch) FDN_REQUIRE(ws_bytes >= st.partial_bytes, "wgrad64 (batched): workspace too small");
+    else FDN_REQUIRE(ws_bytes >= st.partial_bytes, "wgrad64 (winograd): workspace too small");
+    a.bytes = (unsigned)((long long)N * D * H * W * 256);           // (< 4 GB: the plan's addr32_ok)
     a.dbg = fdn_wgrad64_wino_dbg;
-    FDN_PLAN("fam=wgrad_wino_batch op=wgrad dt=f32 N=%d D=%d H=%d W=%d layers=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, n_layers, a.S,
-             4 * a.S * n_layers, a.ntiles, fdn_plan_cus());
-    const size_t lds = (size_t)3 * WBUFB + XSCRATCH + ZSCRATCH;
-    if (int rc = fdn_func_max_lds((const void*)wgrad64_wino_batch_kernel<true>, (int)lds, "wgrad64_wino_batch")) return rc;
-    hipLaunchKernelGGL(wgrad64_wino_batch_kernel<true>, dim3(4 * a.S * n_layers), dim3(512), lds, s, b);
-    FDN_CHECK_LAUNCH("wgrad64_wino_batch_kernel");
-    hipLaunchKernelGGL(wgrad64_reduce_dep_kernel, dim3(9 * 1024 / 64, n_layers), dim3(64 * kRedParts), 0, s, (const float*)ws, t, a.S);
+    const size_t lds = (size_t)3 * WBUFB + (dep ? XSCRATCH + ZSCRATCH : 0);
+    if (!batch) {
+        FDN_PLAN("fam=wgrad_wino op=wgrad dt=f32 N=%d D=%d H=%d W=%d dep=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, dep, a.S, st.grid,
+                 a.ntiles, fdn_plan_cus());
+        const void* fn = dep ? (const void*)wgrad64_wino_kernel<true> : (const void*)wgrad64_wino_kernel<false>;
+        if (int rc = fdn_func_max_lds(fn, (int)lds, "wgrad64_wino")) return rc;
+        if (dep) hipLaunchKernelGGL(wgrad64_wino_kernel<true>, dim3(st.grid), dim3(512), lds, s, a);
+        else hipLaunchKernelGGL(wgrad64_wino_kernel<false>, dim3(st.grid), dim3(512), lds, s, a);
+        FDN_CHECK_LAUNCH("wgrad64_wino_kernel");
+    } else {
+        FDN_PLAN("fam=wgrad_wino_batch op=wgrad dt=f32 N=%d D=%d H=%d W=%d layers=%d splits=%d grid=%d tiles=%d cus=%d", N, D, H, W, st.count, a.S,
+                 st.grid, a.ntiles, fdn_plan_cus());
+        if (int rc = fdn_func_max_lds((const void*)wgrad64_wino_batch_kernel<true>, (int)lds, "wgrad64_wino_batch")) return rc;
+        hipLaunchKernelGGL(wgrad64_wino_batch_kernel<true>, dim3(st.grid), dim3(512), lds, s, b);
+        FDN_CHECK_LAUNCH("wgrad64_wino_batch_kernel");
+    }
+    if (!dep) return fdn_wgrad64_reduce_launch((const float*)ws, dw[0], a.S, s);
+    hipLaunchKernelGGL(wgrad64_reduce_dep_kernel, dim3(9 * 1024 / 64, st.count), dim3(64 * kRedParts), 0, s, (const float*)ws, t, a.S);
     FDN_CHECK_LAUNCH("wgrad64_reduce_dep_kernel");
     return FDN_OK;
 }

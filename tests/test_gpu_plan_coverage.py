@@ -591,6 +591,36 @@ def test_plan_case_matches_float64(fdn, key):
     assert key in reached, "case %s no longer reaches its plan %s; it reached:\n  %s" % (PLAN_CASES[key], key, "\n  ".join(sorted(reached)))
 
 
+@pytest.mark.parametrize("dt,dims,nl,launches", [
+    ("f32", (1, 8, 8, 8), 17, ["fam=wgrad_wino_batch layers=16 splits=4", "fam=wgrad_wino dep=1 splits=8"]),
+    ("bf16", (5, 16, 16, 16), 15, ["fam=wgrad_bf16_batch layers=7 splits=24", "fam=wgrad_bf16_batch layers=4 splits=40"] + ["fam=wgrad_bf16_batch layers=4 splits=40"])])
+def test_batch_steps_reuse_the_workspace_behind_each_other(fdn, dt, dims, nl, launches):
+    """A batch no product shape reaches: several steps of one plan (csrc/wgrad64_plan.h), each writing its partial sums over the ones the
+    step before has reduced.  fp32, 17 layers: a chunk of 16 and then a lone layer on the single-layer kernel -- bit-equal to the
+    single-layer entry point on the same operands.  bf16, 15 layers at the smallest grid with 320 one-plane tiles: 7 + 4 + 4 (no layer
+    count leaves a lone bf16 layer behind chunks: tests/test_wgrad64_plan.py).  Every layer of a chunk against float64."""
+    bf = dt == "bf16"
+    o = bops if bf else ops
+    g = torch.Generator(device="cuda").manual_seed(nl)
+    xs = [torch.randn(dims + (64,), device="cuda", generator=g).to(torch.bfloat16 if bf else torch.float32) for _ in range(nl)]
+    dzs = [torch.randn(dims + (64,), device="cuda", generator=g).to(torch.bfloat16 if bf else torch.float32) for _ in range(nl)]
+    dws = [torch.full((3, 3, 3, 64, 64), float("nan"), device="cuda") for _ in range(nl)]
+    with _lib.test_build() as lib, PlanTap(lib) as tap:
+        tap.take()
+        o.conv3d_wgrad_batch(xs, dzs, dws)
+        torch.cuda.synchronize()
+        recs = [r for _, r in tap.take()]
+        lone = o.conv3d_wgrad(xs[-1], dzs[-1], 3, 64, 64)[0] if not bf else None
+        torch.cuda.synchronize()
+    got = ["fam=%s %s splits=%s" % (r["fam"], "layers=" + r["layers"] if "layers" in r else "dep=" + r["dep"], r["splits"]) for r in recs]
+    assert got == launches
+    chunked = nl - 1 if not bf else nl
+    for i in range(chunked):
+        _wgrad_check(xs[i], dzs[i], dws[i], "%s %s layer %d of %d" % (dt, dims, i, nl))
+    if not bf:
+        assert torch.equal(dws[-1], lone), "the lone layer behind the chunk differs from fdn_conv3d_wgrad on the same operands"
+
+
 def test_gate_reports_a_forced_tile_without_a_case(fdn):
     """A tile shape outside the table (forced through the test hook) is named by the gate, with the shape that reached it."""
     with _lib.test_build() as lib:
