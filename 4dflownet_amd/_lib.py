@@ -126,6 +126,7 @@ DEBUG_SIGNATURES = {
     "fdn_debug_set_wgrad64_bf16_dbg": (c_i, [c_i]),
     "fdn_debug_set_wgrad64_bf16_variant": (c_i, [c_i]),
     "fdn_debug_wgrad64_plan": (c_i, [c_i] * 7 + [ctypes.c_char_p, c_sz]),
+    "fdn_debug_thin_partials": (c_i, [c_i] * 6 + [ctypes.POINTER(ctypes.c_longlong)]),
     "fdn_debug_plan_log": (c_i, [c_i]),
     "fdn_debug_plan_read": (c_sz, [ctypes.c_char_p, c_sz]),
 }

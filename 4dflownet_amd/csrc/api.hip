@@ -10,6 +10,7 @@
 #include <type_traits>
 #include <utility>
 #include "fdn_common.h"
+#include "thin_layers.h"
 #include "wgrad64_plan.h"
 
 static thread_local char g_err[512] = "";
@@ -84,31 +85,6 @@ extern "C" size_t fdn_debug_plan_read(char* buf, size_t n) {
 
 extern "C" int fdn_version(void) { return FDN_VERSION; }   // 161: fdn_conv64_dgrad_fused_multi; 160: FDN_CONV64_PACK_FLOATS = 423 * 4096 (+ the bf16 x 3 stream), FDN_ALGO_WINO_BF16X3
 extern "C" const char* fdn_last_error(void) { return g_err; }
-
-// small-channel kernels (small_convs.hip), templated on the activation storage type (float / uint16_t = bf16 bits)
-template <typename T> int fdn_conv_cin3_fwd_launch(const T* x, const float* w, const float* bias, T* y, int N, int D, int H,
-                                                   int W, int act, float alpha, hipStream_t s);
-template <typename T> int fdn_conv_cout1_fwd_launch(const T* x, const float* w, const float* bias, float* y, int N, int D,
-                                                    int H, int W, int ldy, int y_coff, int act, float alpha, hipStream_t s);
-template <typename T> int fdn_conv1x1_fwd_launch(const T* xa, const T* xb, const float* w, const float* bias, T* y,
-                                                 int64_t nvox, int act, float alpha, hipStream_t s);
-template <typename T> int fdn_conv1x1_dgrad_launch(const T* dz, const float* w, const T* ya, const T* yb, T* dxa, T* dxb,
-                                                   int64_t nvox, hipStream_t s);
-int fdn_conv_cout1_dgrad_launch(const float* dz, const float* w, float* dxpad, int N, int D, int H, int W, int lddz,
-                                int dz_coff, hipStream_t s);
-template <typename T> int fdn_wgrad_cin3_launch(const T* x, const T* dz, float* dw, void* ws, size_t ws_bytes, int N, int D,
-                                                int H, int W, hipStream_t s);
-template <typename T> int fdn_wgrad_cout1_launch(const T* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N,
-                                                 int D, int H, int W, int lddz, int dz_coff, hipStream_t s);
-template <typename T> int fdn_conv_cout1_dgrad_folded_launch(const char* who, const float* dz, const float* w, const T* y_prev, int act,
-                                                             float alpha, T* dz_prev, float* dbias_prev, void* workspace,
-                                                             size_t workspace_bytes, int N, int D, int H, int W, int lddz,
-                                                             int dz_coff, hipStream_t s, const uint16_t* ymask = nullptr);
-template <typename T> int fdn_wgrad_1x1_launch(const T* xa, const T* xb, const T* dz, float* dw, void* ws, size_t ws_bytes,
-                                               int64_t nvox, hipStream_t s);
-template <typename T> int fdn_bias_grad_launch(const T* dz, float* db, void* ws, size_t ws_bytes, int64_t nvox, int C,
-                                               int lddz, int dz_coff, hipStream_t s);
-size_t fdn_small_wgrad_workspace_bytes(int Cin, int Cout, int K);
 
 // An operator that exists once per storage type (fdn_x / fdn_x_bf16) has ONE body below: a static function template on T = float /
 // uint16_t (bf16 bits) that takes the called entry point's name as `who`; the extern "C" twins forward to it.  Where the two modes
@@ -451,14 +427,13 @@ static int conv3d_wgrad(const char* who, const T* x, const T* x2, const void* dz
         return FDN_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    const int64_t nvox = (int64_t)N * D * H * W;
     const T* dzt = (const T*)dz;
     int rc;
     if (Cin == 64 && Cout == 1 && K == 3) {
         const float* dzf = (const float*)dz;
         rc = fdn_wgrad_cout1_launch<T>(x, dzf, dw, workspace, workspace_bytes, N, D, H, W, lddz, dz_coff, s);
         if (rc != FDN_OK || !dbias) return rc;
-        return fdn_bias_grad_launch<float>(dzf, dbias, workspace, workspace_bytes, nvox, 1, lddz, dz_coff, s);
+        return fdn_bias_grad_launch<float>(dzf, dbias, workspace, workspace_bytes, N, D, H, W, 1, lddz, dz_coff, s);
     }
     if (Cin == 64 && Cout == 64 && K == 3) {
         FDN_REQUIRE(lddz == 64 && dz_coff == 0, "%s: 64->64 path reads dense dz rows", who);
@@ -468,13 +443,13 @@ static int conv3d_wgrad(const char* who, const T* x, const T* x2, const void* dz
         rc = fdn_wgrad_cin3_launch<T>(x, dzt, dw, workspace, workspace_bytes, N, D, H, W, s);
     } else if (Cin == 128 && Cout == 64 && K == 1) {
         FDN_REQUIRE(x2 && lddz == 64 && dz_coff == 0, "%s(1x1): needs x2, dense dz rows", who);
-        rc = fdn_wgrad_1x1_launch<T>(x, x2, dzt, dw, workspace, workspace_bytes, nvox, s);
+        rc = fdn_wgrad_1x1_launch<T>(x, x2, dzt, dw, workspace, workspace_bytes, N, D, H, W, s);
     } else {
         fdn_set_error("%s: unsupported (Cin=%d,Cout=%d,K=%d)", who, Cin, Cout, K);
         return FDN_ERR_UNSUPPORTED;
     }
     if (rc != FDN_OK || !dbias) return rc;
-    return fdn_bias_grad_launch<T>(dzt, dbias, workspace, workspace_bytes, nvox, Cout, lddz, dz_coff, s);
+    return fdn_bias_grad_launch<T>(dzt, dbias, workspace, workspace_bytes, N, D, H, W, Cout, lddz, dz_coff, s);
 }
 extern "C" int fdn_conv3d_wgrad(const float* x, const float* x2, const float* dz, float* dw, float* dbias,
                                 void* workspace, size_t workspace_bytes, int N, int D, int H, int W, int Cin, int Cout,
@@ -515,7 +490,7 @@ static int conv3d_wgrad_batch(const char* who, const T* const* x, const T* const
     if (dbias)                           // (stream-ordered behind the reduction: the workspace is free again)
         for (int i = 0; i < n_layers; ++i)
             if (dbias[i])
-                if (int rc = fdn_bias_grad_launch<T>(dz[i], dbias[i], workspace, workspace_bytes, (int64_t)N * D * H * W, 64, 64, 0, s)) return rc;
+                if (int rc = fdn_bias_grad_launch<T>(dz[i], dbias[i], workspace, workspace_bytes, N, D, H, W, 64, 64, 0, s)) return rc;
     return FDN_OK;
 }
 extern "C" int fdn_conv3d_wgrad_batch(const float* const* x, const float* const* dz, float* const* dw, float* const* dbias, int n_layers,

@@ -6,6 +6,7 @@
 // columns are gathered straight from it (edge clamp == SYMMETRIC p=1), so nothing is staged in LDS.
 // Storage type T = float or bf16 bits (uint16_t); arithmetic fp32 in both.
 #include "fdn_common.h"
+#include "thin_layers.h"
 
 namespace {
 

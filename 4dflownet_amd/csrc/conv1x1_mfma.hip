@@ -9,6 +9,7 @@
 // lane), the voxel operand comes straight from global memory with 16-B loads -- nothing is staged in LDS.
 // Storage type T = float or bf16 bits (uint16_t); arithmetic is fp32 in both (exact products of the stored values).
 #include "fdn_common.h"
+#include "thin_layers.h"
 
 namespace {
 

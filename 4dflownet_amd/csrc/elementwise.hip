@@ -1112,62 +1112,54 @@ extern "C" int fdn_loss_metrics(const float* pred, const float* uh, const float*
     return loss_launch("fdn_loss_metrics", pred, uh, vh, wh, mask, out, dpred, scratch, N, V, 1, 1, 1, 0.f, 3, stream);
 }
 
+// The checks of the three entry points that take extents, under the called one's name, then the launches.  An entry point without kind,
+// non_fluid_weight or out_act passes the value that means "as before" (FDN_LOSS_MSE and 0, 1, FDN_ACT_NONE), which passes its check.
+static int loss_checked(const char* who, const float* pred, const float* uh, const float* vh, const float* wh, const float* mask, int kind,
+                        float kind_param, float div_weight, float non_fluid_weight, int out_act, float* out, float* dpred, float* scratch, int N,
+                        int D, int H, int W, void* stream) {
+    FDN_REQUIRE(pred && uh && vh && wh && mask && out && scratch, "%s: NULL operand", who);
+    FDN_REQUIRE(kind == FDN_LOSS_MSE || kind == FDN_LOSS_MAE || kind == FDN_LOSS_HUBER || kind == FDN_LOSS_CHARBONNIER,
+                "%s: kind %d is not a loss (FDN_LOSS_MSE, _MAE, _HUBER or _CHARBONNIER)", who, kind);
+    if (kind == FDN_LOSS_HUBER || kind == FDN_LOSS_CHARBONNIER)
+        FDN_REQUIRE(__builtin_isfinite(kind_param) && kind_param > 0.f, "%s: %s %g must be finite and > 0", who,
+                    kind == FDN_LOSS_HUBER ? "the Huber delta" : "the Charbonnier epsilon", (double)kind_param);
+    else
+        FDN_REQUIRE(kind_param == 0.f, "%s: %s takes no parameter, kind_param %g must be 0", who,
+                    kind == FDN_LOSS_MSE ? "FDN_LOSS_MSE" : "FDN_LOSS_MAE", (double)kind_param);
+    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "%s: extents N=%d D=%d H=%d W=%d must be positive", who, N, D, H, W);
+    FDN_REQUIRE((int64_t)D * H * W <= (int64_t)INT32_MAX, "%s: %d x %d x %d voxels per sample exceed 2^31 - 1", who, D, H, W);
+    FDN_REQUIRE(__builtin_isfinite(div_weight) && div_weight >= 0.f, "%s: div_weight %g must be finite and >= 0", who, (double)div_weight);
+    FDN_REQUIRE(__builtin_isfinite(non_fluid_weight) && non_fluid_weight >= 0.f, "%s: non_fluid_weight %g must be finite and >= 0", who,
+                (double)non_fluid_weight);
+    if (out_act != FDN_ACT_NONE && out_act != FDN_ACT_TANH) {
+        fdn_set_error("%s: out_act %d is not an activation of the heads (FDN_ACT_NONE or FDN_ACT_TANH)", who, out_act);
+        return FDN_ERR_UNSUPPORTED;
+    }
+    return loss_launch(who, pred, uh, vh, wh, mask, out, dpred, scratch, N, (int64_t)D * H * W, D, H, W, div_weight, 5, stream, non_fluid_weight,
+                       out_act, kind, kind_param);
+}
+
 extern "C" int fdn_loss_metrics_div(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask,
                                     float div_weight, float* out, float* dpred, float* scratch, int N, int D, int H, int W,
                                     void* stream) {
-    FDN_REQUIRE(pred && uh && vh && wh && mask && out && scratch, "fdn_loss_metrics_div: NULL operand");
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_loss_metrics_div: extents N=%d D=%d H=%d W=%d must be positive", N, D, H, W);
-    FDN_REQUIRE((int64_t)D * H * W <= (int64_t)INT32_MAX, "fdn_loss_metrics_div: %d x %d x %d voxels per sample exceed 2^31 - 1", D, H, W);
-    FDN_REQUIRE(__builtin_isfinite(div_weight) && div_weight >= 0.f, "fdn_loss_metrics_div: div_weight %g must be finite and >= 0",
-                (double)div_weight);
-    return loss_launch("fdn_loss_metrics_div", pred, uh, vh, wh, mask, out, dpred, scratch, N, (int64_t)D * H * W, D, H, W, div_weight, 5,
-                       stream);
+    return loss_checked("fdn_loss_metrics_div", pred, uh, vh, wh, mask, FDN_LOSS_MSE, 0.f, div_weight, 1.f, FDN_ACT_NONE, out, dpred, scratch, N, D,
+                        H, W, stream);
 }
 
 // the loss with the reference's non_fluid_weight and the heads' activation: the same three launches
 extern "C" int fdn_loss_metrics_act(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask,
                                     float div_weight, float non_fluid_weight, int out_act, float* out, float* dpred, float* scratch,
                                     int N, int D, int H, int W, void* stream) {
-    FDN_REQUIRE(pred && uh && vh && wh && mask && out && scratch, "fdn_loss_metrics_act: NULL operand");
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_loss_metrics_act: extents N=%d D=%d H=%d W=%d must be positive", N, D, H, W);
-    FDN_REQUIRE((int64_t)D * H * W <= (int64_t)INT32_MAX, "fdn_loss_metrics_act: %d x %d x %d voxels per sample exceed 2^31 - 1", D, H, W);
-    FDN_REQUIRE(__builtin_isfinite(div_weight) && div_weight >= 0.f, "fdn_loss_metrics_act: div_weight %g must be finite and >= 0",
-                (double)div_weight);
-    FDN_REQUIRE(__builtin_isfinite(non_fluid_weight) && non_fluid_weight >= 0.f,
-                "fdn_loss_metrics_act: non_fluid_weight %g must be finite and >= 0", (double)non_fluid_weight);
-    if (out_act != FDN_ACT_NONE && out_act != FDN_ACT_TANH) {
-        fdn_set_error("fdn_loss_metrics_act: out_act %d is not an activation of the heads (FDN_ACT_NONE or FDN_ACT_TANH)", out_act);
-        return FDN_ERR_UNSUPPORTED;
-    }
-    return loss_launch("fdn_loss_metrics_act", pred, uh, vh, wh, mask, out, dpred, scratch, N, (int64_t)D * H * W, D, H, W, div_weight, 5,
-                       stream, non_fluid_weight, out_act);
+    return loss_checked("fdn_loss_metrics_act", pred, uh, vh, wh, mask, FDN_LOSS_MSE, 0.f, div_weight, non_fluid_weight, out_act, out, dpred,
+                        scratch, N, D, H, W, stream);
 }
 
 // the data term under another penalty (FDN_LOSS_*): fdn_loss_metrics_act's checks, launches and buffers; FDN_LOSS_MSE is that call
 extern "C" int fdn_loss_metrics_kind(const float* pred, const float* uh, const float* vh, const float* wh, const float* mask, int kind,
                                      float kind_param, float div_weight, float non_fluid_weight, int out_act, float* out, float* dpred,
                                      float* scratch, int N, int D, int H, int W, void* stream) {
-    FDN_REQUIRE(pred && uh && vh && wh && mask && out && scratch, "fdn_loss_metrics_kind: NULL operand");
-    FDN_REQUIRE(kind == FDN_LOSS_MSE || kind == FDN_LOSS_MAE || kind == FDN_LOSS_HUBER || kind == FDN_LOSS_CHARBONNIER,
-                "fdn_loss_metrics_kind: kind %d is not a loss (FDN_LOSS_MSE, _MAE, _HUBER or _CHARBONNIER)", kind);
-    if (kind == FDN_LOSS_HUBER || kind == FDN_LOSS_CHARBONNIER)
-        FDN_REQUIRE(__builtin_isfinite(kind_param) && kind_param > 0.f, "fdn_loss_metrics_kind: %s %g must be finite and > 0",
-                    kind == FDN_LOSS_HUBER ? "the Huber delta" : "the Charbonnier epsilon", (double)kind_param);
-    else
-        FDN_REQUIRE(kind_param == 0.f, "fdn_loss_metrics_kind: %s takes no parameter, kind_param %g must be 0",
-                    kind == FDN_LOSS_MSE ? "FDN_LOSS_MSE" : "FDN_LOSS_MAE", (double)kind_param);
-    FDN_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "fdn_loss_metrics_kind: extents N=%d D=%d H=%d W=%d must be positive", N, D, H, W);
-    FDN_REQUIRE((int64_t)D * H * W <= (int64_t)INT32_MAX, "fdn_loss_metrics_kind: %d x %d x %d voxels per sample exceed 2^31 - 1", D, H, W);
-    FDN_REQUIRE(__builtin_isfinite(div_weight) && div_weight >= 0.f, "fdn_loss_metrics_kind: div_weight %g must be finite and >= 0",
-                (double)div_weight);
-    FDN_REQUIRE(__builtin_isfinite(non_fluid_weight) && non_fluid_weight >= 0.f,
-                "fdn_loss_metrics_kind: non_fluid_weight %g must be finite and >= 0", (double)non_fluid_weight);
-    if (out_act != FDN_ACT_NONE && out_act != FDN_ACT_TANH) {
-        fdn_set_error("fdn_loss_metrics_kind: out_act %d is not an activation of the heads (FDN_ACT_NONE or FDN_ACT_TANH)", out_act);
-        return FDN_ERR_UNSUPPORTED;
-    }
-    return loss_launch("fdn_loss_metrics_kind", pred, uh, vh, wh, mask, out, dpred, scratch, N, (int64_t)D * H * W, D, H, W, div_weight, 5,
-                       stream, non_fluid_weight, out_act, kind, kind_param);
+    return loss_checked("fdn_loss_metrics_kind", pred, uh, vh, wh, mask, kind, kind_param, div_weight, non_fluid_weight, out_act, out, dpred,
+                        scratch, N, D, H, W, stream);
 }
 
 extern "C" int fdn_volume_metrics(const void* pred, int pred_is_f64, const float* truth, const float* mask, int mask_frames,

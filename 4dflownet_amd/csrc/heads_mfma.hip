@@ -21,6 +21,7 @@
 // chain of the LDS patches, not matrix time, bounds that layout; with lane = TAP (every lane forms its tap's scalars for 16 voxels
 // straight from the dz halo), x requested a tile ahead and three workgroups per CU it runs 490 -> 355 us.
 #include "fdn_common.h"
+#include "thin_layers.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -55,7 +56,7 @@ __device__ __forceinline__ float head_act(float z, int act, float alpha) {
     return fdn_act(z, act, alpha);
 }
 
-constexpr int H_TD = 4, H_TH = 8, H_TW = 8;                 // forward tile: 256 outputs, one per thread
+constexpr int H_TD = kHeadTD, H_TH = kHeadTH, H_TW = kHeadTW;   // forward tile (thin_layers.h): 4 x 8 x 8 = 256 outputs, one per thread
 constexpr int H_XD = H_TD + 2, H_XH = H_TH + 2, H_XW = H_TW + 2;
 constexpr int H_HV = H_XD * H_XH * H_XW;                    // 600 halo voxels
 constexpr int H_NMT = (H_HV + 31) / 32;                     // 19 M-tiles of 32 halo voxels (+1 dummy slot: 5 per wave)
@@ -231,16 +232,16 @@ __global__ __launch_bounds__(256, 2) void head_fwd_kernel(const T* __restrict__ 
 template <typename T>
 int fdn_head_fwd_launch(const T* x, const float* w, const float* bias, float* y, int N, int D, int H, int W, int ldy, int y_coff,
                         int act, float alpha, hipStream_t s, int xcd_walk) {
-    const int ntd = (D + H_TD - 1) / H_TD, nth = (H + H_TH - 1) / H_TH, ntw = (W + H_TW - 1) / H_TW;
+    const FdnHeadTiles t(N, D, H, W);
     const size_t lds = (size_t)27 * H_HVP * sizeof(float);
     if (int rc = fdn_func_max_lds((const void*)head_fwd_kernel<T>, (int)lds, "head_fwd")) return rc;
     // persistent grid: every workgroup runs `iters` (a multiple of 3, see the kernel) tiles, at most 2 workgroups per CU
-    const int ntiles = N * ntd * nth * ntw;
+    const int ntiles = (int)t.tiles;
     const int iters = 3 * ((ntiles + 3 * 512 - 1) / (3 * 512));
     const int grid = (ntiles + iters - 1) / iters;
     FDN_PLAN("fam=head_fwd op=fwd dt=%s N=%d D=%d H=%d W=%d iters=%d last=%d grid=%d tiles=%d cus=%d", sizeof(T) == 2 ? "bf16" : "f32", N, D, H, W,
              iters, ntiles - (grid - 1) * iters, grid, ntiles, fdn_plan_cus());
-    hipLaunchKernelGGL(head_fwd_kernel<T>, dim3((unsigned)grid), dim3(256), lds, s, x, w, bias, y, N, D, H, W, ntd, nth, ntw, iters,
+    hipLaunchKernelGGL(head_fwd_kernel<T>, dim3((unsigned)grid), dim3(256), lds, s, x, w, bias, y, N, D, H, W, t.ntd, t.nth, t.ntw, iters,
                        ldy, y_coff, act, alpha, xcd_walk);
     FDN_CHECK_LAUNCH("head_fwd_kernel");
     return FDN_OK;
@@ -585,25 +586,21 @@ __global__ __launch_bounds__(256, 2) void head_dgrad_kernel(const float* __restr
 
 }  // namespace
 
-// grid size of the persistent dgrad kernel = number of bias partial rows the caller must provide
-int fdn_head_dgrad_blocks(int N, int D, int H, int W) {
-    const long long ntiles = (long long)N * ((D + H_TD - 1) / H_TD) * ((H + H_TH - 1) / H_TH) * ((W + H_TW - 1) / H_TW);
-    return (int)(ntiles < 1024 ? ntiles : 1024);
-}
-
+// the persistent grid = the FDN_THIN_HEAD_DBIAS rows the caller provides as bpart
 template <typename T>
 int fdn_head_dgrad_launch(const float* dz, const float* w, const T* y_prev, int act, float alpha, T* dz_prev, float* bpart, int N,
                           int D, int H, int W, int lddz, int dz_coff, hipStream_t s, const uint16_t* ymask) {
-    const int ntd = (D + H_TD - 1) / H_TD, nth = (H + H_TH - 1) / H_TH, ntw = (W + H_TW - 1) / H_TW;
+    const FdnHeadTiles t(N, D, H, W);
+    const int grid = fdn_thin_partials(FDN_THIN_HEAD_DBIAS, sizeof(T) == 2, N, D, H, W, true).rows;
 #ifdef FDN_TEST_HOOKS
     {   // walk: the longest tile walk of any workgroup, in the classes 1 / 2 / >= 3 (one tile; the halo double buffer used once; its parity flipped back)
-        const int tiles = N * ntd * nth * ntw, grid = fdn_head_dgrad_blocks(N, D, H, W), walk = (tiles + grid - 1) / grid;
+        const int tiles = (int)t.tiles, walk = (tiles + grid - 1) / grid;
         FDN_PLAN("fam=head_dgrad op=dgrad dt=%s N=%d D=%d H=%d W=%d mask=%d walk=%d grid=%d tiles=%d cus=%d", sizeof(T) == 2 ? "bf16" : "f32", N, D, H,
                  W, ymask != nullptr, walk < 3 ? walk : 3, grid, tiles, fdn_plan_cus());
     }
 #endif
-    hipLaunchKernelGGL(head_dgrad_kernel<T>, dim3((unsigned)fdn_head_dgrad_blocks(N, D, H, W)), dim3(256), 0, s, dz, w, y_prev, act,
-                       alpha, dz_prev, bpart, N, D, H, W, ntd, nth, ntw, lddz, dz_coff, ymask);
+    hipLaunchKernelGGL(head_dgrad_kernel<T>, dim3((unsigned)grid), dim3(256), 0, s, dz, w, y_prev, act, alpha, dz_prev, bpart, N, D, H, W,
+                       t.ntd, t.nth, t.ntw, lddz, dz_coff, ymask);
     FDN_CHECK_LAUNCH("head_dgrad_kernel");
     return FDN_OK;
 }
@@ -927,26 +924,21 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 3 : 2) void head_wgrad_kernel
 
 }  // namespace
 
-// persistent grid = partial rows the caller provides: two workgroups per CU for fp32 storage (54.5 KB of LDS), three for bf16 (37.6 KB, 153 VGPRs)
-int fdn_head_wgrad_blocks(int N, int D, int H, int W, int elem_bytes) {
-    const long long ntiles = (long long)N * ((D + H_TD - 1) / H_TD) * ((H + H_TH - 1) / H_TH) * ((W + H_TW - 1) / H_TW);
-    const long long cap = elem_bytes == 2 ? 768 : 512;
-    return (int)(ntiles < cap ? ntiles : cap);
-}
-
+// the persistent grid = the FDN_THIN_WGRAD_COUT1 rows the caller provides as partial
 template <typename T>
 int fdn_head_wgrad_launch(const T* x, const float* dz, float* partial, int N, int D, int H, int W, int lddz, int dz_coff,
                           hipStream_t s) {
-    const int ntd = (D + H_TD - 1) / H_TD, nth = (H + H_TH - 1) / H_TH, ntw = (W + H_TW - 1) / H_TW;
+    const FdnHeadTiles t(N, D, H, W);
+    const int grid = fdn_thin_partials(FDN_THIN_WGRAD_COUT1, sizeof(T) == 2, N, D, H, W, true).rows;
 #ifdef FDN_TEST_HOOKS
     {   // walk: as in fdn_head_dgrad_launch
-        const int tiles = N * ntd * nth * ntw, grid = fdn_head_wgrad_blocks(N, D, H, W, (int)sizeof(T)), walk = (tiles + grid - 1) / grid;
+        const int tiles = (int)t.tiles, walk = (tiles + grid - 1) / grid;
         FDN_PLAN("fam=head_wgrad op=wgrad dt=%s N=%d D=%d H=%d W=%d walk=%d grid=%d tiles=%d cus=%d", sizeof(T) == 2 ? "bf16" : "f32", N, D, H, W,
                  walk < 3 ? walk : 3, grid, tiles, fdn_plan_cus());
     }
 #endif
-    hipLaunchKernelGGL(head_wgrad_kernel<T>, dim3((unsigned)fdn_head_wgrad_blocks(N, D, H, W, (int)sizeof(T))), dim3(256), 0, s, x, dz, partial, N, D,
-                       H, W, ntd, nth, ntw, lddz, dz_coff);
+    hipLaunchKernelGGL(head_wgrad_kernel<T>, dim3((unsigned)grid), dim3(256), 0, s, x, dz, partial, N, D, H, W, t.ntd, t.nth, t.ntw, lddz,
+                       dz_coff);
     FDN_CHECK_LAUNCH("head_wgrad_kernel");
     return FDN_OK;
 }

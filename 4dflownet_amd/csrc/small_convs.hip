@@ -3,6 +3,7 @@
 // network's FLOPs and are HBM/L2-bound, so they are plain coalesced VALU kernels (no MFMA reshaping):
 // 256-B channel rows are always read/written by 16 lanes x 16 B or 64 lanes x 4 B.
 #include "fdn_common.h"
+#include "thin_layers.h"
 
 namespace {
 
@@ -564,20 +565,18 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
         out[e] = ((red[0][ei] + red[1][ei]) + (red[2][ei] + red[3][ei])) + ((red[4][ei] + red[5][ei]) + (red[6][ei] + red[7][ei]));
 }
 
-constexpr int kSmallBlocks = 512;   // partial-sum blocks of the thin-layer wgrad / bias kernels
-constexpr int kSmallRows = 768;     // partial rows the workspace holds: the bf16 head wgrad runs three workgroups per CU (heads_mfma.hip)
-
-int reduce_partials(const float* partial, float* out, int nparts, int nelem, hipStream_t s) {
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((nelem + 31) / 32), dim3(256), 0, s, partial, out, nparts, nelem);
+// out = the sum of the p.rows partial rows a launch left in ws
+int reduce_partials(const void* ws, float* out, const FdnThinPartials& p, hipStream_t s) {
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((p.row_floats + 31) / 32), dim3(256), 0, s, (const float*)ws, out, p.rows, p.row_floats);
     FDN_CHECK_LAUNCH("reduce_partials_kernel");
     return FDN_OK;
 }
 
-int nblocks_for(int64_t items, int per_block, int cap) {
-    int64_t b = (items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > cap) b = cap;
-    return (int)b;
+// the launcher's own guard (api.hip checks the size query, which is no smaller, first)
+int partials_fit(const char* who, const FdnThinPartials& p, const void* ws, size_t ws_bytes) {
+    if (ws && ws_bytes >= p.bytes()) return FDN_OK;
+    fdn_set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, p.bytes());
+    return FDN_ERR_WORKSPACE;
 }
 
 }  // namespace
@@ -585,30 +584,30 @@ int nblocks_for(int64_t items, int per_block, int cap) {
 size_t fdn_small_wgrad_workspace_bytes(int Cin, int Cout, int K) {
     size_t elems = (size_t)K * K * K * Cin * Cout;
     if (elems < 64) elems = 64;
-    return (size_t)kSmallRows * elems * sizeof(float);
+    return (size_t)kThinRowsMax * elems * sizeof(float);
 }
 
-// Launchers, templated on the activation storage type T (float, or uint16_t = bf16 bits); parameters, parameter
-// gradients, the 64->1 heads' output (the prediction) and its gradient are always fp32.
-// cin3_mfma.hip: the im2col-GEMM formulation of the two 3 -> 64 kernels (default); the VALU kernels of this file stay selectable
-// for A/B runs in the test build (fdn_debug_set_cin3_mfma(0)) and serve odd W in the weight gradient
-template <typename T> int fdn_conv_cin3_fwd_mfma_launch(const T* x, const float* w, const float* bias, T* y, int N, int D, int H,
-                                                        int W, int act, float alpha, hipStream_t s);
-template <typename T> int fdn_wgrad_cin3_mfma_launch(const T* x, const T* dz, float* partial, int nblocks, int N, int D, int H,
-                                                     int W, hipStream_t s);
+// The launchers (thin_layers.h).  The MFMA formulations of cin3_mfma.hip, conv1x1_mfma.hip and heads_mfma.hip are the default; the VALU
+// kernels of this file stay selectable for A/B runs in the test build (fdn_debug_set_cin3_mfma / _conv1x1_mfma / _heads_mfma (0)) and
+// serve odd W in the 3 -> 64 weight gradient
 FDN_HOOK_VAR(int, fdn_cin3_use_mfma, 1);
-// conv1x1_mfma.hip: the 1x1x1 (64+64) -> 64 layer and its gradients as MFMA GEMMs (default; the VALU kernels stay selectable in the
-// test build: fdn_debug_set_conv1x1_mfma(0))
-template <typename T> int fdn_conv1x1_fwd_mfma_launch(const T* xa, const T* xb, const float* w, const float* bias, T* y, int64_t nvox,
-                                                      int act, float alpha, hipStream_t s);
-template <typename T> int fdn_conv1x1_dgrad_mfma_launch(const T* dz, const float* w, const T* ya, const T* yb, T* dxa, T* dxb,
-                                                        int64_t nvox, hipStream_t s);
-template <typename T> int fdn_wgrad_1x1_mfma_launch(const T* xa, const T* xb, const T* dz, float* partial, int nblocks, int64_t nvox,
-                                                    hipStream_t s);
 FDN_HOOK_VAR(int, fdn_conv1x1_use_mfma, 1);
+FDN_HOOK_VAR(int, fdn_heads_use_mfma, 1);
+// the partial rows of `op` under the hooks as they are set (the 3 -> 64 and the bias rows are the same either way)
+static FdnThinPartials thin_partials(FdnThinOp op, bool bf16, int N, int D, int H, int W) {
+    return fdn_thin_partials(op, bf16, N, D, H, W, (op == FDN_THIN_WGRAD_1X1 ? fdn_conv1x1_use_mfma : fdn_heads_use_mfma) != 0);
+}
 #ifdef FDN_TEST_HOOKS
 extern "C" int fdn_debug_set_cin3_mfma(int on) { fdn_cin3_use_mfma = on; return FDN_OK; }
 extern "C" int fdn_debug_set_conv1x1_mfma(int on) { fdn_conv1x1_use_mfma = on; return FDN_OK; }
+extern "C" int fdn_debug_set_heads_mfma(int on) { fdn_heads_use_mfma = on; return FDN_OK; }
+// out = {rows, row_floats, bytes} of fdn_thin_partials for op (an FdnThinOp) under the hooks as they are set; needs no device
+extern "C" int fdn_debug_thin_partials(int op, int bf16, int N, int D, int H, int W, long long* out) {
+    FDN_REQUIRE(op >= 0 && op < FDN_THIN_OPS && out, "fdn_debug_thin_partials: bad op %d or NULL out", op);
+    const FdnThinPartials p = thin_partials((FdnThinOp)op, bf16 != 0, N, D, H, W);
+    out[0] = p.rows; out[1] = p.row_floats; out[2] = (long long)p.bytes();
+    return FDN_OK;
+}
 #endif
 
 template <typename T>
@@ -626,22 +625,6 @@ int fdn_conv_cin3_fwd_launch(const T* x, const float* w, const float* bias, T* y
     return fdn_conv_cin3_fwd_mfma_launch<T>(x, w, bias, y, N, D, H, W, act, alpha, s);
 }
 
-// heads_mfma.hip: the MFMA formulation of the three 64 -> 1 head kernels (default); the VALU kernels of this file stay
-// selectable for A/B runs (fdn_debug_set_heads_mfma(0))
-template <typename T> int fdn_head_fwd_launch(const T* x, const float* w, const float* bias, float* y, int N, int D, int H,
-                                              int W, int ldy, int y_coff, int act, float alpha, hipStream_t s, int xcd_walk);
-template <typename T> int fdn_head_dgrad_launch(const float* dz, const float* w, const T* y_prev, int act, float alpha, T* dz_prev,
-                                                float* bpart, int N, int D, int H, int W, int lddz, int dz_coff, hipStream_t s,
-                                                const uint16_t* ymask);
-int fdn_head_dgrad_blocks(int N, int D, int H, int W);
-template <typename T> int fdn_head_wgrad_launch(const T* x, const float* dz, float* partial, int N, int D, int H, int W, int lddz,
-                                                int dz_coff, hipStream_t s);
-int fdn_head_wgrad_blocks(int N, int D, int H, int W, int elem_bytes);
-FDN_HOOK_VAR(int, fdn_heads_use_mfma, 1);
-#ifdef FDN_TEST_HOOKS
-extern "C" int fdn_debug_set_heads_mfma(int on) { fdn_heads_use_mfma = on; return FDN_OK; }
-#endif
-
 template <typename T>
 int fdn_conv_cout1_fwd_launch(const T* x, const float* w, const float* bias, float* y, int N, int D, int H, int W, int ldy,
                               int y_coff, int act, float alpha, hipStream_t s) {
@@ -649,7 +632,7 @@ int fdn_conv_cout1_fwd_launch(const T* x, const float* w, const float* bias, flo
     if (!fdn_heads_use_mfma) {
         FDN_REFUSE_TANH(act, "fdn_conv3d_fwd(64->1, VALU kernel)");       // (head_fwd_kernel's epilogue alone has it)
         const int64_t nvox = (int64_t)N * D * H * W;
-        hipLaunchKernelGGL(conv_cout1_fwd_kernel<T>, dim3(nblocks_for(nvox, 16, 8192)), dim3(256), 0, s, x, w, bias, y, N, D, H,
+        hipLaunchKernelGGL(conv_cout1_fwd_kernel<T>, dim3(fdn_blocks_for(nvox, 16, 8192)), dim3(256), 0, s, x, w, bias, y, N, D, H,
                            W, ldy, y_coff, act, alpha);
         FDN_CHECK_LAUNCH("conv_cout1_fwd_kernel");
         return FDN_OK;
@@ -663,7 +646,7 @@ int fdn_conv1x1_fwd_launch(const T* xa, const T* xb, const float* w, const float
                            float alpha, hipStream_t s) {
 #ifdef FDN_TEST_HOOKS
     if (!fdn_conv1x1_use_mfma) {
-        hipLaunchKernelGGL(conv1x1_fwd_kernel<T>, dim3(nblocks_for(nvox, 64, 2048)), dim3(256), 0, s, xa, xb, w, bias, y, nvox,
+        hipLaunchKernelGGL(conv1x1_fwd_kernel<T>, dim3(fdn_blocks_for(nvox, 64, 2048)), dim3(256), 0, s, xa, xb, w, bias, y, nvox,
                            act, alpha);
         FDN_CHECK_LAUNCH("conv1x1_fwd_kernel");
         return FDN_OK;
@@ -677,7 +660,7 @@ int fdn_conv1x1_dgrad_launch(const T* dz, const float* w, const T* ya, const T* 
                              hipStream_t s) {
 #ifdef FDN_TEST_HOOKS
     if (!fdn_conv1x1_use_mfma) {
-        hipLaunchKernelGGL(conv1x1_dgrad_kernel<T>, dim3(nblocks_for(nvox, 32, 2048)), dim3(256), 0, s, dz, w, ya, yb, dxa, dxb,
+        hipLaunchKernelGGL(conv1x1_dgrad_kernel<T>, dim3(fdn_blocks_for(nvox, 32, 2048)), dim3(256), 0, s, dz, w, ya, yb, dxa, dxb,
                            nvox);
         FDN_CHECK_LAUNCH("conv1x1_dgrad_kernel");
         return FDN_OK;
@@ -689,42 +672,40 @@ int fdn_conv1x1_dgrad_launch(const T* dz, const float* w, const T* ya, const T* 
 int fdn_conv_cout1_dgrad_launch(const float* dz, const float* w, float* dxpad, int N, int D, int H, int W, int lddz,
                                 int dz_coff, hipStream_t s) {
     const int64_t npos = (int64_t)N * (D + 2) * (H + 2) * (W + 2);
-    hipLaunchKernelGGL(conv_cout1_dgrad_kernel, dim3(nblocks_for(npos, 4 * 16, 4096)), dim3(256), 0, s, dz, w, dxpad, N,
+    hipLaunchKernelGGL(conv_cout1_dgrad_kernel, dim3(fdn_blocks_for(npos, 4 * 16, 4096)), dim3(256), 0, s, dz, w, dxpad, N,
                        D, H, W, lddz, dz_coff);
     FDN_CHECK_LAUNCH("conv_cout1_dgrad_kernel");
     return FDN_OK;
 }
 
 template <typename T>
-int fdn_wgrad_cin3_launch(const T* x, const T* dz, float* dw, void* ws, size_t, int N, int D, int H, int W, hipStream_t s) {
-    const int64_t nvox = (int64_t)N * D * H * W;
-    const int nb = nblocks_for(nvox, 4 * 32, kSmallBlocks);
+int fdn_wgrad_cin3_launch(const T* x, const T* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H, int W, hipStream_t s) {
+    const FdnThinPartials p = thin_partials(FDN_THIN_WGRAD_CIN3, sizeof(T) == 2, N, D, H, W);
+    if (int rc = partials_fit("wgrad_cin3", p, ws, ws_bytes)) return rc;
     if (fdn_cin3_use_mfma && (W & 1) == 0) {
-        if (int rc = fdn_wgrad_cin3_mfma_launch<T>(x, dz, (float*)ws, nb, N, D, H, W, s)) return rc;
-        return reduce_partials((const float*)ws, dw, nb, 81 * 64, s);
+        if (int rc = fdn_wgrad_cin3_mfma_launch<T>(x, dz, (float*)ws, p.rows, N, D, H, W, s)) return rc;
+        return reduce_partials(ws, dw, p, s);
     }
-    hipLaunchKernelGGL(wgrad_cin3_kernel<T>, dim3(nb), dim3(256), 0, s, x, dz, (float*)ws, N, D, H, W);
+    hipLaunchKernelGGL(wgrad_cin3_kernel<T>, dim3(p.rows), dim3(256), 0, s, x, dz, (float*)ws, N, D, H, W);
     FDN_CHECK_LAUNCH("wgrad_cin3_kernel");
-    return reduce_partials((const float*)ws, dw, nb, 81 * 64, s);
+    return reduce_partials(ws, dw, p, s);
 }
 
 template <typename T>
-int fdn_wgrad_cout1_launch(const T* x, const float* dz, float* dw, void* ws, size_t, int N, int D, int H, int W, int lddz,
+int fdn_wgrad_cout1_launch(const T* x, const float* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H, int W, int lddz,
                            int dz_coff, hipStream_t s) {
+    const FdnThinPartials p = thin_partials(FDN_THIN_WGRAD_COUT1, sizeof(T) == 2, N, D, H, W);
+    if (int rc = partials_fit("wgrad_cout1", p, ws, ws_bytes)) return rc;
 #ifdef FDN_TEST_HOOKS
     if (!fdn_heads_use_mfma) {
-        const int nrows = N * (D + 2) * (H + 2);
-        const int nb = nrows < kSmallBlocks ? nrows : kSmallBlocks;
         const size_t lds = (size_t)(((9 * (W + 4) + 3) & ~3) + 4 * 27 * 64) * sizeof(float);
-        hipLaunchKernelGGL(wgrad_cout1_kernel<T>, dim3(nb), dim3(256), lds, s, x, dz, (float*)ws, N, D, H, W, lddz, dz_coff);
+        hipLaunchKernelGGL(wgrad_cout1_kernel<T>, dim3(p.rows), dim3(256), lds, s, x, dz, (float*)ws, N, D, H, W, lddz, dz_coff);
         FDN_CHECK_LAUNCH("wgrad_cout1_kernel");
-        return reduce_partials((const float*)ws, dw, nb, 27 * 64, s);
+        return reduce_partials(ws, dw, p, s);
     }
 #endif
-    const int nbm = fdn_head_wgrad_blocks(N, D, H, W, (int)sizeof(T));          // <= kSmallBlocks partial rows of 27*64
-    const int rc = fdn_head_wgrad_launch<T>(x, dz, (float*)ws, N, D, H, W, lddz, dz_coff, s);
-    if (rc != FDN_OK) return rc;
-    return reduce_partials((const float*)ws, dw, nbm, 27 * 64, s);
+    if (int rc = fdn_head_wgrad_launch<T>(x, dz, (float*)ws, N, D, H, W, lddz, dz_coff, s)) return rc;      // (its grid: the same p.rows)
+    return reduce_partials(ws, dw, p, s);
 }
 
 template <typename T>
@@ -734,60 +715,50 @@ int fdn_conv_cout1_dgrad_folded_launch(const char* who, const float* dz, const f
     FDN_REQUIRE(dz && w && dz_prev && N > 0 && D > 0 && H > 0 && W > 0, "%s: bad argument", who);
     FDN_REQUIRE(!(ymask && sizeof(T) == 4) || (W % 4 == 0 && fdn_heads_use_mfma), "%s: the fp32 sign mask (planar words) needs W %% 4 == 0", who);
 #ifdef FDN_TEST_HOOKS
+    if (!fdn_heads_use_mfma) FDN_REQUIRE(W <= 4096, "%s: W too large for the row stage", who);
+#endif
+    const FdnThinPartials p = thin_partials(FDN_THIN_HEAD_DBIAS, sizeof(T) == 2, N, D, H, W);
+    float* bpart = dbias_prev ? (float*)workspace : nullptr;
+    if (dbias_prev)
+        if (int rc = partials_fit(who, p, workspace, workspace_bytes)) return rc;
+#ifdef FDN_TEST_HOOKS
     if (!fdn_heads_use_mfma) {
-        FDN_REQUIRE(W <= 4096, "%s: W too large for the row stage", who);
-        const int nrows = N * D * H;
-        const int nb = nrows < 2048 ? nrows : 2048;
-        if (dbias_prev && (!workspace || workspace_bytes < (size_t)nb * 64 * sizeof(float))) {
-            fdn_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, (size_t)nb * 64 * sizeof(float));
-            return FDN_ERR_WORKSPACE;
-        }
         const size_t lds = (size_t)(27 * 64 + 9 * W + 16) * sizeof(float);
-        hipLaunchKernelGGL(conv_cout1_dgrad_folded_kernel<T>, dim3(nb), dim3(256), lds, s, dz, w, y_prev, act, alpha, dz_prev,
-                           dbias_prev ? (float*)workspace : nullptr, N, D, H, W, lddz, dz_coff);
+        hipLaunchKernelGGL(conv_cout1_dgrad_folded_kernel<T>, dim3(p.rows), dim3(256), lds, s, dz, w, y_prev, act, alpha, dz_prev, bpart, N, D, H,
+                           W, lddz, dz_coff);
         FDN_CHECK_LAUNCH("conv_cout1_dgrad_folded_kernel");
-        if (dbias_prev) return reduce_partials((const float*)workspace, dbias_prev, nb, 64, s);
-        return FDN_OK;
+        return dbias_prev ? reduce_partials(workspace, dbias_prev, p, s) : FDN_OK;
     }
 #endif
-    const int nb = fdn_head_dgrad_blocks(N, D, H, W);
-    if (dbias_prev && (!workspace || workspace_bytes < (size_t)nb * 64 * sizeof(float))) {
-        fdn_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, (size_t)nb * 64 * sizeof(float));
-        return FDN_ERR_WORKSPACE;
-    }
-    const int rc = fdn_head_dgrad_launch<T>(dz, w, y_prev, act, alpha, dz_prev, dbias_prev ? (float*)workspace : nullptr, N, D,
-                                            H, W, lddz, dz_coff, s, ymask);
-    if (rc != FDN_OK) return rc;
-    if (dbias_prev) return reduce_partials((const float*)workspace, dbias_prev, nb, 64, s);
-    return FDN_OK;
+    if (int rc = fdn_head_dgrad_launch<T>(dz, w, y_prev, act, alpha, dz_prev, bpart, N, D, H, W, lddz, dz_coff, s, ymask)) return rc;   // (its grid: p.rows)
+    return dbias_prev ? reduce_partials(workspace, dbias_prev, p, s) : FDN_OK;
 }
 
 template <typename T>
-int fdn_wgrad_1x1_launch(const T* xa, const T* xb, const T* dz, float* dw, void* ws, size_t, int64_t nvox, hipStream_t s) {
+int fdn_wgrad_1x1_launch(const T* xa, const T* xb, const T* dz, float* dw, void* ws, size_t ws_bytes, int N, int D, int H, int W, hipStream_t s) {
+    const int64_t nvox = (int64_t)N * D * H * W;
+    const FdnThinPartials p = thin_partials(FDN_THIN_WGRAD_1X1, sizeof(T) == 2, N, D, H, W);
+    if (int rc = partials_fit("wgrad_1x1", p, ws, ws_bytes)) return rc;
 #ifdef FDN_TEST_HOOKS
     if (!fdn_conv1x1_use_mfma) {
-        const int nb = nblocks_for(nvox, 32 * 4, kSmallBlocks);
-        hipLaunchKernelGGL(wgrad_1x1_kernel<T>, dim3(nb), dim3(256), 0, s, xa, xb, dz, (float*)ws, nvox);
+        hipLaunchKernelGGL(wgrad_1x1_kernel<T>, dim3(p.rows), dim3(256), 0, s, xa, xb, dz, (float*)ws, nvox);
         FDN_CHECK_LAUNCH("wgrad_1x1_kernel");
-        return reduce_partials((const float*)ws, dw, nb, 128 * 64, s);
+        return reduce_partials(ws, dw, p, s);
     }
 #endif
-    // one workgroup per CU (128 KB of LDS for the cross-wave sum); >= 64 voxel pairs per wave
-    int nbm = (int)((nvox / 2 + 255) / 256);
-    nbm = nbm < 1 ? 1 : (nbm > 256 ? 256 : nbm);
-    if (int rc = fdn_wgrad_1x1_mfma_launch<T>(xa, xb, dz, (float*)ws, nbm, nvox, s)) return rc;
-    return reduce_partials((const float*)ws, dw, nbm, 128 * 64, s);
+    if (int rc = fdn_wgrad_1x1_mfma_launch<T>(xa, xb, dz, (float*)ws, p.rows, nvox, s)) return rc;
+    return reduce_partials(ws, dw, p, s);
 }
 
 template <typename T>
-int fdn_bias_grad_launch(const T* dz, float* db, void* ws, size_t ws_bytes, int64_t nvox, int C, int lddz, int dz_coff,
+int fdn_bias_grad_launch(const T* dz, float* db, void* ws, size_t ws_bytes, int N, int D, int H, int W, int C, int lddz, int dz_coff,
                          hipStream_t s) {
     if (C != 64 && C != 1) { fdn_set_error("bias_grad: unsupported C=%d", C); return FDN_ERR_UNSUPPORTED; }
-    const int nb = nblocks_for(nvox, C == 64 ? 4 * 64 : 256 * 16, C == 64 ? 256 : kSmallBlocks);
-    if (ws_bytes < (size_t)nb * C * sizeof(float)) { fdn_set_error("bias_grad: workspace too small"); return FDN_ERR_WORKSPACE; }
-    hipLaunchKernelGGL(bias_grad_kernel<T>, dim3(nb), dim3(256), 0, s, dz, (float*)ws, nvox, C, lddz, dz_coff);
+    const FdnThinPartials p = thin_partials(C == 64 ? FDN_THIN_BIAS64 : FDN_THIN_BIAS1, sizeof(T) == 2, N, D, H, W);
+    if (int rc = partials_fit("bias_grad", p, ws, ws_bytes)) return rc;
+    hipLaunchKernelGGL(bias_grad_kernel<T>, dim3(p.rows), dim3(256), 0, s, dz, (float*)ws, (int64_t)N * D * H * W, C, lddz, dz_coff);
     FDN_CHECK_LAUNCH("bias_grad_kernel");
-    return reduce_partials((const float*)ws, db, nb, C, s);
+    return reduce_partials(ws, db, p, s);
 }
 
 // explicit instantiations used by api.hip
@@ -805,7 +776,7 @@ int fdn_bias_grad_launch(const T* dz, float* db, void* ws, size_t ws_bytes, int6
     template int fdn_conv_cout1_dgrad_folded_launch<T>(const char*, const float*, const float*, const T*, int, float, T*,      \
                                                        float*, void*, size_t, int, int, int, int, int, int, hipStream_t,      \
                                                        const uint16_t*);                                                      \
-    template int fdn_wgrad_1x1_launch<T>(const T*, const T*, const T*, float*, void*, size_t, int64_t, hipStream_t);           \
-    template int fdn_bias_grad_launch<T>(const T*, float*, void*, size_t, int64_t, int, int, int, hipStream_t);
+    template int fdn_wgrad_1x1_launch<T>(const T*, const T*, const T*, float*, void*, size_t, int, int, int, int, hipStream_t); \
+    template int fdn_bias_grad_launch<T>(const T*, float*, void*, size_t, int, int, int, int, int, int, int, hipStream_t);
 FDN_INSTANTIATE_SMALL(float)
 FDN_INSTANTIATE_SMALL(uint16_t)
